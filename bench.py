@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark of the MI355X NTT library.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--api dropin|plan]
-                    [--no-cpu-baseline] [--no-traffic] [--no-e2e]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-traffic] [--no-e2e] ...]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Default = BASELINE.json's metric configuration (configs[1], "c2"): forward Merge NTT, 64-bit, N = 2^16,
@@ -17,9 +17,16 @@ library call (all of its kernel launches) over one batch of synthetic random pol
     c5  RNS Merge u64 2^16 x 512 per GPU, 8 primes, X^N+1                 (weak scaling)
 
 Multi-GPU: rank r owns its own shard (polynomials are independent): the timed region has
-no data-path collective, only the barrier and the MAX-reduction of the elapsed time.  With N > 1 the run
-also reports (outside `value`) the end-to-end leg of SURVEY.md 8e(ii): RCCL broadcast of the twiddle
+no data-path collective, only the barrier and the MAX-reduction of the elapsed time.  With N > 1 and --full the
+run also reports (outside `value`) the end-to-end leg of SURVEY.md 8e(ii): RCCL broadcast of the twiddle
 table, scatter of a batch that starts on rank 0, transform, gather back -- each part timed on its own.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the benchmark
+measures or checks, each outside the timed steps: the CPU baseline and bit-exact check against the reference CPU
+build, PMC traffic, socket power, the other API form, the C4 shard overheads, the other BASELINE configs (c2 forward,
+one GPU) and the multi-GPU end-to-end leg; the --no-* switches leave single parts of it out.
+
+--dump-outputs DIR writes what the last timed step computed, as float64 .npy files (see dump_outputs).
 
 Prints ONE JSON line on rank 0 (DESIGN.md "Measurement" has the roofline arithmetic).
 """
@@ -463,6 +470,39 @@ def gpu_sample_for_check(g, cfg, case, polys):
     return g.to_host(case["d_out"][:n].view(p4.n1, p4.n2).t().contiguous().view(-1))
 
 
+DUMP_COEFFS = 1 << 20  # coefficients per dumped buffer: 16 MiB as 64-bit halves; c3 dumps two buffers
+
+
+def dump_index(size):
+    """The flat indices --dump-outputs keeps of a buffer of `size` coefficients (sorted; None = all of them)."""
+    if size <= DUMP_COEFFS:
+        return None
+    return np.unique(np.random.default_rng(0xD0).integers(0, size, DUMP_COEFFS))
+
+
+def dump_outputs(g, cfg, case, out_dir):
+    """--dump-outputs: what a caller of the timed path receives after its last step, as DIR/<name>.npy -- `output`
+    (the buffer the Merge / RNS step writes) or, for the c3 pair, `forward` and `inverse` (what each call writes).  A
+    buffer above DUMP_COEFFS coefficients is sampled at flat indices drawn from a fixed seed and the buffer size only,
+    so two builds run with the same arguments write arrays that compare element for element.  float64 holds a 32-bit
+    word exactly; a 64-bit word is written as its two 32-bit halves (last axis: low, high) so that no bit is rounded."""
+    import torch
+    bufs = {"forward": case["d_out"], "inverse": case["d_back"]} if cfg["kind"] == "4step" else {"output": case["d_out"]}
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, t in bufs.items():
+        flat = t.reshape(-1)
+        idx = dump_index(flat.numel())
+        if idx is not None:
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        w = g.to_host(flat)
+        if cfg["bits"] == 64:
+            a = np.stack([w & np.uint64(0xFFFFFFFF), w >> np.uint64(32)], axis=-1).astype(np.float64)
+        else:
+            a = w.astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def fourstep_buffers_check(case):
     """c3, after the timed steps, on the device, over the WHOLE batch: every copy of the `distinct` polynomials in the
     forward output d_mid equals the first one (whose polynomial 0 the CPU leg checks), and the inverse output d_back
@@ -535,7 +575,7 @@ def c4_shard_overheads(g, cfg, dev, shard_batch=1024):
 
 
 # ------------------------------------------------------------------ the other BASELINE configs
-# What the default run (C2 forward, the headline) times BESIDE its line, so that one driver-owned run witnesses every
+# What the --full run of C2 forward (the headline) times BESIDE its line, so that one driver-owned run witnesses every
 # BASELINE.json config: (key, config, direction, steps, warmup).  Same HIP-event bracket on the launch stream, same
 # bit-exact check against the reference CPU build, PMC traffic from two child passes over all of them.
 OTHER_CONFIGS = (("c2_inv", "c2", "inv", 20, 5), ("c5", "c5", "fwd", 20, 5), ("c5_inv", "c5", "inv", 20, 5),
@@ -896,8 +936,8 @@ def run_sweep(g, args, dist_mod, dist, rank, world, dev):
             torch.cuda.synchronize()
             del keep
         return
-    traffic, tinfo = (None, "disabled / multi-GPU run")
-    if world == 1 and not args.no_traffic:
+    traffic, tinfo = (None, "disabled / multi-GPU run" if args.full else "measured with --full")
+    if args.full and world == 1 and not args.no_traffic:
         traffic, tinfo = sweep_traffic(args, points)
     for k, (kind, bits, logn, batch) in enumerate(points):
         first, step, x0, y0_get, keep = sweep_case(g, kind, bits, logn, batch, dev, rank, args.direction == "inv")
@@ -950,7 +990,7 @@ def run_sweep(g, args, dist_mod, dist, rank, world, dev):
                                  "traffic_over_algorithmic": (traffic[k] / alg) if traffic else None}}
             if k == 0:
                 line["roofline"]["traffic_info"] = tinfo
-            if not args.no_cpu_baseline and world == 1:
+            if args.full and not args.no_cpu_baseline and world == 1:
                 line["cpu_baseline"] = sweep_cpu(kind, bits, logn, x0, y0, args.direction == "inv")
                 if not line["cpu_baseline"]["gpu_output_bit_exact"]:
                     raise SystemExit("bench --sweep: GPU result differs from the CPU reference path at %s 2^%d" % (kind, logn))
@@ -963,8 +1003,14 @@ def run_sweep(g, args, dist_mod, dist, rank, world, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 200; c3: 10)")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps before them (default 20; c3: 2)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (CPU baseline and bit-exact check, PMC "
+                         "traffic, power, the other API form, C4 shard overheads, the other BASELINE configs, the "
+                         "multi-GPU end-to-end leg, the sweep's CPU and traffic columns); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float64)")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2")
     ap.add_argument("--api", choices=("dropin", "plan"), default="dropin")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -983,7 +1029,7 @@ def main():
                     help="c4: do not time the 1024-polynomial shard through the three call forms (kernel-trace runs: keeps the "
                          "per-kernel average about whole-batch launches)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default run (c2 forward, 1 GPU): do not time the other BASELINE configs beside the headline")
+                    help="--full run of c2 forward on 1 GPU: do not time the other BASELINE configs beside the headline")
     ap.add_argument("--sweep", action="store_true",
                     help="log2N sweep (Merge and 4-Step, forward), one JSON line per ring size with PMC bytes and the CPU column")
     ap.add_argument("--sweep-kinds", default="merge,4step")
@@ -997,8 +1043,13 @@ def main():
         cfg["metric"] = cfg["metric"].replace("forward-NTTs/sec", "inverse-NTTs/sec")
         cfg["workload"] = cfg["workload"].replace(" forward", " inverse") if " forward" in cfg["workload"] \
             else cfg["workload"] + " [inverse]"
-    if args.config == "c3" and args.steps == 200:
-        args.steps, args.warmup = 10, 2  # a step is ~25 ms and 16 GiB of traffic
+    c3 = args.config == "c3"  # a c3 step is ~25 ms and 16 GiB of traffic: fewer steps by default
+    args.steps = (10 if c3 else 200) if args.steps is None else args.steps
+    args.warmup = (2 if c3 else 20) if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.sweep:
+        ap.error("--dump-outputs writes the outputs of one config's timed steps; it does not apply to --sweep")
 
     # `python bench.py --gpus N` on its own: start the N ranks here (the driver's torchrun form sets WORLD_SIZE)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1013,6 +1064,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if not torch.cuda.is_available():
+        if args.dump_outputs:
+            raise SystemExit("bench: --dump-outputs needs a GPU (a dry run computes nothing)")
         return dry_run(cfg, args, dist_mod)
     # GPUNTT_BENCH_BACKEND=gloo (diagnostic): control-plane collectives over gloo and ranks mapped onto the devices that
     # exist (LOCAL_RANK % device count) -- lets a one-GPU box run the N-rank code path end to end; RCCL is the default
@@ -1043,7 +1096,8 @@ def main():
     if cfg["kind"] == "rns":
         cpu_polys = max(cfg["mod_count"], cpu_polys - cpu_polys % cfg["mod_count"])
     # taken NOW: the in-place timed calls below transform d_out again and again
-    y_first = gpu_sample_for_check(g, cfg, case, cpu_polys) if (rank == 0 and not args.child) else None
+    cpu_leg = args.full and not args.no_cpu_baseline and world == 1
+    y_first = gpu_sample_for_check(g, cfg, case, cpu_polys) if (rank == 0 and not args.child and cpu_leg) else None
     if args.child:
         for _ in range(args.steps):
             step()
@@ -1057,6 +1111,10 @@ def main():
         for _ in range(4):
             step()
         torch.cuda.synchronize()
+    # the in-place step feeds on its own output and the settle loop's count depends on the clock: start the chain
+    # again from the input, so that what the timed steps compute depends on the arguments alone (--dump-outputs)
+    if "first" in case:
+        case["first"]()
     for _ in range(args.warmup):
         step()
     e0 = torch.cuda.Event(enable_timing=True)
@@ -1076,10 +1134,12 @@ def main():
         t = torch.tensor([dev_ms], device=REDUCE_DEV or dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dev_ms = float(t[0])
+    if args.dump_outputs and rank == 0:  # before anything below runs the step again on the same buffers
+        dump_outputs(g, cfg, case, args.dump_outputs)
 
     # the other API form on the same buffers, timed the same way for the record (never `value`)
     other = None
-    if "other_step" in case:
+    if args.full and "other_step" in case:
         try:
             ostep = case["other_step"]()
             ostep()
@@ -1097,7 +1157,7 @@ def main():
             other = "failed: %r" % (e,)
 
     power = None
-    if world == 1 and not args.no_power:
+    if args.full and world == 1 and not args.no_power:
         try:
             power = measure_power(step, wall * 1e3 / args.steps)
         except Exception as e:  # informational only
@@ -1112,14 +1172,15 @@ def main():
             alg_bytes = 2 * n * (bits // 8) * per_step  # every coefficient read once + written once per transform
             achieved = alg_bytes / (call_ms * 1e-3) / 1e9
             traffic, traffic_info = None, None
-            if world == 1 and not args.no_traffic:
+            if args.full and world == 1 and not args.no_traffic:
                 traffic, traffic_info = measure_traffic(args.config, args.api, args.out_of_place, args.direction)
             quoted = False
             if traffic is None:
                 reason = traffic_info
                 traffic, src = quoted_traffic() if args.config == "c2" else (None, None)
                 quoted = traffic is not None
-                traffic_info = {"quoted": quoted, "source": src, "why_not_measured": reason or "disabled / multi-GPU run"}
+                traffic_info = {"quoted": quoted, "source": src,
+                                "why_not_measured": reason or ("disabled / multi-GPU run" if args.full else "measured with --full")}
             line = {
                 "metric": cfg["metric"],
                 "value": world * per_step * args.steps / wall,
@@ -1168,12 +1229,12 @@ def main():
                 line["power"] = power
             if e2e is not None:
                 line["end_to_end"] = e2e
-            if args.config == "c4" and not args.no_shard_overheads:
+            if args.full and args.config == "c4" and not args.no_shard_overheads:
                 try:
                     line["shard_of_8_gpus_call_overheads"] = c4_shard_overheads(g, cfg, dev)
                 except Exception as e:  # informational only
                     line["shard_of_8_gpus_call_overheads"] = {"error": repr(e)}
-            if not args.no_cpu_baseline and world == 1:  # reported at N = 1 only
+            if cpu_leg:  # reported at N = 1 only
                 if cfg["kind"] != "4step":
                     case["x_sample"] = case["x"][:cpu_polys * n]
                 else:
@@ -1191,7 +1252,7 @@ def main():
                         raise SystemExit("bench: 4-step batch check failed: %r" % (chk,))
                     line["cpu_baseline"]["checked_buffer"] = "polynomial 0 of the buffer the timed GPU_4STEP_NTT calls wrote"
                     line["batch_check"] = chk
-            if (args.config == "c2" and args.direction == "fwd" and args.api == "dropin" and world == 1
+            if (args.full and args.config == "c2" and args.direction == "fwd" and args.api == "dropin" and world == 1
                     and not args.out_of_place and not args.no_other_configs):
                 # (after everything the headline needs: nothing here can change `value`)
                 try:
@@ -1204,7 +1265,7 @@ def main():
     # more than one physical GPU: a collective that hangs must not cost the run its line.  A watchdog prints the line
     # without them and ends the rank.
     e2e = None
-    if dist is not None and not args.no_e2e and case.get("run_shard") is not None:
+    if args.full and dist is not None and not args.no_e2e and case.get("run_shard") is not None:
         import threading
         done = threading.Event()
 

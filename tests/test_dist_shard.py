@@ -96,18 +96,21 @@ def test_two_rank_gloo_sharded_equals_unsharded(tmp_path):
 def test_bench_starts_its_own_ranks_without_torchrun():
     """`python bench.py --gpus 2` with no WORLD_SIZE in the environment re-executes itself under
     torch.distributed.run; on a host without a GPU the ranks rendezvous over gloo and print the dry-run line
-    (value null): launch, sharding and timing plumbing are exercised before an 8-GPU lease ever is"""
+    (value null): launch, sharding and timing plumbing are exercised before an 8-GPU lease ever is.  On a one-GPU host
+    both ranks share cuda:0 with the control plane over gloo (GPUNTT_BENCH_BACKEND; RCCL takes one device per rank)."""
     import json
+    import torch
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    if torch.cuda.is_available() and torch.cuda.device_count() < 2:
+        env["GPUNTT_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
                         "--config", "c5"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
-    import torch
     if torch.cuda.is_available():
-        assert d["n_gpus"] == 2  # a real two-GPU run (or a launch error above)
+        assert d["n_gpus"] == 2 and d["steps"] == 3 and d["value"] > 0  # a real two-rank run (or a launch error above)
         return
     assert d["dry_run"] is True and d["value"] is None and d["n_gpus"] == 2 and d["steps"] == 3
     # weak scaling: every rank its own 512 polynomials, shard bounds multiples of the 8 primes

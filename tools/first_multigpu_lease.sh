@@ -19,10 +19,10 @@ for N in $GPUS; do
   STEPS+=("180|rccl_smoke_x$N|$TR --nproc-per-node $N --master-port {P} tools/rccl_smoke.py")
 done
 for N in $GPUS; do
-  STEPS+=("600|bench_c2_x$N|$TR --nproc-per-node $N --master-port {P} bench.py --gpus $N --steps 20 --warmup 5")
+  STEPS+=("600|bench_c2_x$N|$TR --nproc-per-node $N --master-port {P} bench.py --gpus $N --steps 20 --warmup 5 --full")
 done
 for N in $GPUS; do
-  STEPS+=("600|bench_c4_strong_x$N|$TR --nproc-per-node $N --master-port {P} bench.py --gpus $N --config c4 --steps 50 --warmup 10")
+  STEPS+=("600|bench_c4_strong_x$N|$TR --nproc-per-node $N --master-port {P} bench.py --gpus $N --config c4 --steps 50 --warmup 10 --full")
 done
 for N in $GPUS; do
   STEPS+=("1500|sweep_x$N|$TR --nproc-per-node $N --master-port {P} bench.py --gpus $N --sweep")
