@@ -8,6 +8,7 @@ src/include/gpuntt/ntt_4step/ntt_4step.cuh:46-49,278-308):
 
     GPU_NTT / GPU_INTT / GPU_NTT_Inplace / GPU_INTT_Inplace   (single modulus or RNS)
     GPU_4STEP_NTT / GPU_Transpose
+    GPU_Automorphism_NTT / GPU_Automorphism (extension: Galois automorphisms, gpuntt/ntt_merge/galois.cuh)
     Modulus, ntt_configuration, ntt_rns_configuration, ntt4step_configuration,
     ntt4step_rns_configuration, NTTParameters, NTTParameters4Step
 
@@ -95,8 +96,10 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "4step_params", "plan_workspace_bytes", "plan_create", "plan_execute", "plan_fast_path",
               "plan_destroy", "operator_gpu", "4step_plan_workspace_bytes", "4step_plan_create",
               "4step_plan_execute", "4step_plan_fast_path", "4step_plan_destroy",
-              "generate_power_table", "generate_4step_w", "butterfly_unit", "debug_recip_norm")
-    for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option"]
+              "generate_power_table", "generate_4step_w", "butterfly_unit", "debug_recip_norm",
+              "automorphism_ntt", "automorphism", "automorphism_rns")
+    for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option", "gpuntt_galois_element_u32",
+                                "gpuntt_automorphism_index_map"]
 
 # GPUNTT_* environment variables of the A/B scripts and tests -> library options.  The C++ library reads no
 # environment variable; this harness forwards them once, when it loads the library.
@@ -457,6 +460,84 @@ def GPU_PolyMul(device_a, device_b, device_out, forward_table, inverse_table, mo
         _check(fn(_ptr(device_a), _ptr(device_b), _ptr(device_out), _ptr(forward_table), _ptr(inverse_table),
                   _ptr(modulus), cfg.n_power, cfg.reduction_poly, _ptr(cfg.mod_inverse), _stream(cfg.stream),
                   batch_size, int(mod_count)))
+
+
+DOMAIN_NTT, DOMAIN_COEFFICIENT = 0, 1  # gpuntt_automorphism_index_map
+
+
+def _galois_elts(galois_elts):
+    vals = [galois_elts] if isinstance(galois_elts, int) else list(galois_elts)
+    if not all(isinstance(e, (int, np.integer)) and 0 <= int(e) < (1 << 32) for e in vals):
+        raise ValueError("Galois elements must be 32-bit unsigned integers")
+    return (ctypes.c_uint32 * max(1, len(vals)))(*[int(e) for e in vals]), len(vals)
+
+
+def _check_sizes(device_in, device_out, count, n_power, batch_size):
+    """the library cannot see tensor sizes: in must hold batch x N words, out count x batch x N"""
+    if 1 <= int(n_power) <= 28 and int(batch_size) > 0:
+        words = int(batch_size) << int(n_power)
+        if device_in.numel() < words or device_out.numel() < count * words:
+            raise ValueError("device_in needs %d words and device_out %d (galois_count x batch x N); got %d and %d"
+                             % (words, count * words, device_in.numel(), device_out.numel()))
+
+
+def GPU_Automorphism_NTT(device_in, device_out, galois_elts, n_power, reduction_poly, batch_size, stream=None):
+    """Extension (include/gpuntt/ntt_merge/galois.cuh): sigma_k for every odd k in galois_elts (an int or up to 64 of
+    them) applied to polynomials in GPU_NTT's output order -- a permutation, no modulus.  device_in holds batch x N
+    words, device_out len(galois_elts) x batch x N; the two must not overlap.  One kernel launch."""
+    _require_gpu(device_in, device_out)
+    arr, count = _galois_elts(galois_elts)
+    _check_sizes(device_in, device_out, count, n_power, batch_size)
+    fn = getattr(load_library(), "gpuntt_automorphism_ntt_u%d" % (device_in.element_size() * 8))
+    _check(fn(_ptr(device_in), _ptr(device_out), arr, count, int(n_power), int(reduction_poly), _stream(stream),
+              int(batch_size)))
+
+
+def GPU_Automorphism(device_in, device_out, galois_elts, modulus, n_power, reduction_poly, batch_size,
+                     mod_count=None, stream=None):
+    """Extension: sigma_k in the coefficient domain (negacyclic sign q - x for X_N_plus).  `modulus` is a Modulus or a
+    device tensor of Modulus<T> words with `mod_count` (RNS: polynomial p uses modulus p % mod_count).  Layout and
+    element rules as GPU_Automorphism_NTT."""
+    _require_gpu(device_in, device_out)
+    arr, count = _galois_elts(galois_elts)
+    _check_sizes(device_in, device_out, count, n_power, batch_size)
+    lib = load_library()
+    bits = device_in.element_size() * 8
+    if isinstance(modulus, Modulus):
+        fn = getattr(lib, "gpuntt_automorphism_u%d" % bits)
+        _check(fn(_ptr(device_in), _ptr(device_out), arr, count, modulus.c(), int(n_power), int(reduction_poly),
+                  _stream(stream), int(batch_size)))
+    else:
+        _require_gpu(modulus)
+        fn = getattr(lib, "gpuntt_automorphism_rns_u%d" % bits)
+        _check(fn(_ptr(device_in), _ptr(device_out), arr, count, _ptr(modulus), int(n_power), int(reduction_poly),
+                  _stream(stream), int(batch_size), int(mod_count)))
+
+
+def galois_element_for_rotation(steps, n_power):
+    """GaloisElementForRotation: 5^steps mod 2N (negative steps: the inverse)."""
+    out = ctypes.c_uint32()
+    _check(load_library().gpuntt_galois_element_u32(int(steps), int(n_power), 0, ctypes.byref(out)))
+    return int(out.value)
+
+
+def galois_element_for_conjugation(n_power):
+    """GaloisElementForConjugation: 2N - 1."""
+    out = ctypes.c_uint32()
+    _check(load_library().gpuntt_galois_element_u32(0, int(n_power), 1, ctypes.byref(out)))
+    return int(out.value)
+
+
+def automorphism_index_map(n_power, galois_elt, reduction_poly, domain=DOMAIN_NTT):
+    """Host (no GPU): uint32 array of N entries, the source the kernels read for every output slot (DOMAIN_NTT) or
+    coefficient (DOMAIN_COEFFICIENT; for X_N_plus an entry j >= N means -in[j - N])."""
+    if not 1 <= int(n_power) <= 28:
+        raise ValueError("Invalid n_power range!")
+    out = np.empty(1 << int(n_power), dtype=np.uint32)
+    _check(load_library().gpuntt_automorphism_index_map(int(n_power), ctypes.c_uint32(int(galois_elt) & 0xFFFFFFFF),
+                                                        int(reduction_poly), int(domain),
+                                                        out.ctypes.data_as(ctypes.c_void_p)))
+    return out
 
 
 def GPU_4STEP_NTT_NaturalOrder(device_in, device_out, n1_root_of_unity_table, n2_root_of_unity_table,

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "gpuntt/ntt_4step/ntt_4step.cuh"
+#include "gpuntt/ntt_merge/galois.cuh"
 #include "gpuntt/ntt_merge/ntt.cuh"
 #include "gpuntt_c.h"
 #include "test_hooks.h"
@@ -194,6 +195,36 @@ namespace
                                             const_cast<T*>(mod_inverse), static_cast<hipStream_t>(stream)};
             GPU_PolyMul<T>(a, b, out, const_cast<T*>(fwd), const_cast<T*>(inv),
                            reinterpret_cast<Modulus<T>*>(const_cast<CM*>(modulus)), cfg, batch, mod_count);
+        });
+    }
+
+    template <typename T>
+    int automorphism_ntt(const T* in, T* out, const uint32_t* elts, int count, int n_power, int reduction_poly,
+                         void* stream, int batch)
+    {
+        return guarded([&] {
+            GPU_Automorphism_NTT<T>(in, out, elts, count, n_power, static_cast<ReductionPolynomial>(reduction_poly),
+                                    batch, static_cast<hipStream_t>(stream));
+        });
+    }
+    template <typename T, typename CM>
+    int automorphism_single(const T* in, T* out, const uint32_t* elts, int count, CM modulus, int n_power,
+                            int reduction_poly, void* stream, int batch)
+    {
+        return guarded([&] {
+            GPU_Automorphism<T>(in, out, elts, count, to_mod<T>(modulus), n_power,
+                                static_cast<ReductionPolynomial>(reduction_poly), batch,
+                                static_cast<hipStream_t>(stream));
+        });
+    }
+    template <typename T, typename CM>
+    int automorphism_rns(const T* in, T* out, const uint32_t* elts, int count, const CM* modulus, int n_power,
+                         int reduction_poly, void* stream, int batch, int mod_count)
+    {
+        return guarded([&] {
+            GPU_Automorphism<T>(in, out, elts, count, reinterpret_cast<const Modulus<T>*>(modulus), mod_count, n_power,
+                                static_cast<ReductionPolynomial>(reduction_poly), batch,
+                                static_cast<hipStream_t>(stream));
         });
     }
 
@@ -472,6 +503,39 @@ extern "C"
         return guarded([&] { host::scratch_stats(out); });
     }
 
+    int gpuntt_galois_element_u32(int steps, int n_power, int conjugation, uint32_t* elt_host)
+    {
+        GPUNTT_NEED(elt_host)
+        return guarded([&] {
+            *elt_host = conjugation ? GaloisElementForConjugation(n_power) : GaloisElementForRotation(steps, n_power);
+        });
+    }
+    int gpuntt_automorphism_index_map(int n_power, uint32_t galois_elt, int reduction_poly, int domain,
+                                      uint32_t* map_host)
+    {
+        GPUNTT_NEED(map_host)
+        return guarded([&] {
+            if (n_power <= 0 || n_power >= 29)
+                throw std::invalid_argument("Invalid n_power range!");
+            if (reduction_poly != GPUNTT_X_N_PLUS && reduction_poly != GPUNTT_X_N_MINUS)
+                throw std::invalid_argument("Invalid reduction_poly!");
+            if (domain != GPUNTT_DOMAIN_NTT && domain != GPUNTT_DOMAIN_COEFFICIENT)
+                throw std::invalid_argument("Invalid domain!");
+            const bool neg = reduction_poly == GPUNTT_X_N_PLUS;
+            const uint32_t mask = neg ? (2u << n_power) - 1u : (1u << n_power) - 1u;
+            const uint32_t k = galois_elt & mask;
+            if ((k & 1u) == 0u)
+                throw std::invalid_argument("Invalid Galois element (must be odd)!");
+            const uint32_t n = 1u << n_power;
+            if (domain == GPUNTT_DOMAIN_NTT)
+                for (uint32_t i = 0; i < n; i++)
+                    map_host[i] = galois_ntt_source(i, k, n_power, neg);
+            else
+                for (uint32_t i = 0; i < n; i++)
+                    map_host[i] = galois_coeff_source(i, galois_inverse(k) & mask, n_power, neg);
+        });
+    }
+
     int gpuntt_modulus_u32(uint32_t q, gpuntt_modulus32* out)
     {
         return guarded([&] {
@@ -570,6 +634,28 @@ extern "C"
         GPUNTT_NEED(a, b, out, forward_table, inverse_table, modulus, mod_inverse)                       \
         return polymul_rns<T>(a, b, out, forward_table, inverse_table, modulus, n_power,           \
                               reduction_poly, mod_inverse, stream, batch_size, mod_count);        \
+    }                                                                                             \
+    int gpuntt_automorphism_ntt_##S(const T* in, T* out, const uint32_t* galois_elts_host, int galois_count,      \
+                                    int n_power, int reduction_poly, void* stream, int batch_size)                \
+    {                                                                                             \
+        GPUNTT_NEED(in, out, galois_elts_host)                                                    \
+        return automorphism_ntt<T>(in, out, galois_elts_host, galois_count, n_power, reduction_poly, stream,      \
+                                   batch_size);                                                   \
+    }                                                                                             \
+    int gpuntt_automorphism_##S(const T* in, T* out, const uint32_t* galois_elts_host, int galois_count,          \
+                                CM modulus, int n_power, int reduction_poly, void* stream, int batch_size)        \
+    {                                                                                             \
+        GPUNTT_NEED(in, out, galois_elts_host)                                                    \
+        return automorphism_single<T>(in, out, galois_elts_host, galois_count, modulus, n_power, reduction_poly,  \
+                                      stream, batch_size);                                        \
+    }                                                                                             \
+    int gpuntt_automorphism_rns_##S(const T* in, T* out, const uint32_t* galois_elts_host, int galois_count,      \
+                                    const CM* modulus, int n_power, int reduction_poly, void* stream,             \
+                                    int batch_size, int mod_count)                                \
+    {                                                                                             \
+        GPUNTT_NEED(in, out, galois_elts_host, modulus)                                           \
+        return automorphism_rns<T>(in, out, galois_elts_host, galois_count, modulus, n_power, reduction_poly,     \
+                                   stream, batch_size, mod_count);                                \
     }                                                                                             \
     int gpuntt_4step_natural_##S(T* in_scratch, T* out, const T* n1_table, const T* n2_table,      \
                                  const T* w_table, CM modulus, int n_power, int ntt_type,          \

@@ -25,6 +25,9 @@
  *
  *   gpuntt_plan_*               extension NTTPlan<T> (include/gpuntt/ntt_merge/ntt.cuh): tables prepared once,
  *                               caller-owned workspace; execute = transform kernels only
+ *   gpuntt_automorphism_*, gpuntt_galois_element_u32
+ *                               extension Galois automorphisms (include/gpuntt/ntt_merge/galois.cuh), NTT and
+ *                               coefficient domain, single modulus or RNS
  *   gpuntt_operator_gpu_*       diagnostic: the public device class OPERATOR_GPU<T>
  *                               (src/include/gpuntt/common/modular_arith.cuh:174-454) applied elementwise
  *
@@ -144,6 +147,38 @@ extern "C"
                                const uint64_t* inverse_table, const gpuntt_modulus64* modulus,
                                int n_power, int reduction_poly, const uint64_t* mod_inverse,
                                void* stream, int batch_size, int mod_count);
+
+    /* ---- extension: Galois automorphisms sigma_k: a(X) -> a(X^k), k odd (include/gpuntt/ntt_merge/galois.cuh) ----
+     * in is T[batch][N], out is T[galois_count][batch][N]; galois_elts_host holds 1..64 odd elements (reduced mod 2N
+     * for X_N_plus, mod N for X_N_minus), passed to the kernel as arguments: one launch per call, no scratch.  in and
+     * out must not overlap.  _ntt: the permutation of GPU_NTT's output order (no modulus); otherwise the coefficient
+     * domain, negacyclic sign with the modulus (RNS: polynomial p uses modulus[p % mod_count], a device array). */
+    int gpuntt_automorphism_ntt_u32(const uint32_t* in, uint32_t* out, const uint32_t* galois_elts_host,
+                                    int galois_count, int n_power, int reduction_poly, void* stream, int batch_size);
+    int gpuntt_automorphism_ntt_u64(const uint64_t* in, uint64_t* out, const uint32_t* galois_elts_host,
+                                    int galois_count, int n_power, int reduction_poly, void* stream, int batch_size);
+    int gpuntt_automorphism_u32(const uint32_t* in, uint32_t* out, const uint32_t* galois_elts_host, int galois_count,
+                                gpuntt_modulus32 modulus, int n_power, int reduction_poly, void* stream,
+                                int batch_size);
+    int gpuntt_automorphism_u64(const uint64_t* in, uint64_t* out, const uint32_t* galois_elts_host, int galois_count,
+                                gpuntt_modulus64 modulus, int n_power, int reduction_poly, void* stream,
+                                int batch_size);
+    int gpuntt_automorphism_rns_u32(const uint32_t* in, uint32_t* out, const uint32_t* galois_elts_host,
+                                    int galois_count, const gpuntt_modulus32* modulus, int n_power, int reduction_poly,
+                                    void* stream, int batch_size, int mod_count);
+    int gpuntt_automorphism_rns_u64(const uint64_t* in, uint64_t* out, const uint32_t* galois_elts_host,
+                                    int galois_count, const gpuntt_modulus64* modulus, int n_power, int reduction_poly,
+                                    void* stream, int batch_size, int mod_count);
+    /* host: conjugation == 0: the element rotating slots by `steps` (5^steps mod 2N, negative steps the inverse);
+     * conjugation != 0: 2N - 1 (steps ignored) */
+    int gpuntt_galois_element_u32(int steps, int n_power, int conjugation, uint32_t* elt_host);
+    /* host: map_host[i] (N entries) = the source the kernels read for output slot i, from the same index functions.
+     * GPUNTT_DOMAIN_NTT: a slot of GPU_NTT's output; GPUNTT_DOMAIN_COEFFICIENT: a coefficient, where for X_N_plus a
+     * value j >= N means -in[j - N]. */
+#define GPUNTT_DOMAIN_NTT 0
+#define GPUNTT_DOMAIN_COEFFICIENT 1
+    int gpuntt_automorphism_index_map(int n_power, uint32_t galois_elt, int reduction_poly, int domain,
+                                      uint32_t* map_host);
 
     /* ---- 4-Step NTT (cyclic, 12 <= n_power <= 24, in != out) ------------------------ */
     int gpuntt_4step_u32(const uint32_t* in, uint32_t* out, const uint32_t* n1_table,
