@@ -9,6 +9,7 @@ src/include/gpuntt/ntt_4step/ntt_4step.cuh:46-49,278-308):
     GPU_NTT / GPU_INTT / GPU_NTT_Inplace / GPU_INTT_Inplace   (single modulus or RNS)
     GPU_4STEP_NTT / GPU_Transpose
     GPU_Automorphism_NTT / GPU_Automorphism (extension: Galois automorphisms, gpuntt/ntt_merge/galois.cuh)
+    BaseConvPlan / baseconv_constants (extension: RNS fast base conversion, gpuntt/rns/base_conversion.cuh)
     Modulus, ntt_configuration, ntt_rns_configuration, ntt4step_configuration,
     ntt4step_rns_configuration, NTTParameters, NTTParameters4Step
 
@@ -97,7 +98,10 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "plan_destroy", "operator_gpu", "4step_plan_workspace_bytes", "4step_plan_create",
               "4step_plan_execute", "4step_plan_fast_path", "4step_plan_destroy",
               "generate_power_table", "generate_4step_w", "butterfly_unit", "debug_recip_norm",
-              "automorphism_ntt", "automorphism", "automorphism_rns")
+              "automorphism_ntt", "automorphism", "automorphism_rns",
+              "baseconv_plan_workspace_bytes", "baseconv_plan_create", "baseconv_plan_convert",
+              "baseconv_plan_convert_and_divide", "baseconv_plan_owns_workspace", "baseconv_plan_destroy",
+              "baseconv_constants")
     for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option", "gpuntt_galois_element_u32",
                                 "gpuntt_automorphism_index_map"]
 
@@ -107,7 +111,7 @@ ENV_OPTIONS = {"GPUNTT_PATH": ("path", None), "GPUNTT_U32_E32": ("u32_e32", lamb
                "GPUNTT_TWO_SWEEP_BIG": ("two_sweep_big", None)}
 
 
-TEST_HOOKS = {"no_scratch", "rns_force_fallback", "u32_e32", "reset_predictions", "two_sweep_big"}
+TEST_HOOKS = {"no_scratch", "rns_force_fallback", "u32_e32", "reset_predictions", "two_sweep_big", "baseconv_ksplit"}
 TEST_PATHS = {"fast-strict", "generic-capped"}
 
 
@@ -600,6 +604,104 @@ class NTTPlan:
     def close(self):
         if self._h:
             getattr(load_library(), "gpuntt_plan_destroy_u%d" % self.bits)(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+APPROXIMATE, CENTRED = 0, 1  # BaseConvMode
+BASECONV_TILE = 128  # columns per workgroup of the base conversion kernel (kern::BC_NT)
+
+
+def _baseconv_moduli(moduli, bits):
+    """ints or Modulus objects -> (list of Modulus, C array); a value Modulus<T> refuses raises ValueError"""
+    ms = [m if isinstance(m, Modulus) else Modulus(int(m), bits=bits) for m in moduli]
+    if any(m.bits != bits for m in ms):
+        raise ValueError("every modulus of a BaseConvPlan has the plan's word width")
+    return ms, ((_M32 if bits == 32 else _M64) * max(1, len(ms)))(*[m.c() for m in ms])
+
+
+def baseconv_constants(in_moduli, out_moduli, bits=64):
+    """Host (no GPU): the constants a BaseConvPlan of these bases uploads, as a dict of numpy arrays -- qhat_inv[L],
+    qhat_inv_shoup[L], matrix[L][K] (qhat_i mod p_j), q_mod_p[K], q_inv_mod_p[K], recip[L] (floor(2^(W-1+b_i) / q_i)
+    mod 2^W), bit_length[L].  Raises ValueError where the plan's constructor would."""
+    qs, qarr = _baseconv_moduli(in_moduli, bits)
+    ps, parr = _baseconv_moduli(out_moduli, bits)
+    L, K, dt = len(qs), len(ps), np_dtype(bits)
+    shapes = (("qhat_inv", (L,)), ("qhat_inv_shoup", (L,)), ("matrix", (L, K)), ("q_mod_p", (K,)),
+              ("q_inv_mod_p", (K,)), ("recip", (L,)), ("bit_length", (L,)))
+    out = {name: np.zeros(tuple(max(1, d) for d in shape), dtype=dt) for name, shape in shapes}
+    fn = getattr(load_library(), "gpuntt_baseconv_constants_u%d" % bits)
+    _check(fn(qarr, L, parr, K, *[out[name].ctypes.data_as(ctypes.c_void_p) for name, _ in shapes]))
+    return out
+
+
+class BaseConvPlan:
+    """Extension BaseConvPlan<T> (include/gpuntt/rns/base_conversion.cuh): RNS fast base conversion from the base
+    `in_moduli` (q_0 .. q_{L-1}) to the base `out_moduli` (p_0 .. p_{K-1}); ints or Modulus objects, 1 <= L, K <= 64.
+    The constants are derived once, on the host, into `workspace` (an optional uint8 device tensor of
+    workspace_bytes() bytes owned by the caller).  convert() and convert_and_divide() launch one kernel each and
+    allocate nothing.  device_in holds count x L x N words, device_out and device_c count x K x N; device_out may be
+    device_c, and must not overlap device_in."""
+
+    def __init__(self, in_moduli, out_moduli, bits=64, stream=None, workspace=None):
+        lib = load_library()
+        qs, qarr = _baseconv_moduli(in_moduli, bits)
+        ps, parr = _baseconv_moduli(out_moduli, bits)
+        _require_gpu(workspace)
+        self.bits, self.in_count, self.out_count = bits, len(qs), len(ps)
+        if workspace is not None and 1 <= len(qs) <= 64 and 1 <= len(ps) <= 64 and \
+                workspace.numel() * workspace.element_size() < self.workspace_bytes(len(qs), len(ps), bits):
+            raise ValueError("workspace holds fewer than workspace_bytes() bytes")
+        self._keep = workspace
+        self._h = ctypes.c_void_p()
+        fn = getattr(lib, "gpuntt_baseconv_plan_create_u%d" % bits)
+        _check(fn(ctypes.byref(self._h), qarr, len(qs), parr, len(ps), _ptr(workspace), _stream(stream)))
+
+    @staticmethod
+    def workspace_bytes(in_count, out_count, bits=64):
+        out = ctypes.c_uint64()
+        _check(getattr(load_library(), "gpuntt_baseconv_plan_workspace_bytes_u%d" % bits)(
+            int(in_count), int(out_count), ctypes.byref(out)))
+        return int(out.value)
+
+    @property
+    def owns_workspace(self):
+        """False: the plan lives in the caller's workspace and has allocated no device memory"""
+        return bool(getattr(load_library(), "gpuntt_baseconv_plan_owns_workspace_u%d" % self.bits)(self._h))
+
+    def _check_buffers(self, device_in, outs, n_power, count):
+        """the library cannot see tensor sizes or types"""
+        _require_gpu(device_in, *outs)
+        if not 1 <= int(n_power) <= 28:
+            raise ValueError("Invalid n_power range!")
+        for t in (device_in, *outs):
+            if t.element_size() * 8 != self.bits or t.dtype.is_floating_point:
+                raise ValueError("a %d-bit BaseConvPlan takes %d-bit integer tensors" % (self.bits, self.bits))
+        if int(count) > 0:
+            words = int(count) << int(n_power)
+            if device_in.numel() < self.in_count * words or any(t.numel() < self.out_count * words for t in outs):
+                raise ValueError("device_in needs %d words (count x L x N), device_out and device_c %d (count x K x N)"
+                                 % (self.in_count * words, self.out_count * words))
+
+    def convert(self, device_in, device_out, n_power, count, mode=CENTRED, stream=None):
+        self._check_buffers(device_in, (device_out,), n_power, count)
+        fn = getattr(load_library(), "gpuntt_baseconv_plan_convert_u%d" % self.bits)
+        _check(fn(self._h, _ptr(device_in), _ptr(device_out), int(n_power), int(count), int(mode), _stream(stream)))
+
+    def convert_and_divide(self, device_in, device_c, device_out, n_power, count, mode=CENTRED, stream=None):
+        self._check_buffers(device_in, (device_c, device_out), n_power, count)
+        fn = getattr(load_library(), "gpuntt_baseconv_plan_convert_and_divide_u%d" % self.bits)
+        _check(fn(self._h, _ptr(device_in), _ptr(device_c), _ptr(device_out), int(n_power), int(count), int(mode),
+                  _stream(stream)))
+
+    def close(self):
+        if self._h:
+            getattr(load_library(), "gpuntt_baseconv_plan_destroy_u%d" % self.bits)(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

@@ -1,0 +1,514 @@
+// base_conversion.hip -- RNS fast base conversion (extension, include/gpuntt/rns/base_conversion.cuh).
+//
+// One lane owns one coefficient column of one ring element: it reads its L input words (coalesced: consecutive lanes,
+// consecutive columns), turns each into y_i with one exact Shoup product and parks the y_i in LDS -- at word
+// [i][lane], so a lane only ever reads what it wrote itself: no barrier, and consecutive lanes hit consecutive banks.
+// The K outputs are then produced KB at a time: for a block of KB outputs the lane walks i = 0 .. L-1 once, reads y_i
+// back from LDS and multiply-accumulates it into KB three-word accumulators (a 2W-bit sum plus a carry count: L = 64
+// terms of 2^124 do not fit 128 bits, 64 carries fit any word; 16 terms do fit, so the carry is looked at once per
+// 16 terms).  Blocking the OUTPUT loop keeps the live state at KB accumulators whatever L and K are; blocking the
+// input loop instead would need all K accumulators live (K = 64: 320 VGPRs).  Every constant -- the Shoup pair of
+// qhat_i^-1, the matrix row, the folding constants -- is indexed by
+// wave-uniform values only, so it travels through the scalar cache.
+//
+// The accumulator S = c 2^2W + h 2^W + l leaves as  (h * [2^W]_p + c * [2^2W]_p + l) mod p: three exact Shoup
+// products against constants the plan derives (each canonical, their sum below 3 p < 2^W) and two conditional
+// subtractions.  Modulus<T>::mu is not used: its Barrett step is exact only for operands below 2^(2 bit + 1), and a
+// 20-bit p_j under 62-bit q_i sums to 2^88.
+//
+// Small count * N: the grid's second dimension splits the blocks of KB outputs over several workgroups, each of
+// which re-reads the column (from L2) and recomputes the y_i -- see base_conv_ksplit().
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <stdexcept>
+#include <vector>
+
+#include "gpuntt/rns/base_conversion.cuh"
+#include "launch.hpp"
+
+namespace gpuntt
+{
+    namespace kern
+    {
+        constexpr int BC_NT = 128; // lanes per workgroup: L = 64 u64 words per lane are 64 KiB of LDS
+        constexpr int BC_KB = 4;   // outputs per pass over the y_i
+
+        template <typename T> struct BcWide;
+        template <> struct BcWide<Data32>
+        {
+            using type = Data64;
+        };
+        template <> struct BcWide<Data64>
+        {
+            using type = unsigned __int128;
+        };
+
+        __device__ __forceinline__ Data32 bc_mulhi(Data32 a, Data32 b) { return __umulhi(a, b); }
+        __device__ __forceinline__ Data64 bc_mulhi(Data64 a, Data64 b) { return __umul64hi(a, b); }
+
+        // (x * w) mod m, canonical, for ANY word x, w < m < 2^(W-1) and wp = floor(w 2^W / m): the quotient estimate
+        // hi(x * wp) is floor(x w / m) or one less, so the remainder lies in [0, 2m)
+        template <typename T> __device__ __forceinline__ T bc_shoup(T x, T w, T wp, T m)
+        {
+            const T r = x * w - bc_mulhi(x, wp) * m;
+            return r >= m ? r - m : r;
+        }
+
+        // where the plan's constants lie in the workspace, in words: L = in_count, KP = out_count rounded up to BC_KB
+        // (the padding columns of the matrix are zero and are never stored)
+        struct BcOffsets
+        {
+            unsigned q;      // [L]
+            unsigned w;      // [L] qhat_i^-1 mod q_i
+            unsigned wp;     // [L] its Shoup companion
+            unsigned recip;  // [L] R_i (0: q_i is a power of two)
+            unsigned shift;  // [L] b_i - 1
+            unsigned matrix; // [L][KP] qhat_i mod p_j
+            unsigned p;      // [KP]
+            unsigned negq;   // [KP] (-Q) mod p_j
+            unsigned qinv;   // [KP] Q^-1 mod p_j
+            unsigned qinvp;  // [KP] its Shoup companion
+            unsigned t1;     // [KP] 2^W mod p_j
+            unsigned t1p;
+            unsigned t2;     // [KP] 2^2W mod p_j
+            unsigned t2p;
+            unsigned onep;   // [KP] floor(2^W / p_j): the Shoup companion of 1
+        };
+        // the same as pointers into the workspace `base`, in the CONSTANT address space: nothing writes the workspace
+        // while a conversion runs, and a load from that address space at a wave-uniform address is a scalar load
+        // whatever the stores around it are (as plain global pointers the compiler could not rule out the stores to
+        // `out` -- which may alias c, so neither is __restrict__ -- and fetched the matrix rows with vector loads)
+        template <typename T> struct BcConsts
+        {
+            using CP = const T __attribute__((address_space(4)))*;
+            CP q, w, wp, recip, shift, matrix, p, negq, qinv, qinvp, t1, t1p, t2, t2p, onep;
+            __device__ BcConsts(const T* workspace, const BcOffsets& o)
+            {
+                const CP base = (CP) (workspace);
+                q = base + o.q, w = base + o.w, wp = base + o.wp, recip = base + o.recip, shift = base + o.shift;
+                matrix = base + o.matrix, p = base + o.p, negq = base + o.negq, qinv = base + o.qinv;
+                qinvp = base + o.qinvp, t1 = base + o.t1, t1p = base + o.t1p, t2 = base + o.t2, t2p = base + o.t2p;
+                onep = base + o.onep;
+            }
+        };
+
+        constexpr int BC_CHUNK = 16; // terms below 2^(2W-4) (moduli below 2^(W-2)) that a 2W-bit sum holds
+
+        template <typename T, bool CENTRED, bool DIVIDE>
+        __global__ __launch_bounds__(BC_NT) void base_convert(const T* __restrict__ in, const T* c_in, T* out,
+                                                              const T* __restrict__ consts, BcOffsets off,
+                                                              int L, int K, int KP, int n_power,
+                                                              unsigned long long total)
+        {
+            const BcConsts<T> k(consts, off);
+            using W2 = typename BcWide<T>::type;
+            constexpr int W = static_cast<int>(8 * sizeof(T));
+            extern __shared__ __align__(16) unsigned char bc_smem[];
+            T* ys = reinterpret_cast<T*>(bc_smem) + threadIdx.x;
+
+            const unsigned long long t = static_cast<unsigned long long>(blockIdx.x) * BC_NT + threadIdx.x;
+            if (t >= total)
+                return; // (no barrier below)
+            const unsigned long long e = t >> n_power, col = t & ((1ull << n_power) - 1ull);
+            const T* src = in + ((e * static_cast<unsigned>(L)) << n_power) + col;
+
+            W2 zsum = static_cast<W2>(1) << (W - 1);
+#pragma unroll 4
+            for (int i = 0; i < L; i++)
+            {
+                const T q = k.q[i];
+                const T y = bc_shoup<T>(src[static_cast<unsigned long long>(i) << n_power], k.w[i], k.wp[i], q);
+                ys[i * BC_NT] = y;
+                if constexpr (CENTRED)
+                {
+                    const T r = k.recip[i];
+                    const int sh = static_cast<int>(k.shift[i]);
+                    // z_i = (y R_i) >> (b_i - 1) < 2^W; a power of two q_i = 2^(b_i - 1) has R_i = 2^W
+                    const T z = (r != 0) ? static_cast<T>((static_cast<W2>(y) * r) >> sh) : (y << (W - sh));
+                    zsum += z;
+                }
+            }
+            T v = 0;
+            if constexpr (CENTRED)
+                v = static_cast<T>(zsum >> W);
+
+            const unsigned long long obase = ((e * static_cast<unsigned>(K)) << n_power) + col;
+            for (int j0 = static_cast<int>(blockIdx.y) * BC_KB; j0 < K; j0 += static_cast<int>(gridDim.y) * BC_KB)
+            {
+                // BC_CHUNK terms at a time go into a plain 2W-bit sum (no carry to watch); the sums go into the
+                // three-word accumulator {carry, acc}, one carry test per chunk and output
+                W2 acc[BC_KB];
+                T carry[BC_KB];
+#pragma unroll
+                for (int b = 0; b < BC_KB; b++)
+                {
+                    acc[b] = CENTRED ? static_cast<W2>(v) * k.negq[j0 + b] : static_cast<W2>(0);
+                    carry[b] = 0;
+                }
+                typename BcConsts<T>::CP row = k.matrix + j0;
+                for (int i0 = 0; i0 < L; i0 += BC_CHUNK)
+                {
+                    const int i1 = min(i0 + BC_CHUNK, L);
+                    W2 part[BC_KB];
+#pragma unroll
+                    for (int b = 0; b < BC_KB; b++)
+                        part[b] = 0;
+#pragma unroll 2
+                    for (int i = i0; i < i1; i++)
+                    {
+                        const T y = ys[i * BC_NT];
+#pragma unroll
+                        for (int b = 0; b < BC_KB; b++)
+                            part[b] += static_cast<W2>(y) * row[b];
+                        row += KP;
+                    }
+#pragma unroll
+                    for (int b = 0; b < BC_KB; b++)
+                    {
+                        acc[b] += part[b];
+                        carry[b] += (acc[b] < part[b]) ? 1u : 0u;
+                    }
+                }
+#pragma unroll
+                for (int b = 0; b < BC_KB; b++)
+                {
+                    const int j = j0 + b;
+                    if (j < K)
+                    {
+                        const T p = k.p[j];
+                        T r = bc_shoup<T>(static_cast<T>(acc[b] >> W), k.t1[j], k.t1p[j], p);
+                        r += bc_shoup<T>(carry[b], k.t2[j], k.t2p[j], p);
+                        r += bc_shoup<T>(static_cast<T>(acc[b]), T(1), k.onep[j], p); // r < 3 p < 2^W
+                        r = r >= p ? r - p : r;
+                        r = r >= p ? r - p : r;
+                        const unsigned long long o = obase + (static_cast<unsigned long long>(j) << n_power);
+                        if constexpr (DIVIDE)
+                        {
+                            const T cj = c_in[o];
+                            // c - conv as a word that is congruent to it: any word c is read modulo p
+                            const T d = cj >= r ? cj - r : cj + (p - r);
+                            r = bc_shoup<T>(d, k.qinv[j], k.qinvp[j], p);
+                        }
+                        out[o] = r;
+                    }
+                }
+            }
+        }
+    } // namespace kern
+
+    namespace host
+    {
+        namespace
+        {
+            std::atomic<int> g_bc_ksplit{0}; // test hook baseconv_ksplit: 0 = base_conv_ksplit(), n = n workgroups per column tile
+        }
+        void baseconv_set_ksplit(int v) { g_bc_ksplit.store(v, std::memory_order_relaxed); }
+    } // namespace host
+
+    namespace
+    {
+        using U128 = unsigned __int128;
+
+        std::uint64_t bc_gcd(std::uint64_t a, std::uint64_t b)
+        {
+            while (b != 0)
+            {
+                const std::uint64_t r = a % b;
+                a = b;
+                b = r;
+            }
+            return a;
+        }
+        std::uint64_t bc_mulmod(std::uint64_t a, std::uint64_t b, std::uint64_t m)
+        {
+            return static_cast<std::uint64_t>(static_cast<U128>(a) * b % m);
+        }
+        // a^-1 mod m for gcd(a, m) = 1, m >= 2 (extended Euclid)
+        std::uint64_t bc_modinv(std::uint64_t a, std::uint64_t m)
+        {
+            __int128 r0 = m, r1 = a % m, s0 = 0, s1 = 1;
+            while (r1 != 0)
+            {
+                const __int128 qt = r0 / r1;
+                const __int128 r2 = r0 - qt * r1, s2 = s0 - qt * s1;
+                r0 = r1, r1 = r2, s0 = s1, s1 = s2;
+            }
+            if (s0 < 0)
+                s0 += m;
+            return static_cast<std::uint64_t>(s0 % static_cast<__int128>(m));
+        }
+        int bc_bit_length(std::uint64_t v)
+        {
+            int b = 0;
+            for (; v != 0; v >>= 1)
+                b++;
+            return b;
+        }
+
+        // the constants in exact integers (64-bit words for both widths)
+        struct HostConsts
+        {
+            int L, K;
+            std::vector<std::uint64_t> q, p, w, wp, recip, blen, matrix, qmod, negq, qinv, qinvp, t1, t1p, t2, t2p, onep;
+        };
+
+        template <typename T> std::uint64_t checked_value(const Modulus<T>& m)
+        {
+            if (m.value < 2)
+                throw std::invalid_argument("Invalid modulus!");
+            const Modulus<T> ref(m.value); // throws for a modulus outside the library's domain
+            if (ref.bit != m.bit || ref.mu != m.mu)
+                throw std::invalid_argument("Invalid modulus!");
+            return static_cast<std::uint64_t>(m.value);
+        }
+
+        template <typename T> HostConsts derive(const Modulus<T>* qm, int L, const Modulus<T>* pm, int K)
+        {
+            constexpr int W = static_cast<int>(8 * sizeof(T));
+            if (L < 1 || L > BASECONV_MAX_COUNT)
+                throw std::invalid_argument("Invalid in_count!");
+            if (K < 1 || K > BASECONV_MAX_COUNT)
+                throw std::invalid_argument("Invalid out_count!");
+            if (qm == nullptr || pm == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            HostConsts h;
+            h.L = L, h.K = K;
+            for (int i = 0; i < L; i++)
+                h.q.push_back(checked_value(qm[i]));
+            for (int j = 0; j < K; j++)
+                h.p.push_back(checked_value(pm[j]));
+            for (int i = 0; i < L; i++)
+            {
+                for (int o = i + 1; o < L; o++)
+                    if (bc_gcd(h.q[i], h.q[o]) != 1)
+                        throw std::invalid_argument("Input base moduli are not pairwise coprime!");
+                for (int j = 0; j < K; j++)
+                    if (bc_gcd(h.q[i], h.p[j]) != 1)
+                        throw std::invalid_argument("An output modulus is not coprime to the input base!");
+            }
+            auto shoup = [](std::uint64_t v, std::uint64_t m) {
+                return static_cast<std::uint64_t>((static_cast<U128>(v) << W) / m);
+            };
+            // qhat_i mod m: the product of the other q's
+            auto qhat_mod = [&](int i, std::uint64_t m) {
+                std::uint64_t r = 1 % m;
+                for (int o = 0; o < L; o++)
+                    if (o != i)
+                        r = bc_mulmod(r, h.q[o] % m, m);
+                return r;
+            };
+            h.matrix.assign(static_cast<size_t>(L) * K, 0);
+            for (int i = 0; i < L; i++)
+            {
+                const std::uint64_t q = h.q[i];
+                const std::uint64_t w = bc_modinv(qhat_mod(i, q), q);
+                h.w.push_back(w);
+                h.wp.push_back(shoup(w, q));
+                const int b = bc_bit_length(q);
+                const U128 r = (static_cast<U128>(1) << (W - 1 + b)) / q;
+                h.recip.push_back((r >> W) != 0 ? 0 : static_cast<std::uint64_t>(r));
+                h.blen.push_back(static_cast<std::uint64_t>(b));
+                for (int j = 0; j < K; j++)
+                    h.matrix[static_cast<size_t>(i) * K + j] = qhat_mod(i, h.p[j]);
+            }
+            for (int j = 0; j < K; j++)
+            {
+                const std::uint64_t p = h.p[j];
+                const std::uint64_t qm_p = qhat_mod(-1, p);
+                const std::uint64_t qi = bc_modinv(qm_p, p);
+                const std::uint64_t t1 = static_cast<std::uint64_t>((static_cast<U128>(1) << W) % p);
+                const std::uint64_t t2 = bc_mulmod(t1, t1, p);
+                h.qmod.push_back(qm_p);
+                h.negq.push_back(qm_p == 0 ? 0 : p - qm_p);
+                h.qinv.push_back(qi);
+                h.qinvp.push_back(shoup(qi, p));
+                h.t1.push_back(t1);
+                h.t1p.push_back(shoup(t1, p));
+                h.t2.push_back(t2);
+                h.t2p.push_back(shoup(t2, p));
+                h.onep.push_back(shoup(1, p));
+            }
+            return h;
+        }
+
+        int padded(int K) { return (K + kern::BC_KB - 1) / kern::BC_KB * kern::BC_KB; }
+        size_t ws_words(int L, int K) { return 5 * static_cast<size_t>(L) + static_cast<size_t>(L + 9) * padded(K); }
+
+        // Workgroups per column tile.  A tile is BC_NT columns, and a workgroup that owns all of a tile's outputs
+        // reads the input once.  Below two workgroups per CU (256 CUs) the blocks of BC_KB outputs are spread over
+        // up to 8 workgroups per tile, which re-read the tile's input from L2.  Both numbers are estimates (two
+        // workgroups per CU as the fill target), not measured: DESIGN.md 3.10.
+        int base_conv_ksplit(unsigned long long tiles, int K)
+        {
+            const int jblocks = padded(K) / kern::BC_KB;
+            const int forced = host::g_bc_ksplit.load(std::memory_order_relaxed);
+            int s = 1;
+            if (forced > 0)
+                s = forced;
+            else
+                while (s < 8 && tiles * s < 512)
+                    s *= 2;
+            return s < jblocks ? s : jblocks;
+        }
+    } // namespace
+
+    template <typename T> struct BaseConvPlan<T>::Impl
+    {
+        int L = 0, K = 0, KP = 0;
+        void* ws = nullptr;
+        bool owns = false;
+        kern::BcOffsets off{};
+
+        void launch(const T* in, const T* c, T* out, int n_power, int count, BaseConvMode mode, bool divide,
+                    hipStream_t stream) const
+        {
+            if (n_power <= 0 || n_power >= 29)
+                throw std::invalid_argument("Invalid n_power range!");
+            if (mode != BaseConvMode::approximate && mode != BaseConvMode::centred)
+                throw std::invalid_argument("Invalid mode!");
+            if (count < 0)
+                throw std::invalid_argument("Invalid count!");
+            if (in == nullptr || out == nullptr || (divide && c == nullptr))
+                throw std::invalid_argument("null pointer argument");
+            if (count == 0)
+                return;
+            const unsigned long long total = static_cast<unsigned long long>(count) << n_power;
+            const unsigned long long tiles = (total + kern::BC_NT - 1) / kern::BC_NT;
+            if (tiles * kern::BC_NT > 0xFFFFFFFFull) // HIP caps a launch at 2^32 - 1 work-items per dimension
+                throw std::invalid_argument("Invalid count!");
+            const auto in_lo = reinterpret_cast<uintptr_t>(in), out_lo = reinterpret_cast<uintptr_t>(out);
+            const auto in_hi = in_lo + total * L * sizeof(T), out_hi = out_lo + total * K * sizeof(T);
+            if (in_lo < out_hi && out_lo < in_hi)
+                throw std::invalid_argument("Base conversion input and output overlap!");
+            const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(base_conv_ksplit(tiles, K)));
+            const size_t lds = static_cast<size_t>(L) * kern::BC_NT * sizeof(T);
+            const bool cen = mode == BaseConvMode::centred;
+#define GPUNTT_BC_LAUNCH(CEN, DIV)                                                                                     \
+    GPUNTT_LAUNCH((kern::base_convert<T, CEN, DIV>), grid, dim3(kern::BC_NT), lds, stream, in, c, out,                 \
+                  static_cast<const T*>(ws), off, L, K, KP, n_power, total)
+            if (cen && divide)
+                GPUNTT_BC_LAUNCH(true, true);
+            else if (cen)
+                GPUNTT_BC_LAUNCH(true, false);
+            else if (divide)
+                GPUNTT_BC_LAUNCH(false, true);
+            else
+                GPUNTT_BC_LAUNCH(false, false);
+#undef GPUNTT_BC_LAUNCH
+            GPUNTT_HIP_CHECK(hipGetLastError());
+        }
+    };
+
+    template <typename T> size_t BaseConvPlan<T>::workspace_bytes(int in_count, int out_count)
+    {
+        if (in_count < 1 || in_count > BASECONV_MAX_COUNT)
+            throw std::invalid_argument("Invalid in_count!");
+        if (out_count < 1 || out_count > BASECONV_MAX_COUNT)
+            throw std::invalid_argument("Invalid out_count!");
+        return (ws_words(in_count, out_count) * sizeof(T) + 255) / 256 * 256;
+    }
+
+    template <typename T>
+    BaseConvPlan<T>::BaseConvPlan(const Modulus<T>* in_moduli_host, int in_count, const Modulus<T>* out_moduli_host,
+                                  int out_count, stream_t stream, void* workspace_device)
+        : p_(nullptr)
+    {
+        const HostConsts h = derive<T>(in_moduli_host, in_count, out_moduli_host, out_count);
+        const int L = h.L, K = h.K, KP = padded(K);
+        std::vector<T> img(ws_words(L, K), T(0));
+        size_t at = 0;
+        auto put = [&](const std::vector<std::uint64_t>& v, size_t slots) {
+            const size_t first = at;
+            for (size_t i = 0; i < v.size(); i++)
+                img[at + i] = static_cast<T>(v[i]);
+            at += slots;
+            return first;
+        };
+        std::vector<std::uint64_t> shift(L), mat(static_cast<size_t>(L) * KP, 0), ppad(h.p);
+        for (int i = 0; i < L; i++)
+        {
+            shift[i] = h.blen[i] - 1;
+            for (int j = 0; j < K; j++)
+                mat[static_cast<size_t>(i) * KP + j] = h.matrix[static_cast<size_t>(i) * K + j];
+        }
+        const size_t o_q = put(h.q, L), o_w = put(h.w, L), o_wp = put(h.wp, L), o_r = put(h.recip, L),
+                     o_sh = put(shift, L), o_m = put(mat, static_cast<size_t>(L) * KP), o_p = put(ppad, KP),
+                     o_nq = put(h.negq, KP), o_qi = put(h.qinv, KP), o_qip = put(h.qinvp, KP), o_t1 = put(h.t1, KP),
+                     o_t1p = put(h.t1p, KP), o_t2 = put(h.t2, KP), o_t2p = put(h.t2p, KP), o_one = put(h.onep, KP);
+
+        Impl* p = new Impl;
+        p->L = L, p->K = K, p->KP = KP;
+        try
+        {
+            if (workspace_device != nullptr)
+                p->ws = workspace_device;
+            else
+            {
+                GPUNTT_HIP_CHECK(hipMalloc(&p->ws, workspace_bytes(L, K)));
+                p->owns = true;
+            }
+            GPUNTT_HIP_CHECK(hipMemcpyAsync(p->ws, img.data(), img.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+            GPUNTT_HIP_CHECK(hipStreamSynchronize(stream)); // `img` dies with this scope
+        }
+        catch (...)
+        {
+            if (p->owns)
+                (void) hipFree(p->ws);
+            delete p;
+            throw;
+        }
+        auto u = [](size_t v) { return static_cast<unsigned>(v); };
+        p->off = kern::BcOffsets{u(o_q),  u(o_w),   u(o_wp), u(o_r),   u(o_sh), u(o_m),  u(o_p),  u(o_nq),
+                                 u(o_qi), u(o_qip), u(o_t1), u(o_t1p), u(o_t2), u(o_t2p), u(o_one)};
+        p_ = p;
+    }
+
+    template <typename T> BaseConvPlan<T>::~BaseConvPlan()
+    {
+        if (p_ != nullptr && p_->owns)
+            (void) hipFree(p_->ws);
+        delete p_;
+    }
+
+    template <typename T>
+    void BaseConvPlan<T>::convert(const T* device_in, T* device_out, int n_power, int count, BaseConvMode mode,
+                                  stream_t stream) const
+    {
+        p_->launch(device_in, nullptr, device_out, n_power, count, mode, false, stream);
+    }
+
+    template <typename T>
+    void BaseConvPlan<T>::convert_and_divide(const T* device_in, const T* device_c, T* device_out, int n_power,
+                                             int count, BaseConvMode mode, stream_t stream) const
+    {
+        p_->launch(device_in, device_c, device_out, n_power, count, mode, true, stream);
+    }
+
+    template <typename T> int BaseConvPlan<T>::in_count() const { return p_->L; }
+    template <typename T> int BaseConvPlan<T>::out_count() const { return p_->K; }
+    template <typename T> bool BaseConvPlan<T>::owns_workspace() const { return p_->owns; }
+
+    template <typename T>
+    void BaseConvPlan<T>::constants(const Modulus<T>* in_moduli_host, int in_count, const Modulus<T>* out_moduli_host,
+                                    int out_count, const BaseConvConstants<T>& out)
+    {
+        const HostConsts h = derive<T>(in_moduli_host, in_count, out_moduli_host, out_count);
+        auto copy = [](const std::vector<std::uint64_t>& v, T* dst) {
+            if (dst == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            for (size_t i = 0; i < v.size(); i++)
+                dst[i] = static_cast<T>(v[i]);
+        };
+        copy(h.w, out.qhat_inv);
+        copy(h.wp, out.qhat_inv_shoup);
+        copy(h.matrix, out.matrix);
+        copy(h.qmod, out.q_mod_p);
+        copy(h.qinv, out.q_inv_mod_p);
+        copy(h.recip, out.recip);
+        copy(h.blen, out.bit_length);
+    }
+
+    template class BaseConvPlan<Data32>;
+    template class BaseConvPlan<Data64>;
+} // namespace gpuntt

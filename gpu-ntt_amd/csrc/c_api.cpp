@@ -10,6 +10,7 @@
 #include "gpuntt/ntt_4step/ntt_4step.cuh"
 #include "gpuntt/ntt_merge/galois.cuh"
 #include "gpuntt/ntt_merge/ntt.cuh"
+#include "gpuntt/rns/base_conversion.cuh"
 #include "gpuntt_c.h"
 #include "test_hooks.h"
 
@@ -456,6 +457,16 @@ namespace
             *plan = reinterpret_cast<gpuntt_plan*>(p);
         });
     }
+
+    template <typename T, typename CM> std::vector<Modulus<T>> to_mods(const CM* moduli, int count, const char* what)
+    {
+        if (moduli == nullptr || count < 1 || count > BASECONV_MAX_COUNT)
+            throw std::invalid_argument(what);
+        std::vector<Modulus<T>> ms;
+        for (int i = 0; i < count; i++)
+            ms.push_back(to_mod<T>(moduli[i]));
+        return ms;
+    }
 } // namespace
 
 extern "C"
@@ -724,6 +735,64 @@ extern "C"
     int gpuntt_plan_destroy_##S(gpuntt_plan* plan)                                                \
     {                                                                                             \
         return guarded([&] { delete reinterpret_cast<NTTPlan<T>*>(plan); });                      \
+    }                                                                                             \
+    int gpuntt_baseconv_plan_workspace_bytes_##S(int in_count, int out_count, uint64_t* bytes_host)               \
+    {                                                                                             \
+        GPUNTT_NEED(bytes_host)                                                                   \
+        return guarded([&] { *bytes_host = BaseConvPlan<T>::workspace_bytes(in_count, out_count); });             \
+    }                                                                                             \
+    int gpuntt_baseconv_plan_create_##S(gpuntt_baseconv_plan** plan_host, const CM* in_moduli_host, int in_count,  \
+                                        const CM* out_moduli_host, int out_count, void* workspace_device,         \
+                                        void* stream)                                             \
+    {                                                                                             \
+        GPUNTT_NEED(plan_host)                                                                    \
+        return guarded([&] {                                                                      \
+            const auto qs = to_mods<T>(in_moduli_host, in_count, "Invalid in_count!");             \
+            const auto ps = to_mods<T>(out_moduli_host, out_count, "Invalid out_count!");          \
+            *plan_host = reinterpret_cast<gpuntt_baseconv_plan*>(new BaseConvPlan<T>(             \
+                qs.data(), in_count, ps.data(), out_count, static_cast<hipStream_t>(stream), workspace_device));  \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_baseconv_plan_convert_##S(const gpuntt_baseconv_plan* plan, const T* in, T* out, int n_power,       \
+                                         int count, int mode, void* stream)                       \
+    {                                                                                             \
+        GPUNTT_NEED(plan, in, out)                                                                \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const BaseConvPlan<T>*>(plan)->convert(in, out, n_power, count,       \
+                                                                    static_cast<BaseConvMode>(mode),              \
+                                                                    static_cast<hipStream_t>(stream));            \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_baseconv_plan_convert_and_divide_##S(const gpuntt_baseconv_plan* plan, const T* in, const T* c,     \
+                                                    T* out, int n_power, int count, int mode, void* stream)       \
+    {                                                                                             \
+        GPUNTT_NEED(plan, in, c, out)                                                             \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const BaseConvPlan<T>*>(plan)->convert_and_divide(                   \
+                in, c, out, n_power, count, static_cast<BaseConvMode>(mode), static_cast<hipStream_t>(stream));   \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_baseconv_plan_owns_workspace_##S(const gpuntt_baseconv_plan* plan)                 \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return reinterpret_cast<const BaseConvPlan<T>*>(plan)->owns_workspace() ? 1 : 0;          \
+    }                                                                                             \
+    int gpuntt_baseconv_plan_destroy_##S(gpuntt_baseconv_plan* plan)                              \
+    {                                                                                             \
+        return guarded([&] { delete reinterpret_cast<BaseConvPlan<T>*>(plan); });                 \
+    }                                                                                             \
+    int gpuntt_baseconv_constants_##S(const CM* in_moduli_host, int in_count, const CM* out_moduli_host,          \
+                                      int out_count, T* qhat_inv, T* qhat_inv_shoup, T* matrix, T* q_mod_p,       \
+                                      T* q_inv_mod_p, T* recip, T* bit_length)                    \
+    {                                                                                             \
+        GPUNTT_NEED(qhat_inv, qhat_inv_shoup, matrix, q_mod_p, q_inv_mod_p, recip, bit_length)    \
+        return guarded([&] {                                                                      \
+            const auto qs = to_mods<T>(in_moduli_host, in_count, "Invalid in_count!");             \
+            const auto ps = to_mods<T>(out_moduli_host, out_count, "Invalid out_count!");          \
+            BaseConvPlan<T>::constants(qs.data(), in_count, ps.data(), out_count,                 \
+                                       BaseConvConstants<T>{qhat_inv, qhat_inv_shoup, matrix, q_mod_p,            \
+                                                            q_inv_mod_p, recip, bit_length});     \
+        });                                                                                       \
     }                                                                                             \
     int gpuntt_4step_plan_workspace_bytes_##S(int n_power, uint64_t* bytes_host)                  \
     {                                                                                             \

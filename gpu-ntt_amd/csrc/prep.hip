@@ -629,6 +629,7 @@ namespace gpuntt
         // fast-strict | generic-capped, no_scratch, rns_force_fallback, u32_e32.  Every public entry point opens a
         // WorkspaceScope, and the outermost scope of a thread takes ONE snapshot of all of them: a call sees the same values
         // from its first decision to its last launch, whatever another thread sets meanwhile.
+        void baseconv_set_ksplit(int v); // base_conversion.hip
         namespace
         {
             struct OptionValues
@@ -702,6 +703,11 @@ namespace gpuntt
                     g_opt.u32_e32 = iv; // a mask over the rings 2^12 .. 2^15; bit 16: the contiguous pass of larger rings
                 else if (test_hooks && k == "two_sweep_big" && bit)
                     g_opt.two_sweep_big = iv;
+                else if (test_hooks && k == "baseconv_ksplit" && is_num && lv >= 0 && lv <= 16)
+                    // base_conversion.hip: workgroups per column tile, 0 = its own choice.  NOT part of the per-call
+                    // snapshot below: a measurement knob of tools/bench_baseconv.py, read once per launch from a
+                    // process-wide atomic; whatever it holds, the outputs are the same words
+                    baseconv_set_ksplit(iv);
                 else if (test_hooks && k == "reset_predictions" && bit)
                     g_reset_predictions.store(1, std::memory_order_relaxed); // rns_guess forgets every stack it has seen
                 else

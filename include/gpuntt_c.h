@@ -28,6 +28,8 @@
  *   gpuntt_automorphism_*, gpuntt_galois_element_u32
  *                               extension Galois automorphisms (include/gpuntt/ntt_merge/galois.cuh), NTT and
  *                               coefficient domain, single modulus or RNS
+ *   gpuntt_baseconv_*           extension RNS fast base conversion (include/gpuntt/rns/base_conversion.cuh): ModUp,
+ *                               ModDown and rescale from one prepared plan, one kernel launch per call
  *   gpuntt_operator_gpu_*       diagnostic: the public device class OPERATOR_GPU<T>
  *                               (src/include/gpuntt/common/modular_arith.cuh:174-454) applied elementwise
  *
@@ -258,6 +260,52 @@ extern "C"
     int gpuntt_plan_fast_path_u64(const gpuntt_plan* plan);
     int gpuntt_plan_destroy_u32(gpuntt_plan* plan);
     int gpuntt_plan_destroy_u64(gpuntt_plan* plan);
+
+    /* ---- extension: RNS fast base conversion (BaseConvPlan<T>, include/gpuntt/rns/base_conversion.cuh) ----------
+     * in_moduli_host[in_count] (q_0 .. q_{L-1}, pairwise coprime) and out_moduli_host[out_count] (p_0 .. p_{K-1}, each
+     * coprime to every q_i) are HOST arrays, 1 <= L, K <= 64.  workspace_device: gpuntt_baseconv_plan_workspace_bytes_*()
+     * bytes of device memory owned by the caller, or NULL (the plan allocates).  in is T[count][L][N], out and c are
+     * T[count][K][N], N = 2^n_power; out may alias c, in must not overlap out.  mode: GPUNTT_BASECONV_APPROXIMATE
+     * ((x~ + u Q) mod p_j, 0 <= u < L) or GPUNTT_BASECONV_CENTRED (the representative in [-Q/2, Q/2 + 3L/2^W Q)).
+     * convert_and_divide: out_j = ((c_j - conv_j) * Q^-1) mod p_j.  Both calls allocate nothing, never synchronise
+     * and launch one kernel. */
+#define GPUNTT_BASECONV_APPROXIMATE 0
+#define GPUNTT_BASECONV_CENTRED 1
+    typedef struct gpuntt_baseconv_plan gpuntt_baseconv_plan;
+    int gpuntt_baseconv_plan_workspace_bytes_u32(int in_count, int out_count, uint64_t* bytes_host);
+    int gpuntt_baseconv_plan_workspace_bytes_u64(int in_count, int out_count, uint64_t* bytes_host);
+    int gpuntt_baseconv_plan_create_u32(gpuntt_baseconv_plan** plan_host, const gpuntt_modulus32* in_moduli_host,
+                                        int in_count, const gpuntt_modulus32* out_moduli_host, int out_count,
+                                        void* workspace_device, void* stream);
+    int gpuntt_baseconv_plan_create_u64(gpuntt_baseconv_plan** plan_host, const gpuntt_modulus64* in_moduli_host,
+                                        int in_count, const gpuntt_modulus64* out_moduli_host, int out_count,
+                                        void* workspace_device, void* stream);
+    int gpuntt_baseconv_plan_convert_u32(const gpuntt_baseconv_plan* plan, const uint32_t* in, uint32_t* out,
+                                         int n_power, int count, int mode, void* stream);
+    int gpuntt_baseconv_plan_convert_u64(const gpuntt_baseconv_plan* plan, const uint64_t* in, uint64_t* out,
+                                         int n_power, int count, int mode, void* stream);
+    int gpuntt_baseconv_plan_convert_and_divide_u32(const gpuntt_baseconv_plan* plan, const uint32_t* in,
+                                                    const uint32_t* c, uint32_t* out, int n_power, int count, int mode,
+                                                    void* stream);
+    int gpuntt_baseconv_plan_convert_and_divide_u64(const gpuntt_baseconv_plan* plan, const uint64_t* in,
+                                                    const uint64_t* c, uint64_t* out, int n_power, int count, int mode,
+                                                    void* stream);
+    int gpuntt_baseconv_plan_owns_workspace_u32(const gpuntt_baseconv_plan* plan); /* 1 / 0, negative on error */
+    int gpuntt_baseconv_plan_owns_workspace_u64(const gpuntt_baseconv_plan* plan);
+    int gpuntt_baseconv_plan_destroy_u32(gpuntt_baseconv_plan* plan);
+    int gpuntt_baseconv_plan_destroy_u64(gpuntt_baseconv_plan* plan);
+    /* host only (no GPU): the constants a plan of these bases uploads, with the checks of plan_create.  Caller arrays:
+     * qhat_inv[L] = qhat_i^-1 mod q_i, qhat_inv_shoup[L] = floor(qhat_inv_i 2^W / q_i), matrix[L][K] = qhat_i mod p_j,
+     * q_mod_p[K], q_inv_mod_p[K], recip[L] = floor(2^(W-1+b_i) / q_i) mod 2^W (0 for a power of two q_i),
+     * bit_length[L] = b_i */
+    int gpuntt_baseconv_constants_u32(const gpuntt_modulus32* in_moduli_host, int in_count,
+                                      const gpuntt_modulus32* out_moduli_host, int out_count, uint32_t* qhat_inv,
+                                      uint32_t* qhat_inv_shoup, uint32_t* matrix, uint32_t* q_mod_p,
+                                      uint32_t* q_inv_mod_p, uint32_t* recip, uint32_t* bit_length);
+    int gpuntt_baseconv_constants_u64(const gpuntt_modulus64* in_moduli_host, int in_count,
+                                      const gpuntt_modulus64* out_moduli_host, int out_count, uint64_t* qhat_inv,
+                                      uint64_t* qhat_inv_shoup, uint64_t* matrix, uint64_t* q_mod_p,
+                                      uint64_t* q_inv_mod_p, uint64_t* recip, uint64_t* bit_length);
 
     /* ---- extension: prepared 4-step transforms (FourStepPlan<T>, include/gpuntt/ntt_4step/ntt_4step.cuh) ----
      * The Shoup pairs of the n1 / n2 / W tables are derived once, at creation, into workspace_device
