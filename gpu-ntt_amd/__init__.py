@@ -10,6 +10,8 @@ src/include/gpuntt/ntt_4step/ntt_4step.cuh:46-49,278-308):
     GPU_4STEP_NTT / GPU_Transpose
     GPU_Automorphism_NTT / GPU_Automorphism (extension: Galois automorphisms, gpuntt/ntt_merge/galois.cuh)
     BaseConvPlan / baseconv_constants (extension: RNS fast base conversion, gpuntt/rns/base_conversion.cuh)
+    InnerProductPlan / innerprod_constants / innerprod_reference (extension: RNS inner product,
+    gpuntt/rns/inner_product.cuh)
     Modulus, ntt_configuration, ntt_rns_configuration, ntt4step_configuration,
     ntt4step_rns_configuration, NTTParameters, NTTParameters4Step
 
@@ -101,7 +103,10 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "automorphism_ntt", "automorphism", "automorphism_rns",
               "baseconv_plan_workspace_bytes", "baseconv_plan_create", "baseconv_plan_convert",
               "baseconv_plan_convert_and_divide", "baseconv_plan_owns_workspace", "baseconv_plan_destroy",
-              "baseconv_constants")
+              "baseconv_constants",
+              "innerprod_plan_workspace_bytes", "innerprod_plan_create", "innerprod_plan_execute",
+              "innerprod_plan_owns_workspace", "innerprod_plan_destroy", "innerprod_constants",
+              "innerprod_reference")
     for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option", "gpuntt_galois_element_u32",
                                 "gpuntt_automorphism_index_map"]
 
@@ -702,6 +707,135 @@ class BaseConvPlan:
     def close(self):
         if self._h:
             getattr(load_library(), "gpuntt_baseconv_plan_destroy_u%d" % self.bits)(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _innerprod_moduli(moduli, bits):
+    """ints or Modulus objects -> (list of Modulus, C array); a value Modulus<T> refuses raises ValueError"""
+    ms = [m if isinstance(m, Modulus) else Modulus(int(m), bits=bits) for m in moduli]
+    if any(m.bits != bits for m in ms):
+        raise ValueError("every modulus of an InnerProductPlan has the plan's word width")
+    return ms, ((_M32 if bits == 32 else _M64) * max(1, len(ms)))(*[m.c() for m in ms])
+
+
+def _innerprod_limbs(key_limbs, mod_count):
+    """None (the identity) or mod_count ints -> a C int array or None"""
+    if key_limbs is None:
+        return None
+    limbs = [int(v) for v in key_limbs]
+    if len(limbs) != mod_count:
+        raise ValueError("key_limbs holds one key limb index per modulus of the plan")
+    return (ctypes.c_int * max(1, len(limbs)))(*limbs)
+
+
+def innerprod_constants(moduli, bits=64):
+    """Host (no GPU): the folding constants an InnerProductPlan of these moduli uploads, as a dict of numpy arrays of M
+    words -- pow_w (2^W mod q), pow_w_shoup, pow_2w (2^2W mod q), pow_2w_shoup, one_shoup (floor(2^W / q)).  Raises
+    ValueError where the plan's constructor would."""
+    ms, marr = _innerprod_moduli(moduli, bits)
+    names = ("pow_w", "pow_w_shoup", "pow_2w", "pow_2w_shoup", "one_shoup")
+    out = {name: np.zeros(max(1, len(ms)), dtype=np_dtype(bits)) for name in names}
+    fn = getattr(load_library(), "gpuntt_innerprod_constants_u%d" % bits)
+    _check(fn(marr, len(ms), *[out[name].ctypes.data_as(ctypes.c_void_p) for name in names]))
+    return out
+
+
+def innerprod_reference(moduli, a, key, out, n_power, digits, components, count, accumulate=False, key_mod_count=None,
+                        key_limbs=None, bits=64):
+    """Host (no GPU): InnerProductPlan<T>::reference -- the definition of multiply_accumulate on numpy arrays of the
+    plan's word type, in exact integers, after the argument checks of the call itself (ValueError).  `out` is written
+    in place (and read first when accumulating) and returned.  None for an array is the C NULL."""
+    ms, marr = _innerprod_moduli(moduli, bits)
+    M, dt = len(ms), np_dtype(bits)
+    km = M if key_mod_count is None else int(key_mod_count)
+    limbs = _innerprod_limbs(key_limbs, M)
+    need = None
+    if 1 <= int(n_power) <= 28 and int(count) >= 0 and int(digits) >= 1 and int(components) >= 1 and km >= 1:
+        words = (int(count) * M) << int(n_power)
+        need = (int(digits) * words, (int(digits) * int(components) * km) << int(n_power), int(components) * words)
+    for i, arr in enumerate((a, key, out)):
+        if arr is None:
+            continue
+        if arr.dtype != dt or not arr.flags["C_CONTIGUOUS"]:
+            raise ValueError("innerprod_reference takes C-contiguous %d-bit unsigned arrays" % bits)
+        if need is not None and arr.size < need[i]:
+            raise ValueError("a needs %d words (D x count x M x N), key %d (D x C x key_mod_count x N), out %d "
+                             "(C x count x M x N)" % need)
+    ptr = [ctypes.c_void_p(0 if arr is None else arr.ctypes.data) for arr in (a, key, out)]
+    fn = getattr(load_library(), "gpuntt_innerprod_reference_u%d" % bits)
+    _check(fn(marr, M, ptr[0], ptr[1], ptr[2], int(n_power), int(digits), int(components), int(count),
+              1 if accumulate else 0, km, limbs))
+    return out
+
+
+class InnerProductPlan:
+    """Extension InnerProductPlan<T> (include/gpuntt/rns/inner_product.cuh): the key-switching multiply-accumulate for
+    the moduli q_0 .. q_{M-1} (ints or Modulus objects, 1 <= M <= 64).  The folding constants are derived once, on the
+    host, into `workspace` (an optional uint8 device tensor of workspace_bytes() bytes owned by the caller).
+    multiply_accumulate() launches one kernel and allocates nothing."""
+
+    def __init__(self, moduli, bits=64, stream=None, workspace=None):
+        lib = load_library()
+        ms, marr = _innerprod_moduli(moduli, bits)
+        _require_gpu(workspace)
+        self.bits, self.mod_count = bits, len(ms)
+        if workspace is not None and 1 <= len(ms) <= 64 and \
+                workspace.numel() * workspace.element_size() < self.workspace_bytes(len(ms), bits):
+            raise ValueError("workspace holds fewer than workspace_bytes() bytes")
+        self._keep = workspace
+        self._h = ctypes.c_void_p()
+        fn = getattr(lib, "gpuntt_innerprod_plan_create_u%d" % bits)
+        _check(fn(ctypes.byref(self._h), marr, len(ms), _ptr(workspace), _stream(stream)))
+
+    @staticmethod
+    def workspace_bytes(mod_count, bits=64):
+        out = ctypes.c_uint64()
+        _check(getattr(load_library(), "gpuntt_innerprod_plan_workspace_bytes_u%d" % bits)(
+            int(mod_count), ctypes.byref(out)))
+        return int(out.value)
+
+    @property
+    def owns_workspace(self):
+        """False: the plan lives in the caller's workspace and has allocated no device memory"""
+        return bool(getattr(load_library(), "gpuntt_innerprod_plan_owns_workspace_u%d" % self.bits)(self._h))
+
+    def _check_buffers(self, a, key, out, n_power, digits, components, count, key_mod_count):
+        """the library cannot see tensor sizes or types"""
+        _require_gpu(a, key, out)
+        if not 1 <= int(n_power) <= 28:
+            raise ValueError("Invalid n_power range!")
+        for t in (a, key, out):
+            if t.element_size() * 8 != self.bits or t.dtype.is_floating_point:
+                raise ValueError("a %d-bit InnerProductPlan takes %d-bit integer tensors" % (self.bits, self.bits))
+        if int(count) > 0 and int(digits) >= 1 and int(components) >= 1 and int(key_mod_count) >= 1:
+            words = (int(count) * self.mod_count) << int(n_power)
+            need = (int(digits) * words, (int(digits) * int(components) * int(key_mod_count)) << int(n_power),
+                    int(components) * words)
+            if a.numel() < need[0] or key.numel() < need[1] or out.numel() < need[2]:
+                raise ValueError("a needs %d words (D x count x M x N), key %d (D x C x key_mod_count x N), out %d "
+                                 "(C x count x M x N)" % need)
+
+    def multiply_accumulate(self, a, key, out, n_power, digits, components, count, accumulate=False,
+                            key_mod_count=None, key_limbs=None, stream=None):
+        """out[c][r][m] (+)= sum_d a[d][r][m] * key[d][c][key_limbs[m]] mod q_m, pointwise over the N columns: a holds
+        digits x count x M x N words, key (at least) digits x components x key_mod_count x N, out components x count x
+        M x N.  key_mod_count defaults to M, key_limbs (M indices into the key's limbs) to the identity."""
+        km = self.mod_count if key_mod_count is None else int(key_mod_count)
+        self._check_buffers(a, key, out, n_power, digits, components, count, km)
+        limbs = _innerprod_limbs(key_limbs, self.mod_count)
+        fn = getattr(load_library(), "gpuntt_innerprod_plan_execute_u%d" % self.bits)
+        _check(fn(self._h, _ptr(a), _ptr(key), _ptr(out), int(n_power), int(digits), int(components), int(count),
+                  1 if accumulate else 0, km, limbs, _stream(stream)))
+
+    def close(self):
+        if self._h:
+            getattr(load_library(), "gpuntt_innerprod_plan_destroy_u%d" % self.bits)(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

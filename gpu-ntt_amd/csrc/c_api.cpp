@@ -11,6 +11,7 @@
 #include "gpuntt/ntt_merge/galois.cuh"
 #include "gpuntt/ntt_merge/ntt.cuh"
 #include "gpuntt/rns/base_conversion.cuh"
+#include "gpuntt/rns/inner_product.cuh"
 #include "gpuntt_c.h"
 #include "test_hooks.h"
 
@@ -792,6 +793,63 @@ extern "C"
             BaseConvPlan<T>::constants(qs.data(), in_count, ps.data(), out_count,                 \
                                        BaseConvConstants<T>{qhat_inv, qhat_inv_shoup, matrix, q_mod_p,            \
                                                             q_inv_mod_p, recip, bit_length});     \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_innerprod_plan_workspace_bytes_##S(int mod_count, uint64_t* bytes_host)            \
+    {                                                                                             \
+        GPUNTT_NEED(bytes_host)                                                                   \
+        return guarded([&] { *bytes_host = InnerProductPlan<T>::workspace_bytes(mod_count); });    \
+    }                                                                                             \
+    int gpuntt_innerprod_plan_create_##S(gpuntt_innerprod_plan** plan_host, const CM* moduli_host, int mod_count,  \
+                                         void* workspace_device, void* stream)                    \
+    {                                                                                             \
+        GPUNTT_NEED(plan_host)                                                                    \
+        return guarded([&] {                                                                      \
+            const auto ms = to_mods<T>(moduli_host, mod_count, "Invalid mod_count!");              \
+            *plan_host = reinterpret_cast<gpuntt_innerprod_plan*>(new InnerProductPlan<T>(        \
+                ms.data(), mod_count, static_cast<hipStream_t>(stream), workspace_device));       \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_innerprod_plan_execute_##S(const gpuntt_innerprod_plan* plan, const T* a, const T* key, T* out,     \
+                                          int n_power, int digits, int components, int count, int accumulate,     \
+                                          int key_mod_count, const int* key_limbs_host, void* stream)             \
+    {                                                                                             \
+        GPUNTT_NEED(plan, a, key, out)                                                            \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const InnerProductPlan<T>*>(plan)->multiply_accumulate(              \
+                a, key, out, n_power, digits, components, count, accumulate != 0, key_mod_count, key_limbs_host,  \
+                static_cast<hipStream_t>(stream));                                                \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_innerprod_plan_owns_workspace_##S(const gpuntt_innerprod_plan* plan)               \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return reinterpret_cast<const InnerProductPlan<T>*>(plan)->owns_workspace() ? 1 : 0;      \
+    }                                                                                             \
+    int gpuntt_innerprod_plan_destroy_##S(gpuntt_innerprod_plan* plan)                            \
+    {                                                                                             \
+        return guarded([&] { delete reinterpret_cast<InnerProductPlan<T>*>(plan); });             \
+    }                                                                                             \
+    int gpuntt_innerprod_constants_##S(const CM* moduli_host, int mod_count, T* pow_w, T* pow_w_shoup, T* pow_2w,  \
+                                       T* pow_2w_shoup, T* one_shoup)                             \
+    {                                                                                             \
+        GPUNTT_NEED(pow_w, pow_w_shoup, pow_2w, pow_2w_shoup, one_shoup)                          \
+        return guarded([&] {                                                                      \
+            const auto ms = to_mods<T>(moduli_host, mod_count, "Invalid mod_count!");              \
+            InnerProductPlan<T>::constants(                                                       \
+                ms.data(), mod_count,                                                             \
+                InnerProductConstants<T>{pow_w, pow_w_shoup, pow_2w, pow_2w_shoup, one_shoup});   \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_innerprod_reference_##S(const CM* moduli_host, int mod_count, const T* a_host, const T* key_host,   \
+                                       T* out_host, int n_power, int digits, int components, int count,           \
+                                       int accumulate, int key_mod_count, const int* key_limbs_host)              \
+    {                                                                                             \
+        GPUNTT_NEED(a_host, key_host, out_host)                                                   \
+        return guarded([&] {                                                                      \
+            const auto ms = to_mods<T>(moduli_host, mod_count, "Invalid mod_count!");              \
+            InnerProductPlan<T>::reference(ms.data(), mod_count, a_host, key_host, out_host, n_power, digits,     \
+                                           components, count, accumulate != 0, key_mod_count, key_limbs_host);    \
         });                                                                                       \
     }                                                                                             \
     int gpuntt_4step_plan_workspace_bytes_##S(int n_power, uint64_t* bytes_host)                  \

@@ -30,6 +30,8 @@
  *                               coefficient domain, single modulus or RNS
  *   gpuntt_baseconv_*           extension RNS fast base conversion (include/gpuntt/rns/base_conversion.cuh): ModUp,
  *                               ModDown and rescale from one prepared plan, one kernel launch per call
+ *   gpuntt_innerprod_*          extension RNS inner product (include/gpuntt/rns/inner_product.cuh): the key-switching
+ *                               multiply-accumulate over digits and key components, one kernel launch per call
  *   gpuntt_operator_gpu_*       diagnostic: the public device class OPERATOR_GPU<T>
  *                               (src/include/gpuntt/common/modular_arith.cuh:174-454) applied elementwise
  *
@@ -306,6 +308,53 @@ extern "C"
                                       const gpuntt_modulus64* out_moduli_host, int out_count, uint64_t* qhat_inv,
                                       uint64_t* qhat_inv_shoup, uint64_t* matrix, uint64_t* q_mod_p,
                                       uint64_t* q_inv_mod_p, uint64_t* recip, uint64_t* bit_length);
+
+    /* ---- extension: RNS inner product (InnerProductPlan<T>, include/gpuntt/rns/inner_product.cuh) ----------------
+     * moduli_host[mod_count] (q_0 .. q_{M-1}, 1 <= M <= 64) is a HOST array.  workspace_device:
+     * gpuntt_innerprod_plan_workspace_bytes_*() bytes of device memory owned by the caller, or NULL (the plan allocates).
+     * execute: out[c][r][m][j] = ([accumulate ? out[c][r][m][j] : 0] + sum_{d < digits} a[d][r][m][j] *
+     * key[d][c][limb(m)][j]) mod q_m with a = T[digits][count][M][N], out = T[components][count][M][N],
+     * key = T[D_key][components][key_mod_count][N] (its first `digits` digits are used), N = 2^n_power, limb(m) =
+     * key_limbs_host[m] in [0, key_mod_count) or m when key_limbs_host is NULL (a HOST array of M ints, read before the
+     * call returns).  1 <= digits <= 64, 1 <= components <= 4, count >= 0, M <= key_mod_count <= 256.  Any word value is
+     * read modulo q_m; every output word is canonical; out must not overlap a or key.  execute allocates nothing, never
+     * synchronises and launches one kernel. */
+    typedef struct gpuntt_innerprod_plan gpuntt_innerprod_plan;
+    int gpuntt_innerprod_plan_workspace_bytes_u32(int mod_count, uint64_t* bytes_host);
+    int gpuntt_innerprod_plan_workspace_bytes_u64(int mod_count, uint64_t* bytes_host);
+    int gpuntt_innerprod_plan_create_u32(gpuntt_innerprod_plan** plan_host, const gpuntt_modulus32* moduli_host,
+                                         int mod_count, void* workspace_device, void* stream);
+    int gpuntt_innerprod_plan_create_u64(gpuntt_innerprod_plan** plan_host, const gpuntt_modulus64* moduli_host,
+                                         int mod_count, void* workspace_device, void* stream);
+    int gpuntt_innerprod_plan_execute_u32(const gpuntt_innerprod_plan* plan, const uint32_t* a, const uint32_t* key,
+                                          uint32_t* out, int n_power, int digits, int components, int count,
+                                          int accumulate, int key_mod_count, const int* key_limbs_host, void* stream);
+    int gpuntt_innerprod_plan_execute_u64(const gpuntt_innerprod_plan* plan, const uint64_t* a, const uint64_t* key,
+                                          uint64_t* out, int n_power, int digits, int components, int count,
+                                          int accumulate, int key_mod_count, const int* key_limbs_host, void* stream);
+    int gpuntt_innerprod_plan_owns_workspace_u32(const gpuntt_innerprod_plan* plan); /* 1 / 0, negative on error */
+    int gpuntt_innerprod_plan_owns_workspace_u64(const gpuntt_innerprod_plan* plan);
+    int gpuntt_innerprod_plan_destroy_u32(gpuntt_innerprod_plan* plan);
+    int gpuntt_innerprod_plan_destroy_u64(gpuntt_innerprod_plan* plan);
+    /* host only (no GPU): the folding constants a plan of these moduli uploads, with the checks of plan_create.  Caller
+     * arrays of M words: pow_w = 2^W mod q_m, pow_2w = 2^2W mod q_m, the Shoup companions floor(v 2^W / q_m) of both, and
+     * one_shoup = floor(2^W / q_m) */
+    int gpuntt_innerprod_constants_u32(const gpuntt_modulus32* moduli_host, int mod_count, uint32_t* pow_w,
+                                       uint32_t* pow_w_shoup, uint32_t* pow_2w, uint32_t* pow_2w_shoup,
+                                       uint32_t* one_shoup);
+    int gpuntt_innerprod_constants_u64(const gpuntt_modulus64* moduli_host, int mod_count, uint64_t* pow_w,
+                                       uint64_t* pow_w_shoup, uint64_t* pow_2w, uint64_t* pow_2w_shoup,
+                                       uint64_t* one_shoup);
+    /* host only (no GPU): what execute computes, on HOST arrays in exact integers, after the same argument checks.  The
+     * value tests and examples compare the kernel with; never a fall-back */
+    int gpuntt_innerprod_reference_u32(const gpuntt_modulus32* moduli_host, int mod_count, const uint32_t* a_host,
+                                       const uint32_t* key_host, uint32_t* out_host, int n_power, int digits,
+                                       int components, int count, int accumulate, int key_mod_count,
+                                       const int* key_limbs_host);
+    int gpuntt_innerprod_reference_u64(const gpuntt_modulus64* moduli_host, int mod_count, const uint64_t* a_host,
+                                       const uint64_t* key_host, uint64_t* out_host, int n_power, int digits,
+                                       int components, int count, int accumulate, int key_mod_count,
+                                       const int* key_limbs_host);
 
     /* ---- extension: prepared 4-step transforms (FourStepPlan<T>, include/gpuntt/ntt_4step/ntt_4step.cuh) ----
      * The Shoup pairs of the n1 / n2 / W tables are derived once, at creation, into workspace_device
