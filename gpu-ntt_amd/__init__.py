@@ -12,6 +12,9 @@ src/include/gpuntt/ntt_4step/ntt_4step.cuh:46-49,278-308):
     BaseConvPlan / baseconv_constants (extension: RNS fast base conversion, gpuntt/rns/base_conversion.cuh)
     InnerProductPlan / innerprod_constants / innerprod_reference (extension: RNS inner product,
     gpuntt/rns/inner_product.cuh)
+    KeySwitchPlan / keyswitch_constants / keyswitch_scratch_bytes / keyswitch_reference_mod_up /
+    keyswitch_reference_mod_down (extension: hybrid
+    key switching, gpuntt/rns/key_switch.cuh)
     Modulus, ntt_configuration, ntt_rns_configuration, ntt4step_configuration,
     ntt4step_rns_configuration, NTTParameters, NTTParameters4Step
 
@@ -106,7 +109,12 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "baseconv_constants",
               "innerprod_plan_workspace_bytes", "innerprod_plan_create", "innerprod_plan_execute",
               "innerprod_plan_owns_workspace", "innerprod_plan_destroy", "innerprod_constants",
-              "innerprod_reference")
+              "innerprod_reference",
+              "keyswitch_plan_workspace_bytes", "keyswitch_plan_scratch_bytes", "keyswitch_plan_create",
+              "keyswitch_plan_mod_up", "keyswitch_plan_mod_down", "keyswitch_plan_decompose",
+              "keyswitch_plan_switch_digits", "keyswitch_plan_apply", "keyswitch_plan_owns_workspace",
+              "keyswitch_plan_destroy", "keyswitch_constants", "keyswitch_reference_mod_up",
+              "keyswitch_reference_mod_down")
     for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option", "gpuntt_galois_element_u32",
                                 "gpuntt_automorphism_index_map"]
 
@@ -116,7 +124,8 @@ ENV_OPTIONS = {"GPUNTT_PATH": ("path", None), "GPUNTT_U32_E32": ("u32_e32", lamb
                "GPUNTT_TWO_SWEEP_BIG": ("two_sweep_big", None)}
 
 
-TEST_HOOKS = {"no_scratch", "rns_force_fallback", "u32_e32", "reset_predictions", "two_sweep_big", "baseconv_ksplit"}
+TEST_HOOKS = {"no_scratch", "rns_force_fallback", "u32_e32", "reset_predictions", "two_sweep_big", "baseconv_ksplit",
+              "keyswitch_split"}
 TEST_PATHS = {"fast-strict", "generic-capped"}
 
 
@@ -836,6 +845,241 @@ class InnerProductPlan:
     def close(self):
         if self._h:
             getattr(load_library(), "gpuntt_innerprod_plan_destroy_u%d" % self.bits)(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _keyswitch_moduli(moduli, bits):
+    """ints or Modulus objects -> (list of Modulus, C array); a value Modulus<T> refuses raises ValueError"""
+    ms = [m if isinstance(m, Modulus) else Modulus(int(m), bits=bits) for m in moduli]
+    if any(m.bits != bits for m in ms):
+        raise ValueError("every modulus of a KeySwitchPlan has the plan's word width")
+    return ms, ((_M32 if bits == 32 else _M64) * max(1, len(ms)))(*[m.c() for m in ms])
+
+
+def keyswitch_digits(q_count, alpha):
+    """D = ceil(L / alpha)"""
+    return -(-int(q_count) // max(1, int(alpha)))
+
+
+def keyswitch_scratch_bytes(q_count, p_count, alpha, n_power, count, components=1, bits=64):
+    """KeySwitchPlan<T>::scratch_bytes (host only): the caller-owned scratch of the pipeline calls, in bytes"""
+    out = ctypes.c_uint64()
+    _check(getattr(load_library(), "gpuntt_keyswitch_plan_scratch_bytes_u%d" % bits)(
+        int(q_count), int(p_count), int(alpha), int(n_power), int(count), int(components), ctypes.byref(out)))
+    return int(out.value)
+
+
+def keyswitch_constants(q_moduli, p_moduli, alpha, bits=64):
+    """Host (no GPU): the constants a KeySwitchPlan of these bases uploads (KeySwitchConstants<T>), as a dict of numpy
+    arrays -- per digit the ModUp constants up_qhat_inv[L], up_qhat_inv_shoup[L], up_matrix[L][M], up_q_mod[D][M],
+    up_recip[L], up_bit_length[L]; the ModDown constants down_qhat_inv[K], down_qhat_inv_shoup[K], down_matrix[K][L],
+    down_p_mod_q[L], down_p_inv_mod_q[L], down_recip[K], down_bit_length[K]; the folding constants pow_w, pow_w_shoup,
+    pow_2w, pow_2w_shoup, one_shoup [M].  Raises ValueError where the plan's constructor would."""
+    qs, qarr = _keyswitch_moduli(q_moduli, bits)
+    ps, parr = _keyswitch_moduli(p_moduli, bits)
+    L, K, dt = len(qs), len(ps), np_dtype(bits)
+    M, D = L + K, keyswitch_digits(L, alpha)
+    shapes = (("up_qhat_inv", (L,)), ("up_qhat_inv_shoup", (L,)), ("up_matrix", (L, M)), ("up_q_mod", (D, M)),
+              ("up_recip", (L,)), ("up_bit_length", (L,)), ("down_qhat_inv", (K,)), ("down_qhat_inv_shoup", (K,)),
+              ("down_matrix", (K, L)), ("down_p_mod_q", (L,)), ("down_p_inv_mod_q", (L,)), ("down_recip", (K,)),
+              ("down_bit_length", (K,)), ("pow_w", (M,)), ("pow_w_shoup", (M,)), ("pow_2w", (M,)),
+              ("pow_2w_shoup", (M,)), ("one_shoup", (M,)))
+    out = {name: np.zeros(tuple(max(1, d) for d in shape), dtype=dt) for name, shape in shapes}
+    ptrs = (ctypes.c_void_p * len(shapes))(*[out[name].ctypes.data for name, _ in shapes])
+    fn = getattr(load_library(), "gpuntt_keyswitch_constants_u%d" % bits)
+    _check(fn(qarr, L, parr, K, int(alpha), ptrs))
+    return out
+
+
+def _keyswitch_host_array(arr, bits, words, what):
+    if arr is None:
+        return ctypes.c_void_p(0)
+    if arr.dtype != np_dtype(bits) or not arr.flags["C_CONTIGUOUS"]:
+        raise ValueError("the key switching references take C-contiguous %d-bit unsigned arrays" % bits)
+    if words is not None and arr.size < words:
+        raise ValueError("%s needs %d words" % (what, words))
+    return ctypes.c_void_p(arr.ctypes.data)
+
+
+def keyswitch_reference_mod_up(q_moduli, p_moduli, alpha, x, a, n_power, count, mode=CENTRED, bits=64):
+    """Host (no GPU): KeySwitchPlan<T>::reference_mod_up on numpy arrays of the plan's word type -- x holds count x L x
+    N words, a D x count x M x N (written and returned) -- after the argument checks of mod_up (ValueError).  None for
+    an array is the C NULL."""
+    qs, qarr = _keyswitch_moduli(q_moduli, bits)
+    ps, parr = _keyswitch_moduli(p_moduli, bits)
+    L, M = len(qs), len(qs) + len(ps)
+    ok = 1 <= int(n_power) <= 28 and int(count) >= 0 and int(alpha) >= 1
+    cols = (int(count) << int(n_power)) if ok else None
+    px = _keyswitch_host_array(x, bits, cols * L if ok else None, "in (count x L x N)")
+    pa = _keyswitch_host_array(a, bits, cols * M * keyswitch_digits(L, alpha) if ok else None, "a (D x count x M x N)")
+    fn = getattr(load_library(), "gpuntt_keyswitch_reference_mod_up_u%d" % bits)
+    _check(fn(qarr, len(qs), parr, len(ps), int(alpha), px, pa, int(n_power), int(count), int(mode)))
+    return a
+
+
+def keyswitch_reference_mod_down(q_moduli, p_moduli, x, out, n_power, stacks, bits=64):
+    """Host (no GPU): KeySwitchPlan<T>::reference_mod_down -- x holds stacks x M x N words, out stacks x L x N (written
+    and returned)."""
+    qs, qarr = _keyswitch_moduli(q_moduli, bits)
+    ps, parr = _keyswitch_moduli(p_moduli, bits)
+    L, M = len(qs), len(qs) + len(ps)
+    ok = 1 <= int(n_power) <= 28 and int(stacks) >= 0
+    cols = (int(stacks) << int(n_power)) if ok else None
+    px = _keyswitch_host_array(x, bits, cols * M if ok else None, "x (stacks x M x N)")
+    po = _keyswitch_host_array(out, bits, cols * L if ok else None, "out (stacks x L x N)")
+    fn = getattr(load_library(), "gpuntt_keyswitch_reference_mod_down_u%d" % bits)
+    _check(fn(qarr, len(qs), parr, len(ps), px, po, int(n_power), int(stacks)))
+    return out
+
+
+class KeySwitchPlan:
+    """Extension KeySwitchPlan<T> (include/gpuntt/rns/key_switch.cuh): hybrid key switching for the q-base `q_moduli`
+    (L), the special primes `p_moduli` (K) and the digit size `alpha` on a ring of 2^n_power, M = L + K <= 64.
+    forward_table / inverse_table: device tensors as for GPU_NTT / GPU_INTT over the full base (slot i at i << n_power),
+    mod_inverse the M host n^-1 values; all three None: a plan without transforms (mod_up / mod_down only).
+    key_mod_count / key_limbs as for InnerProductPlan.multiply_accumulate.  `workspace`: an optional uint8 device
+    tensor of workspace_bytes() bytes owned by the caller.  `scratch` of the pipeline calls: a device tensor of at least
+    plan.scratch_bytes(count, components) bytes -- the header's static scratch_bytes(L, K, alpha, n_power, count,
+    components) with this plan's shape filled in; keyswitch_scratch_bytes() is that static -- 256-byte aligned, owned by
+    the caller; nothing is allocated by any call."""
+
+    def __init__(self, q_moduli, p_moduli, alpha, n_power, forward_table=None, inverse_table=None, mod_inverse=None,
+                 reduction_poly=X_N_plus, batch_hint=1024, key_mod_count=None, key_limbs=None, bits=64, stream=None,
+                 workspace=None):
+        lib = load_library()
+        qs, qarr = _keyswitch_moduli(q_moduli, bits)
+        ps, parr = _keyswitch_moduli(p_moduli, bits)
+        _require_gpu(workspace, forward_table, inverse_table)
+        self.bits, self.q_count, self.p_count, self.mod_count = bits, len(qs), len(ps), len(qs) + len(ps)
+        self.alpha, self.n_power = int(alpha), int(n_power)
+        self.digits = keyswitch_digits(len(qs), alpha)
+        for t in (forward_table, inverse_table):
+            if t is not None and (t.element_size() * 8 != bits or t.numel() < self.mod_count << self.n_power):
+                raise ValueError("a table holds M x N %d-bit words" % bits)
+        ninv = None
+        if mod_inverse is not None:
+            vals = [int(v) for v in mod_inverse]
+            if len(vals) != self.mod_count:
+                raise ValueError("mod_inverse holds one n^-1 per modulus of the full base")
+            ninv = (_ct(bits) * max(1, len(vals)))(*vals)
+        km = self.mod_count if key_mod_count is None else int(key_mod_count)
+        limbs = _innerprod_limbs(key_limbs, self.mod_count)
+        if workspace is not None:
+            need = self.workspace_bytes(len(qs), len(ps), alpha, n_power, bits)  # raises for counts out of range
+            if workspace.numel() * workspace.element_size() < need:
+                raise ValueError("workspace holds fewer than workspace_bytes() bytes")
+        self.key_mod_count = km
+        self._keep = (workspace, forward_table, inverse_table)
+        self._h = ctypes.c_void_p()
+        fn = getattr(lib, "gpuntt_keyswitch_plan_create_u%d" % bits)
+        _check(fn(ctypes.byref(self._h), qarr, len(qs), parr, len(ps), int(alpha), int(n_power), _ptr(forward_table),
+                  _ptr(inverse_table), ninv, int(reduction_poly), int(batch_hint), km, limbs, _ptr(workspace),
+                  _stream(stream)))
+
+    @staticmethod
+    def workspace_bytes(q_count, p_count, alpha, n_power, bits=64):
+        out = ctypes.c_uint64()
+        _check(getattr(load_library(), "gpuntt_keyswitch_plan_workspace_bytes_u%d" % bits)(
+            int(q_count), int(p_count), int(alpha), int(n_power), ctypes.byref(out)))
+        return int(out.value)
+
+    def scratch_bytes(self, count, components=1):
+        return keyswitch_scratch_bytes(self.q_count, self.p_count, self.alpha, self.n_power, count, components,
+                                       self.bits)
+
+    @property
+    def owns_workspace(self):
+        """False: the plan lives in the caller's workspace and has allocated no device memory"""
+        return bool(getattr(load_library(), "gpuntt_keyswitch_plan_owns_workspace_u%d" % self.bits)(self._h))
+
+    def _check_buffers(self, sized):
+        """the library cannot see tensor sizes or types: sized = (tensor, words needed, name) ..."""
+        _require_gpu(*[t for t, _, _ in sized])
+        for t, words, name in sized:
+            if t.element_size() * 8 != self.bits or t.dtype.is_floating_point:
+                raise ValueError("a %d-bit KeySwitchPlan takes %d-bit integer tensors" % (self.bits, self.bits))
+            if words > 0 and t.numel() < words:
+                raise ValueError("%s needs %d words; got %d" % (name, words, t.numel()))
+
+    def _check_scratch(self, scratch, count, components):
+        _require_gpu(scratch)
+        if scratch is None:
+            raise ValueError("the pipeline calls need a caller-owned scratch of scratch_bytes() bytes")
+        if int(count) > 0:
+            if scratch.numel() * scratch.element_size() < self.scratch_bytes(count, components):
+                raise ValueError("scratch holds fewer than scratch_bytes(count, components) bytes")
+            if scratch.data_ptr() % 256:
+                raise ValueError("scratch must be 256-byte aligned")
+
+    def _cols(self, count):
+        return (int(count) << self.n_power) if int(count) > 0 else 0
+
+    def mod_up(self, device_in, device_a, count, mode=CENTRED, stream=None):
+        """device_in T[count][L][N] -> device_a T[D][count][M][N]; one kernel launch"""
+        cols = self._cols(count)
+        self._check_buffers(((device_in, cols * self.q_count, "in (count x L x N)"),
+                             (device_a, cols * self.mod_count * self.digits, "a (D x count x M x N)")))
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_mod_up_u%d" % self.bits)
+        _check(fn(self._h, _ptr(device_in), _ptr(device_a), int(count), int(mode), _stream(stream)))
+
+    def mod_down(self, device_x, device_out, stacks, stream=None):
+        """device_x T[stacks][M][N] -> device_out T[stacks][L][N]; one kernel launch"""
+        cols = self._cols(stacks)
+        self._check_buffers(((device_x, cols * self.mod_count, "x (stacks x M x N)"),
+                             (device_out, cols * self.q_count, "out (stacks x L x N)")))
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_mod_down_u%d" % self.bits)
+        _check(fn(self._h, _ptr(device_x), _ptr(device_out), int(stacks), _stream(stream)))
+
+    def decompose(self, device_c_in, device_a, count, input_ntt=False, scratch=None, stream=None):
+        cols = self._cols(count)
+        self._check_buffers(((device_c_in, cols * self.q_count, "c_in (count x L x N)"),
+                             (device_a, cols * self.mod_count * self.digits, "a (D x count x M x N)")))
+        if input_ntt or scratch is not None:
+            self._check_scratch(scratch, count, 1)
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_decompose_u%d" % self.bits)
+        _check(fn(self._h, _ptr(device_c_in), _ptr(device_a), int(count), int(bool(input_ntt)), _ptr(scratch),
+                  _stream(stream)))
+
+    def _key_words(self, components):
+        return (self.digits * int(components) * self.key_mod_count) << self.n_power
+
+    def switch_digits(self, device_a, device_key, device_out, count, components, output_ntt=False, scratch=None,
+                      stream=None):
+        cols = self._cols(count)
+        ok = 1 <= int(components) <= 4
+        self._check_buffers(((device_a, cols * self.mod_count * self.digits, "a (D x count x M x N)"),
+                             (device_key, self._key_words(components) if ok and cols else 0,
+                              "key (D x C x key_mod_count x N)"),
+                             (device_out, cols * self.q_count * int(components) if ok else 0, "out (C x count x L x N)")))
+        if ok:
+            self._check_scratch(scratch, count, components)
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_switch_digits_u%d" % self.bits)
+        _check(fn(self._h, _ptr(device_a), _ptr(device_key), _ptr(device_out), int(count), int(components),
+                  int(bool(output_ntt)), _ptr(scratch), _stream(stream)))
+
+    def apply(self, device_c_in, device_key, device_out, count, components, input_ntt=False, output_ntt=False,
+              scratch=None, stream=None):
+        cols = self._cols(count)
+        ok = 1 <= int(components) <= 4
+        self._check_buffers(((device_c_in, cols * self.q_count, "c_in (count x L x N)"),
+                             (device_key, self._key_words(components) if ok and cols else 0,
+                              "key (D x C x key_mod_count x N)"),
+                             (device_out, cols * self.q_count * int(components) if ok else 0, "out (C x count x L x N)")))
+        if ok:
+            self._check_scratch(scratch, count, components)
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_apply_u%d" % self.bits)
+        _check(fn(self._h, _ptr(device_c_in), _ptr(device_key), _ptr(device_out), int(count), int(components),
+                  int(bool(input_ntt)), int(bool(output_ntt)), _ptr(scratch), _stream(stream)))
+
+    def close(self):
+        if self._h:
+            getattr(load_library(), "gpuntt_keyswitch_plan_destroy_u%d" % self.bits)(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

@@ -24,178 +24,13 @@
 #include <stdexcept>
 #include <vector>
 
+#include "base_conversion_internal.hpp"
 #include "gpuntt/rns/base_conversion.cuh"
 #include "launch.hpp"
 
 namespace gpuntt
 {
-    namespace kern
-    {
-        constexpr int BC_NT = 128; // lanes per workgroup: L = 64 u64 words per lane are 64 KiB of LDS
-        constexpr int BC_KB = 4;   // outputs per pass over the y_i
-
-        template <typename T> struct BcWide;
-        template <> struct BcWide<Data32>
-        {
-            using type = Data64;
-        };
-        template <> struct BcWide<Data64>
-        {
-            using type = unsigned __int128;
-        };
-
-        __device__ __forceinline__ Data32 bc_mulhi(Data32 a, Data32 b) { return __umulhi(a, b); }
-        __device__ __forceinline__ Data64 bc_mulhi(Data64 a, Data64 b) { return __umul64hi(a, b); }
-
-        // (x * w) mod m, canonical, for ANY word x, w < m < 2^(W-1) and wp = floor(w 2^W / m): the quotient estimate
-        // hi(x * wp) is floor(x w / m) or one less, so the remainder lies in [0, 2m)
-        template <typename T> __device__ __forceinline__ T bc_shoup(T x, T w, T wp, T m)
-        {
-            const T r = x * w - bc_mulhi(x, wp) * m;
-            return r >= m ? r - m : r;
-        }
-
-        // where the plan's constants lie in the workspace, in words: L = in_count, KP = out_count rounded up to BC_KB
-        // (the padding columns of the matrix are zero and are never stored)
-        struct BcOffsets
-        {
-            unsigned q;      // [L]
-            unsigned w;      // [L] qhat_i^-1 mod q_i
-            unsigned wp;     // [L] its Shoup companion
-            unsigned recip;  // [L] R_i (0: q_i is a power of two)
-            unsigned shift;  // [L] b_i - 1
-            unsigned matrix; // [L][KP] qhat_i mod p_j
-            unsigned p;      // [KP]
-            unsigned negq;   // [KP] (-Q) mod p_j
-            unsigned qinv;   // [KP] Q^-1 mod p_j
-            unsigned qinvp;  // [KP] its Shoup companion
-            unsigned t1;     // [KP] 2^W mod p_j
-            unsigned t1p;
-            unsigned t2;     // [KP] 2^2W mod p_j
-            unsigned t2p;
-            unsigned onep;   // [KP] floor(2^W / p_j): the Shoup companion of 1
-        };
-        // the same as pointers into the workspace `base`, in the CONSTANT address space: nothing writes the workspace
-        // while a conversion runs, and a load from that address space at a wave-uniform address is a scalar load
-        // whatever the stores around it are (as plain global pointers the compiler could not rule out the stores to
-        // `out` -- which may alias c, so neither is __restrict__ -- and fetched the matrix rows with vector loads)
-        template <typename T> struct BcConsts
-        {
-            using CP = const T __attribute__((address_space(4)))*;
-            CP q, w, wp, recip, shift, matrix, p, negq, qinv, qinvp, t1, t1p, t2, t2p, onep;
-            __device__ BcConsts(const T* workspace, const BcOffsets& o)
-            {
-                const CP base = (CP) (workspace);
-                q = base + o.q, w = base + o.w, wp = base + o.wp, recip = base + o.recip, shift = base + o.shift;
-                matrix = base + o.matrix, p = base + o.p, negq = base + o.negq, qinv = base + o.qinv;
-                qinvp = base + o.qinvp, t1 = base + o.t1, t1p = base + o.t1p, t2 = base + o.t2, t2p = base + o.t2p;
-                onep = base + o.onep;
-            }
-        };
-
-        constexpr int BC_CHUNK = 16; // terms below 2^(2W-4) (moduli below 2^(W-2)) that a 2W-bit sum holds
-
-        template <typename T, bool CENTRED, bool DIVIDE>
-        __global__ __launch_bounds__(BC_NT) void base_convert(const T* __restrict__ in, const T* c_in, T* out,
-                                                              const T* __restrict__ consts, BcOffsets off,
-                                                              int L, int K, int KP, int n_power,
-                                                              unsigned long long total)
-        {
-            const BcConsts<T> k(consts, off);
-            using W2 = typename BcWide<T>::type;
-            constexpr int W = static_cast<int>(8 * sizeof(T));
-            extern __shared__ __align__(16) unsigned char bc_smem[];
-            T* ys = reinterpret_cast<T*>(bc_smem) + threadIdx.x;
-
-            const unsigned long long t = static_cast<unsigned long long>(blockIdx.x) * BC_NT + threadIdx.x;
-            if (t >= total)
-                return; // (no barrier below)
-            const unsigned long long e = t >> n_power, col = t & ((1ull << n_power) - 1ull);
-            const T* src = in + ((e * static_cast<unsigned>(L)) << n_power) + col;
-
-            W2 zsum = static_cast<W2>(1) << (W - 1);
-#pragma unroll 4
-            for (int i = 0; i < L; i++)
-            {
-                const T q = k.q[i];
-                const T y = bc_shoup<T>(src[static_cast<unsigned long long>(i) << n_power], k.w[i], k.wp[i], q);
-                ys[i * BC_NT] = y;
-                if constexpr (CENTRED)
-                {
-                    const T r = k.recip[i];
-                    const int sh = static_cast<int>(k.shift[i]);
-                    // z_i = (y R_i) >> (b_i - 1) < 2^W; a power of two q_i = 2^(b_i - 1) has R_i = 2^W
-                    const T z = (r != 0) ? static_cast<T>((static_cast<W2>(y) * r) >> sh) : (y << (W - sh));
-                    zsum += z;
-                }
-            }
-            T v = 0;
-            if constexpr (CENTRED)
-                v = static_cast<T>(zsum >> W);
-
-            const unsigned long long obase = ((e * static_cast<unsigned>(K)) << n_power) + col;
-            for (int j0 = static_cast<int>(blockIdx.y) * BC_KB; j0 < K; j0 += static_cast<int>(gridDim.y) * BC_KB)
-            {
-                // BC_CHUNK terms at a time go into a plain 2W-bit sum (no carry to watch); the sums go into the
-                // three-word accumulator {carry, acc}, one carry test per chunk and output
-                W2 acc[BC_KB];
-                T carry[BC_KB];
-#pragma unroll
-                for (int b = 0; b < BC_KB; b++)
-                {
-                    acc[b] = CENTRED ? static_cast<W2>(v) * k.negq[j0 + b] : static_cast<W2>(0);
-                    carry[b] = 0;
-                }
-                typename BcConsts<T>::CP row = k.matrix + j0;
-                for (int i0 = 0; i0 < L; i0 += BC_CHUNK)
-                {
-                    const int i1 = min(i0 + BC_CHUNK, L);
-                    W2 part[BC_KB];
-#pragma unroll
-                    for (int b = 0; b < BC_KB; b++)
-                        part[b] = 0;
-#pragma unroll 2
-                    for (int i = i0; i < i1; i++)
-                    {
-                        const T y = ys[i * BC_NT];
-#pragma unroll
-                        for (int b = 0; b < BC_KB; b++)
-                            part[b] += static_cast<W2>(y) * row[b];
-                        row += KP;
-                    }
-#pragma unroll
-                    for (int b = 0; b < BC_KB; b++)
-                    {
-                        acc[b] += part[b];
-                        carry[b] += (acc[b] < part[b]) ? 1u : 0u;
-                    }
-                }
-#pragma unroll
-                for (int b = 0; b < BC_KB; b++)
-                {
-                    const int j = j0 + b;
-                    if (j < K)
-                    {
-                        const T p = k.p[j];
-                        T r = bc_shoup<T>(static_cast<T>(acc[b] >> W), k.t1[j], k.t1p[j], p);
-                        r += bc_shoup<T>(carry[b], k.t2[j], k.t2p[j], p);
-                        r += bc_shoup<T>(static_cast<T>(acc[b]), T(1), k.onep[j], p); // r < 3 p < 2^W
-                        r = r >= p ? r - p : r;
-                        r = r >= p ? r - p : r;
-                        const unsigned long long o = obase + (static_cast<unsigned long long>(j) << n_power);
-                        if constexpr (DIVIDE)
-                        {
-                            const T cj = c_in[o];
-                            // c - conv as a word that is congruent to it: any word c is read modulo p
-                            const T d = cj >= r ? cj - r : cj + (p - r);
-                            r = bc_shoup<T>(d, k.qinv[j], k.qinvp[j], p);
-                        }
-                        out[o] = r;
-                    }
-                }
-            }
-        }
-    } // namespace kern
+    // kern::base_convert and what it is made of: base_conversion_internal.hpp (key_switch.hip launches its strided form)
 
     namespace host
     {
@@ -246,12 +81,7 @@ namespace gpuntt
             return b;
         }
 
-        // the constants in exact integers (64-bit words for both widths)
-        struct HostConsts
-        {
-            int L, K;
-            std::vector<std::uint64_t> q, p, w, wp, recip, blen, matrix, qmod, negq, qinv, qinvp, t1, t1p, t2, t2p, onep;
-        };
+        using HostConsts = host::BcHostConsts; // the constants in exact integers (64-bit words for both widths)
 
         template <typename T> std::uint64_t checked_value(const Modulus<T>& m)
         {
@@ -386,7 +216,7 @@ namespace gpuntt
             const bool cen = mode == BaseConvMode::centred;
 #define GPUNTT_BC_LAUNCH(CEN, DIV)                                                                                     \
     GPUNTT_LAUNCH((kern::base_convert<T, CEN, DIV>), grid, dim3(kern::BC_NT), lds, stream, in, c, out,                 \
-                  static_cast<const T*>(ws), off, L, K, KP, n_power, total)
+                  static_cast<const T*>(ws), off, L, K, KP, n_power, total, kern::BcStrides<false>{})
             if (cen && divide)
                 GPUNTT_BC_LAUNCH(true, true);
             else if (cen)
@@ -399,6 +229,55 @@ namespace gpuntt
             GPUNTT_HIP_CHECK(hipGetLastError());
         }
     };
+
+    namespace host
+    {
+        template <typename T> std::uint64_t bc_checked_value(const Modulus<T>& m) { return checked_value<T>(m); }
+        template <typename T> BcHostConsts bc_derive(const Modulus<T>* qm, int L, const Modulus<T>* pm, int K)
+        {
+            return derive<T>(qm, L, pm, K);
+        }
+        size_t bc_image_words(int L, int K) { return ws_words(L, K); }
+
+        template <typename T> std::vector<T> bc_image(const BcHostConsts& h, kern::BcOffsets& off)
+        {
+            const int L = h.L, K = h.K, KP = padded(K);
+            std::vector<T> img(ws_words(L, K), T(0));
+            size_t at = 0;
+            auto put = [&](const std::vector<std::uint64_t>& v, size_t slots) {
+                const size_t first = at;
+                for (size_t i = 0; i < v.size(); i++)
+                    img[at + i] = static_cast<T>(v[i]);
+                at += slots;
+                return first;
+            };
+            std::vector<std::uint64_t> shift(L), mat(static_cast<size_t>(L) * KP, 0), ppad(h.p);
+            for (int i = 0; i < L; i++)
+            {
+                shift[i] = h.blen[i] - 1;
+                for (int j = 0; j < K; j++)
+                    mat[static_cast<size_t>(i) * KP + j] = h.matrix[static_cast<size_t>(i) * K + j];
+            }
+            const size_t o_q = put(h.q, L), o_w = put(h.w, L), o_wp = put(h.wp, L), o_r = put(h.recip, L),
+                         o_sh = put(shift, L), o_m = put(mat, static_cast<size_t>(L) * KP), o_p = put(ppad, KP),
+                         o_nq = put(h.negq, KP), o_qi = put(h.qinv, KP), o_qip = put(h.qinvp, KP), o_t1 = put(h.t1, KP),
+                         o_t1p = put(h.t1p, KP), o_t2 = put(h.t2, KP), o_t2p = put(h.t2p, KP), o_one = put(h.onep, KP);
+            auto u = [](size_t v) { return static_cast<unsigned>(v); };
+            off = kern::BcOffsets{u(o_q),  u(o_w),   u(o_wp), u(o_r),   u(o_sh), u(o_m),  u(o_p),  u(o_nq),
+                                  u(o_qi), u(o_qip), u(o_t1), u(o_t1p), u(o_t2), u(o_t2p), u(o_one)};
+            return img;
+        }
+
+        int bc_ksplit(unsigned long long tiles, int K) { return base_conv_ksplit(tiles, K); }
+
+#define GPUNTT_BC_INTERNAL(T)                                                                                          \
+    template std::uint64_t bc_checked_value<T>(const Modulus<T>&);                                                     \
+    template BcHostConsts bc_derive<T>(const Modulus<T>*, int, const Modulus<T>*, int);                                \
+    template std::vector<T> bc_image<T>(const BcHostConsts&, kern::BcOffsets&);
+        GPUNTT_BC_INTERNAL(Data32)
+        GPUNTT_BC_INTERNAL(Data64)
+#undef GPUNTT_BC_INTERNAL
+    } // namespace host
 
     template <typename T> size_t BaseConvPlan<T>::workspace_bytes(int in_count, int out_count)
     {
@@ -416,26 +295,8 @@ namespace gpuntt
     {
         const HostConsts h = derive<T>(in_moduli_host, in_count, out_moduli_host, out_count);
         const int L = h.L, K = h.K, KP = padded(K);
-        std::vector<T> img(ws_words(L, K), T(0));
-        size_t at = 0;
-        auto put = [&](const std::vector<std::uint64_t>& v, size_t slots) {
-            const size_t first = at;
-            for (size_t i = 0; i < v.size(); i++)
-                img[at + i] = static_cast<T>(v[i]);
-            at += slots;
-            return first;
-        };
-        std::vector<std::uint64_t> shift(L), mat(static_cast<size_t>(L) * KP, 0), ppad(h.p);
-        for (int i = 0; i < L; i++)
-        {
-            shift[i] = h.blen[i] - 1;
-            for (int j = 0; j < K; j++)
-                mat[static_cast<size_t>(i) * KP + j] = h.matrix[static_cast<size_t>(i) * K + j];
-        }
-        const size_t o_q = put(h.q, L), o_w = put(h.w, L), o_wp = put(h.wp, L), o_r = put(h.recip, L),
-                     o_sh = put(shift, L), o_m = put(mat, static_cast<size_t>(L) * KP), o_p = put(ppad, KP),
-                     o_nq = put(h.negq, KP), o_qi = put(h.qinv, KP), o_qip = put(h.qinvp, KP), o_t1 = put(h.t1, KP),
-                     o_t1p = put(h.t1p, KP), o_t2 = put(h.t2, KP), o_t2p = put(h.t2p, KP), o_one = put(h.onep, KP);
+        kern::BcOffsets off{};
+        const std::vector<T> img = host::bc_image<T>(h, off);
 
         Impl* p = new Impl;
         p->L = L, p->K = K, p->KP = KP;
@@ -458,9 +319,7 @@ namespace gpuntt
             delete p;
             throw;
         }
-        auto u = [](size_t v) { return static_cast<unsigned>(v); };
-        p->off = kern::BcOffsets{u(o_q),  u(o_w),   u(o_wp), u(o_r),   u(o_sh), u(o_m),  u(o_p),  u(o_nq),
-                                 u(o_qi), u(o_qip), u(o_t1), u(o_t1p), u(o_t2), u(o_t2p), u(o_one)};
+        p->off = off;
         p_ = p;
     }
 

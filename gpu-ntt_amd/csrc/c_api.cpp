@@ -12,6 +12,7 @@
 #include "gpuntt/ntt_merge/ntt.cuh"
 #include "gpuntt/rns/base_conversion.cuh"
 #include "gpuntt/rns/inner_product.cuh"
+#include "gpuntt/rns/key_switch.cuh"
 #include "gpuntt_c.h"
 #include "test_hooks.h"
 
@@ -850,6 +851,133 @@ extern "C"
             const auto ms = to_mods<T>(moduli_host, mod_count, "Invalid mod_count!");              \
             InnerProductPlan<T>::reference(ms.data(), mod_count, a_host, key_host, out_host, n_power, digits,     \
                                            components, count, accumulate != 0, key_mod_count, key_limbs_host);    \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_workspace_bytes_##S(int q_count, int p_count, int alpha, int n_power,               \
+                                                  uint64_t* bytes_host)                           \
+    {                                                                                             \
+        GPUNTT_NEED(bytes_host)                                                                   \
+        return guarded(                                                                           \
+            [&] { *bytes_host = KeySwitchPlan<T>::workspace_bytes(q_count, p_count, alpha, n_power); });          \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_scratch_bytes_##S(int q_count, int p_count, int alpha, int n_power, int count,      \
+                                                int components, uint64_t* bytes_host)             \
+    {                                                                                             \
+        GPUNTT_NEED(bytes_host)                                                                   \
+        return guarded([&] {                                                                      \
+            *bytes_host = KeySwitchPlan<T>::scratch_bytes(q_count, p_count, alpha, n_power, count, components);   \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_create_##S(gpuntt_keyswitch_plan** plan_host, const CM* q_moduli_host, int q_count, \
+                                         const CM* p_moduli_host, int p_count, int alpha, int n_power,            \
+                                         const T* forward_table, const T* inverse_table,          \
+                                         const T* mod_inverse_host, int reduction_poly, int batch_hint,           \
+                                         int key_mod_count, const int* key_limbs_host, void* workspace_device,    \
+                                         void* stream)                                            \
+    {                                                                                             \
+        GPUNTT_NEED(plan_host)                                                                    \
+        return guarded([&] {                                                                      \
+            const auto qs = to_mods<T>(q_moduli_host, q_count, "Invalid q_count!");                \
+            const auto ps = to_mods<T>(p_moduli_host, p_count, "Invalid p_count!");                \
+            if (reduction_poly != GPUNTT_X_N_PLUS && reduction_poly != GPUNTT_X_N_MINUS)          \
+                throw std::invalid_argument("Invalid reduction_poly!");                           \
+            *plan_host = reinterpret_cast<gpuntt_keyswitch_plan*>(new KeySwitchPlan<T>(           \
+                qs.data(), q_count, ps.data(), p_count, alpha, n_power, forward_table, inverse_table,             \
+                mod_inverse_host, static_cast<ReductionPolynomial>(reduction_poly), batch_hint, key_mod_count,    \
+                key_limbs_host, static_cast<hipStream_t>(stream), workspace_device));             \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_mod_up_##S(const gpuntt_keyswitch_plan* plan, const T* in, T* a, int count,          \
+                                         int mode, void* stream)                                  \
+    {                                                                                             \
+        GPUNTT_NEED(plan, in, a)                                                                  \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->mod_up(in, a, count, static_cast<BaseConvMode>(mode), \
+                                                                    static_cast<hipStream_t>(stream));            \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_mod_down_##S(const gpuntt_keyswitch_plan* plan, const T* x, T* out, int stacks,      \
+                                           void* stream)                                          \
+    {                                                                                             \
+        GPUNTT_NEED(plan, x, out)                                                                 \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->mod_down(x, out, stacks,              \
+                                                                      static_cast<hipStream_t>(stream));          \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_decompose_##S(const gpuntt_keyswitch_plan* plan, const T* c_in, T* a, int count,     \
+                                            int input_ntt, void* scratch, void* stream)           \
+    {                                                                                             \
+        GPUNTT_NEED(plan, c_in, a)                                                                \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->decompose(c_in, a, count, input_ntt != 0, scratch,   \
+                                                                       static_cast<hipStream_t>(stream));         \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_switch_digits_##S(const gpuntt_keyswitch_plan* plan, const T* a, const T* key,       \
+                                                T* out, int count, int components, int output_ntt, void* scratch,  \
+                                                void* stream)                                     \
+    {                                                                                             \
+        GPUNTT_NEED(plan, a, key, out, scratch)                                                   \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->switch_digits(                       \
+                a, key, out, count, components, output_ntt != 0, scratch, static_cast<hipStream_t>(stream));      \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_apply_##S(const gpuntt_keyswitch_plan* plan, const T* c_in, const T* key, T* out,    \
+                                        int count, int components, int input_ntt, int output_ntt, void* scratch,  \
+                                        void* stream)                                             \
+    {                                                                                             \
+        GPUNTT_NEED(plan, c_in, key, out, scratch)                                                \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->apply(c_in, key, out, count, components,              \
+                                                                   input_ntt != 0, output_ntt != 0, scratch,      \
+                                                                   static_cast<hipStream_t>(stream));             \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_owns_workspace_##S(const gpuntt_keyswitch_plan* plan)               \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return reinterpret_cast<const KeySwitchPlan<T>*>(plan)->owns_workspace() ? 1 : 0;         \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_destroy_##S(gpuntt_keyswitch_plan* plan)                            \
+    {                                                                                             \
+        return guarded([&] { delete reinterpret_cast<KeySwitchPlan<T>*>(plan); });                \
+    }                                                                                             \
+    int gpuntt_keyswitch_constants_##S(const CM* q_moduli_host, int q_count, const CM* p_moduli_host, int p_count, \
+                                       int alpha, T* const* arrays_host)                          \
+    {                                                                                             \
+        GPUNTT_NEED(arrays_host)                                                                  \
+        return guarded([&] {                                                                      \
+            const auto qs = to_mods<T>(q_moduli_host, q_count, "Invalid q_count!");                \
+            const auto ps = to_mods<T>(p_moduli_host, p_count, "Invalid p_count!");                \
+            T* const* v = arrays_host;                                                            \
+            KeySwitchPlan<T>::constants(qs.data(), q_count, ps.data(), p_count, alpha,            \
+                                        KeySwitchConstants<T>{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], \
+                                                              v[9], v[10], v[11], v[12], v[13], v[14], v[15],     \
+                                                              v[16], v[17]});                     \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_reference_mod_up_##S(const CM* q_moduli_host, int q_count, const CM* p_moduli_host,       \
+                                              int p_count, int alpha, const T* in_host, T* a_host, int n_power,   \
+                                              int count, int mode)                                \
+    {                                                                                             \
+        return guarded([&] {                                                                      \
+            const auto qs = to_mods<T>(q_moduli_host, q_count, "Invalid q_count!");                \
+            const auto ps = to_mods<T>(p_moduli_host, p_count, "Invalid p_count!");                \
+            KeySwitchPlan<T>::reference_mod_up(qs.data(), q_count, ps.data(), p_count, alpha, in_host, a_host,    \
+                                               n_power, count, static_cast<BaseConvMode>(mode));  \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_reference_mod_down_##S(const CM* q_moduli_host, int q_count, const CM* p_moduli_host,     \
+                                                int p_count, const T* x_host, T* out_host, int n_power,           \
+                                                int stacks)                                       \
+    {                                                                                             \
+        return guarded([&] {                                                                      \
+            const auto qs = to_mods<T>(q_moduli_host, q_count, "Invalid q_count!");                \
+            const auto ps = to_mods<T>(p_moduli_host, p_count, "Invalid p_count!");                \
+            KeySwitchPlan<T>::reference_mod_down(qs.data(), q_count, ps.data(), p_count, x_host, out_host,        \
+                                                 n_power, stacks);                                \
         });                                                                                       \
     }                                                                                             \
     int gpuntt_4step_plan_workspace_bytes_##S(int n_power, uint64_t* bytes_host)                  \

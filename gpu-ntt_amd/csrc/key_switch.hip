@@ -1,0 +1,819 @@
+// key_switch.hip -- hybrid key switching (extension, include/gpuntt/rns/key_switch.cuh).
+//
+// ks_mod_up: ModUp of ALL digits from one read of the input.  One lane owns one coefficient column of one input: it
+// reads its L words once (coalesced: consecutive lanes, consecutive columns) and parks two words per limb in LDS, at
+// [i][lane] -- y_i, one exact Shoup product with the constants of the limb's OWN digit, and the canonical word, one Shoup
+// product against the companion of 1 (a conditional subtraction does not reduce a 64-bit word modulo a 20-bit q).  A lane
+// only reads back what it wrote: no barrier.  The outputs are then walked as (digit d, block of KS_KB moduli) pairs: a
+// block inside S_d is KS_KB stores of parked words; any other block is the multiply-accumulate of base_conversion.hip
+// over i in S_d only -- KS_KB three-word accumulators, BC_CHUNK terms per 2W-bit partial sum, the chunk hand-over kept
+// because alpha may exceed a chunk -- followed by the three-product fold, with the parked word stored instead for the
+// moduli of the block that do lie in S_d (their matrix column is zero).  The live state is KS_KB accumulators whatever
+// L, M and D are.  The centred mode's v_d is recomputed only when the walk enters another digit: once per digit and
+// workgroup.  Stores (D M words per column) dominate loads (L words) and carry no lane condition.  Every constant is
+// indexed by wave-uniform values and comes through the constant address space, hence the scalar cache.
+//
+// Small count * N: blockIdx.y splits the (d, block) pairs of a column tile over several workgroups, each of which
+// re-reads the tile's input (from L2) and recomputes the parked words -- ks_split(), as base_conv_ksplit().
+//
+// mod_down: kern::base_convert<T, centred, divide, STRIDED> of base_conversion_internal.hpp -- the shared kernel, the same
+// constants image (bc_image) -- with the stack strides of the full base: the special limbs and the q-limbs are read where
+// the inner product left them, inside the M-limb stacks.  The strides are a compile-time form of the kernel, so the dense
+// instantiations behind BaseConvPlan keep their registers.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <memory>
+#include <stdexcept>
+#include <vector>
+
+#include "base_conversion_internal.hpp"
+#include "gpuntt/ntt_merge/ntt.cuh"
+#include "gpuntt/rns/key_switch.cuh"
+#include "launch.hpp"
+
+namespace gpuntt
+{
+    namespace kern
+    {
+        constexpr int KS_NT = 128;    // lanes per workgroup at most; 64 when two words per limb and lane pass 64 KiB of LDS
+        constexpr int KS_KB = 4;      // moduli per pass over the y_i of a digit
+        constexpr size_t KS_LDS = 65536;
+
+        // BcWide, bc_shoup, BC_CHUNK: base_conversion_internal.hpp
+
+        // where the ModUp constants lie in the workspace, in words; MP = M rounded up to KS_KB (padding: zero)
+        struct KsOffsets
+        {
+            unsigned q;      // [L]
+            unsigned w;      // [L] (Q_d(i) / q_i)^-1 mod q_i
+            unsigned wp;     // [L] its Shoup companion
+            unsigned recip;  // [L] R_i (0: q_i is a power of two)
+            unsigned shift;  // [L] b_i - 1
+            unsigned matrix; // [L][MP] (Q_d(i) / q_i) mod modulus m, 0 for m in S_d(i)
+            unsigned mod;    // [MP] the full base
+            unsigned t1;     // [MP] 2^W mod modulus m
+            unsigned t1p;
+            unsigned t2;     // [MP] 2^2W mod modulus m
+            unsigned t2p;
+            unsigned onep;   // [MP] floor(2^W / modulus m): the Shoup companion of 1
+            unsigned negq;   // [D][MP] (-Q_d) mod modulus m
+        };
+        template <typename T> struct KsConsts
+        {
+            using CP = const T __attribute__((address_space(4)))*;
+            CP q, w, wp, recip, shift, matrix, mod, t1, t1p, t2, t2p, onep, negq;
+            __device__ KsConsts(const T* workspace, const KsOffsets& o)
+            {
+                const CP base = (CP) (workspace);
+                q = base + o.q, w = base + o.w, wp = base + o.wp, recip = base + o.recip, shift = base + o.shift;
+                matrix = base + o.matrix, mod = base + o.mod, t1 = base + o.t1, t1p = base + o.t1p, t2 = base + o.t2;
+                t2p = base + o.t2p, onep = base + o.onep, negq = base + o.negq;
+            }
+        };
+
+        // in: T[count][L][N]; a: T[D][count][M][N], digit_stride = count M N words; total = count N columns
+        template <typename T, bool CENTRED>
+        __global__ __launch_bounds__(KS_NT) void ks_mod_up(const T* __restrict__ in, T* __restrict__ a,
+                                                           const T* __restrict__ consts, KsOffsets off, int L, int M,
+                                                           int MP, int alpha, int D, int n_power,
+                                                           unsigned long long total, unsigned long long digit_stride)
+        {
+            const KsConsts<T> k(consts, off);
+            using W2 = typename BcWide<T>::type;
+            constexpr int W = static_cast<int>(8 * sizeof(T));
+            extern __shared__ __align__(16) unsigned char ks_smem[];
+            const int nt = static_cast<int>(blockDim.x);
+            T* ys = reinterpret_cast<T*>(ks_smem) + threadIdx.x; // y_i at ys[i * nt]
+            T* cs = ys + L * nt;                                  // in[i] mod q_i at cs[i * nt]
+
+            const unsigned long long t = static_cast<unsigned long long>(blockIdx.x) * nt + threadIdx.x;
+            if (t >= total)
+                return; // (no barrier below)
+            const unsigned long long e = t >> n_power, col = t & ((1ull << n_power) - 1ull);
+            const T* src = in + ((e * static_cast<unsigned>(L)) << n_power) + col;
+#pragma unroll 4
+            for (int i = 0; i < L; i++)
+            {
+                const T q = k.q[i];
+                const T x = src[static_cast<unsigned long long>(i) << n_power];
+                ys[i * nt] = bc_shoup<T>(x, k.w[i], k.wp[i], q);
+                cs[i * nt] = bc_shoup<T>(x, T(1), k.onep[i], q);
+            }
+
+            const unsigned long long abase = ((e * static_cast<unsigned>(M)) << n_power) + col;
+            const int jblocks = MP / KS_KB, pairs = D * jblocks;
+            int v_digit = -1;
+            T v = 0;
+            for (int pi = static_cast<int>(blockIdx.y); pi < pairs; pi += static_cast<int>(gridDim.y))
+            {
+                const int d = pi / jblocks, j0 = (pi - d * jblocks) * KS_KB;
+                const int lo = d * alpha, hi = min(lo + alpha, L); // S_d
+                T* dst = a + static_cast<unsigned long long>(d) * digit_stride + abase;
+                if (j0 >= lo && j0 + KS_KB <= hi)
+                {
+#pragma unroll
+                    for (int b = 0; b < KS_KB; b++)
+                        dst[static_cast<unsigned long long>(j0 + b) << n_power] = cs[(j0 + b) * nt];
+                    continue;
+                }
+                if constexpr (CENTRED)
+                {
+                    if (d != v_digit) // pi only grows: once per digit
+                    {
+                        W2 zsum = static_cast<W2>(1) << (W - 1);
+                        for (int i = lo; i < hi; i++)
+                        {
+                            const T y = ys[i * nt];
+                            const T r = k.recip[i];
+                            const int sh = static_cast<int>(k.shift[i]);
+                            // z_i = (y R_i) >> (b_i - 1) < 2^W; a power of two q_i = 2^(b_i - 1) has R_i = 2^W
+                            const T z = (r != 0) ? static_cast<T>((static_cast<W2>(y) * r) >> sh) : (y << (W - sh));
+                            zsum += z;
+                        }
+                        v = static_cast<T>(zsum >> W);
+                        v_digit = d;
+                    }
+                }
+                W2 acc[KS_KB];
+                T carry[KS_KB];
+#pragma unroll
+                for (int b = 0; b < KS_KB; b++)
+                {
+                    acc[b] = CENTRED ? static_cast<W2>(v) * k.negq[d * MP + j0 + b] : static_cast<W2>(0);
+                    carry[b] = 0;
+                }
+                typename KsConsts<T>::CP row = k.matrix + lo * MP + j0;
+                for (int i0 = lo; i0 < hi; i0 += BC_CHUNK)
+                {
+                    const int i1 = min(i0 + BC_CHUNK, hi);
+                    W2 part[KS_KB];
+#pragma unroll
+                    for (int b = 0; b < KS_KB; b++)
+                        part[b] = 0;
+#pragma unroll 2
+                    for (int i = i0; i < i1; i++)
+                    {
+                        const T y = ys[i * nt];
+#pragma unroll
+                        for (int b = 0; b < KS_KB; b++)
+                            part[b] += static_cast<W2>(y) * row[b];
+                        row += MP;
+                    }
+#pragma unroll
+                    for (int b = 0; b < KS_KB; b++)
+                    {
+                        acc[b] += part[b];
+                        carry[b] += (acc[b] < part[b]) ? 1u : 0u;
+                    }
+                }
+#pragma unroll
+                for (int b = 0; b < KS_KB; b++)
+                {
+                    const int m = j0 + b;
+                    if (m < M)
+                    {
+                        T r;
+                        if (m >= lo && m < hi)
+                            r = cs[m * nt];
+                        else
+                        {
+                            const T p = k.mod[m];
+                            r = bc_shoup<T>(static_cast<T>(acc[b] >> W), k.t1[m], k.t1p[m], p);
+                            r += bc_shoup<T>(carry[b], k.t2[m], k.t2p[m], p);
+                            r += bc_shoup<T>(static_cast<T>(acc[b]), T(1), k.onep[m], p); // r < 3 p < 2^W
+                            r = r >= p ? r - p : r;
+                            r = r >= p ? r - p : r;
+                        }
+                        dst[static_cast<unsigned long long>(m) << n_power] = r;
+                    }
+                }
+            }
+        }
+
+    } // namespace kern
+
+    namespace host
+    {
+        namespace
+        {
+            std::atomic<int> g_ks_split{0}; // test hook keyswitch_split: 0 = ks_split(), n = n workgroups per column tile
+        }
+        void keyswitch_set_split(int v) { g_ks_split.store(v, std::memory_order_relaxed); }
+    } // namespace host
+
+    namespace
+    {
+        using U128 = unsigned __int128;
+
+        int ks_padded(int M) { return (M + kern::KS_KB - 1) / kern::KS_KB * kern::KS_KB; }
+        size_t ks_align(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+        // everything the host derives for one (q-base, special base, alpha), in exact integers
+        struct KsHost
+        {
+            int L = 0, K = 0, M = 0, alpha = 0, D = 0;
+            std::vector<std::uint64_t> mod;                                // [M] the full base
+            std::vector<host::BcHostConsts> up;                            // [D] {q_i : i in S_d} -> the complement
+            host::BcHostConsts down;                                       // {p_k} -> {q_j}
+            std::vector<std::uint64_t> t1, t1p, t2, t2p, onep;             // [M]
+            int lo(int d) const { return d * alpha; }
+            int hi(int d) const { return std::min((d + 1) * alpha, L); }
+        };
+
+        void ks_check_counts(int L, int K, int alpha)
+        {
+            if (L < 1 || L > INNERPROD_MAX_MODULI)
+                throw std::invalid_argument("Invalid q_count!");
+            if (K < 1 || K > INNERPROD_MAX_MODULI || L + K > INNERPROD_MAX_MODULI)
+                throw std::invalid_argument("Invalid p_count!");
+            if (alpha < 1)
+                throw std::invalid_argument("Invalid alpha!");
+        }
+        void ks_check_n_power(int n_power)
+        {
+            if (n_power <= 0 || n_power >= 29)
+                throw std::invalid_argument("Invalid n_power range!");
+        }
+        int ks_digits(int L, int alpha) { return static_cast<int>((static_cast<long long>(L) + alpha - 1) / alpha); }
+
+        template <typename T>
+        KsHost ks_derive(const Modulus<T>* qm, int L, const Modulus<T>* pm, int K, int alpha, bool digits = true)
+        {
+            constexpr int W = static_cast<int>(8 * sizeof(T));
+            ks_check_counts(L, K, alpha);
+            if (qm == nullptr || pm == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            KsHost h;
+            h.L = L, h.K = K, h.M = L + K, h.alpha = alpha > L ? L : alpha, h.D = ks_digits(L, h.alpha);
+            std::vector<Modulus<T>> full(qm, qm + L);
+            full.insert(full.end(), pm, pm + K);
+            for (const Modulus<T>& m : full)
+                h.mod.push_back(host::bc_checked_value<T>(m));
+            // {p} -> {q} checks p pairwise and every p against every q; the q among themselves here (the digits would
+            // find the same pairs, but reference_mod_down derives none)
+            h.down = host::bc_derive<T>(pm, K, qm, L);
+            for (int i = 0; i < L; i++)
+                for (int o = i + 1; o < L; o++)
+                    if (std::__gcd(h.mod[i], h.mod[o]) != 1)
+                        throw std::invalid_argument("Input base moduli are not pairwise coprime!");
+            for (int d = 0; digits && d < h.D; d++)
+            {
+                std::vector<Modulus<T>> rest(full.begin(), full.begin() + h.lo(d));
+                rest.insert(rest.end(), full.begin() + h.hi(d), full.end());
+                h.up.push_back(host::bc_derive<T>(qm + h.lo(d), h.hi(d) - h.lo(d), rest.data(),
+                                                  static_cast<int>(rest.size())));
+            }
+            for (int m = 0; m < h.M; m++)
+            {
+                const std::uint64_t q = h.mod[m];
+                const std::uint64_t t1 = static_cast<std::uint64_t>((static_cast<U128>(1) << W) % q);
+                const std::uint64_t t2 = static_cast<std::uint64_t>(static_cast<U128>(t1) * t1 % q);
+                auto shoup = [&](std::uint64_t v) { return static_cast<std::uint64_t>((static_cast<U128>(v) << W) / q); };
+                h.t1.push_back(t1), h.t1p.push_back(shoup(t1)), h.t2.push_back(t2), h.t2p.push_back(shoup(t2));
+                h.onep.push_back(shoup(1));
+            }
+            return h;
+        }
+
+        // column of modulus m in the output base of digit d (the complement of S_d in full-base order); m not in S_d
+        int ks_column(const KsHost& h, int d, int m) { return m < h.lo(d) ? m : m - (h.hi(d) - h.lo(d)); }
+
+        size_t ks_up_words(int L, int M, int D)
+        {
+            const size_t MP = static_cast<size_t>(ks_padded(M));
+            return 5 * static_cast<size_t>(L) + static_cast<size_t>(L) * MP + 6 * MP + static_cast<size_t>(D) * MP;
+        }
+
+        template <typename T> std::vector<T> ks_up_image(const KsHost& h, kern::KsOffsets& off)
+        {
+            const int L = h.L, M = h.M, D = h.D, MP = ks_padded(M);
+            std::vector<T> img(ks_up_words(L, M, D), T(0));
+            size_t at = 0;
+            auto take = [&](size_t words) {
+                const size_t first = at;
+                at += words;
+                return first;
+            };
+            const size_t o_q = take(L), o_w = take(L), o_wp = take(L), o_r = take(L), o_sh = take(L),
+                         o_m = take(static_cast<size_t>(L) * MP), o_mod = take(MP), o_t1 = take(MP), o_t1p = take(MP),
+                         o_t2 = take(MP), o_t2p = take(MP), o_one = take(MP), o_nq = take(static_cast<size_t>(D) * MP);
+            for (int d = 0; d < D; d++)
+            {
+                const host::BcHostConsts& u = h.up[d];
+                for (int i = h.lo(d); i < h.hi(d); i++)
+                {
+                    const int li = i - h.lo(d);
+                    img[o_q + i] = static_cast<T>(u.q[li]), img[o_w + i] = static_cast<T>(u.w[li]);
+                    img[o_wp + i] = static_cast<T>(u.wp[li]), img[o_r + i] = static_cast<T>(u.recip[li]);
+                    img[o_sh + i] = static_cast<T>(u.blen[li] - 1);
+                    for (int m = 0; m < M; m++)
+                        if (m < h.lo(d) || m >= h.hi(d))
+                            img[o_m + static_cast<size_t>(i) * MP + m] =
+                                static_cast<T>(u.matrix[static_cast<size_t>(li) * u.K + ks_column(h, d, m)]);
+                }
+                for (int m = 0; m < M; m++)
+                    if (m < h.lo(d) || m >= h.hi(d))
+                        img[o_nq + static_cast<size_t>(d) * MP + m] = static_cast<T>(u.negq[ks_column(h, d, m)]);
+            }
+            for (int m = 0; m < M; m++)
+            {
+                img[o_mod + m] = static_cast<T>(h.mod[m]), img[o_t1 + m] = static_cast<T>(h.t1[m]);
+                img[o_t1p + m] = static_cast<T>(h.t1p[m]), img[o_t2 + m] = static_cast<T>(h.t2[m]);
+                img[o_t2p + m] = static_cast<T>(h.t2p[m]), img[o_one + m] = static_cast<T>(h.onep[m]);
+            }
+            auto u32 = [](size_t v) { return static_cast<unsigned>(v); };
+            off = kern::KsOffsets{u32(o_q),  u32(o_w),   u32(o_wp), u32(o_r),   u32(o_sh),  u32(o_m), u32(o_mod),
+                                  u32(o_t1), u32(o_t1p), u32(o_t2), u32(o_t2p), u32(o_one), u32(o_nq)};
+            return img;
+        }
+
+        // Workgroups per column tile.  A workgroup that owns all (digit, block) pairs of a tile reads the input once.
+        // Below two workgroups per CU (256 CUs) the pairs are spread over up to 8 workgroups per tile, which re-read
+        // the tile's input from L2 and recompute the parked words.  Both numbers are estimates, as in
+        // base_conv_ksplit(), not measured: DESIGN.md 3.12.
+        int ks_split(unsigned long long tiles, int pairs)
+        {
+            const int forced = host::g_ks_split.load(std::memory_order_relaxed);
+            int s = 1;
+            if (forced > 0)
+                s = forced;
+            else
+                while (s < 8 && tiles * s < 512)
+                    s *= 2;
+            return s < pairs ? s : pairs;
+        }
+
+        bool ks_overlap(const void* a, std::uint64_t a_bytes, const void* b, std::uint64_t b_bytes)
+        {
+            const auto al = reinterpret_cast<uintptr_t>(a), bl = reinterpret_cast<uintptr_t>(b);
+            return al < bl + b_bytes && bl < al + a_bytes;
+        }
+
+        // the argument checks of mod_up / mod_down (device or host arrays alike)
+        template <typename T>
+        void ks_check_mod_up(int L, int M, int D, const T* in, const T* a, int n_power, int count, BaseConvMode mode)
+        {
+            ks_check_n_power(n_power);
+            if (mode != BaseConvMode::approximate && mode != BaseConvMode::centred)
+                throw std::invalid_argument("Invalid mode!");
+            if (count < 0)
+                throw std::invalid_argument("Invalid count!");
+            if (in == nullptr || a == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n_power;
+            if (ks_overlap(in, cols * L * sizeof(T), a, cols * M * D * sizeof(T)) && count > 0)
+                throw std::invalid_argument("ModUp input and output overlap!");
+        }
+        template <typename T>
+        void ks_check_mod_down(int L, int M, const T* x, const T* out, int n_power, int stacks)
+        {
+            ks_check_n_power(n_power);
+            if (stacks < 0)
+                throw std::invalid_argument("Invalid stacks!");
+            if (x == nullptr || out == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            const std::uint64_t cols = static_cast<std::uint64_t>(stacks) << n_power;
+            if (ks_overlap(x, cols * M * sizeof(T), out, cols * L * sizeof(T)) && stacks > 0)
+                throw std::invalid_argument("ModDown input and output overlap!");
+        }
+
+        struct KsLayout // the workspace, in bytes
+        {
+            size_t up, down, inner, ntt_full_f, ntt_full_i, ntt_q_i, ntt_q_f, total;
+        };
+        template <typename T> KsLayout ks_layout(int L, int K, int alpha, int n_power)
+        {
+            ks_check_counts(L, K, alpha);
+            ks_check_n_power(n_power);
+            const int M = L + K, D = ks_digits(L, alpha > L ? L : alpha);
+            KsLayout w{};
+            size_t at = 0;
+            auto take = [&](size_t bytes) {
+                const size_t first = at;
+                at += ks_align(bytes);
+                return first;
+            };
+            w.up = take(ks_up_words(L, M, D) * sizeof(T));
+            w.down = take(host::bc_image_words(K, L) * sizeof(T));
+            w.inner = take(InnerProductPlan<T>::workspace_bytes(M));
+            w.ntt_full_f = take(NTTPlan<T>::workspace_bytes(n_power, M));
+            w.ntt_full_i = take(NTTPlan<T>::workspace_bytes(n_power, M));
+            w.ntt_q_i = take(NTTPlan<T>::workspace_bytes(n_power, L));
+            w.ntt_q_f = take(NTTPlan<T>::workspace_bytes(n_power, L));
+            w.total = at;
+            return w;
+        }
+
+        struct KsScratch // the caller's scratch, in bytes
+        {
+            size_t a, c_coeff, inner_out, total; // c_coeff does not move with `components`: decompose needs no C
+        };
+        template <typename T> KsScratch ks_scratch(int L, int M, int D, int n_power, int count, int components)
+        {
+            if (count < 0)
+                throw std::invalid_argument("Invalid count!");
+            if (components < 1 || components > INNERPROD_MAX_COMPONENTS)
+                throw std::invalid_argument("Invalid components!");
+            const size_t poly = (static_cast<size_t>(count) << n_power) * sizeof(T);
+            KsScratch s{};
+            s.a = 0;
+            s.c_coeff = s.a + ks_align(poly * M * D);
+            s.inner_out = s.c_coeff + ks_align(poly * L);
+            s.total = s.inner_out + ks_align(poly * M * components);
+            return s;
+        }
+    } // namespace
+
+    template <typename T> struct KeySwitchPlan<T>::Impl
+    {
+        int L = 0, K = 0, M = 0, alpha = 0, D = 0, n = 0, KM = 0;
+        std::vector<int> limbs;
+        char* ws = nullptr;
+        bool owns = false;
+        KsLayout lay{};
+        kern::KsOffsets up_off{};
+        kern::BcOffsets down_off{};
+        std::unique_ptr<InnerProductPlan<T>> inner;
+        std::unique_ptr<NTTPlan<T>> ntt_full_f, ntt_full_i, ntt_q_i, ntt_q_f;
+
+        void mod_up(const T* in, T* a, int count, BaseConvMode mode, hipStream_t stream) const
+        {
+            ks_check_mod_up<T>(L, M, D, in, a, n, count, mode);
+            if (count == 0)
+                return;
+            const unsigned long long total = static_cast<unsigned long long>(count) << n;
+            unsigned nt = kern::KS_NT;
+            while (nt > 64 && 2 * static_cast<size_t>(L) * nt * sizeof(T) > kern::KS_LDS)
+                nt /= 2;
+            const unsigned long long tiles = (total + nt - 1) / nt;
+            if (tiles * nt > 0xFFFFFFFFull) // HIP caps a launch at 2^32 - 1 work-items per dimension
+                throw std::invalid_argument("Invalid count!");
+            const int MP = ks_padded(M), pairs = D * (MP / kern::KS_KB);
+            const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(ks_split(tiles, pairs)));
+            const size_t lds = 2 * static_cast<size_t>(L) * nt * sizeof(T);
+            const T* consts = reinterpret_cast<const T*>(ws + lay.up);
+            const unsigned long long digit_stride = total * static_cast<unsigned>(M);
+            if (mode == BaseConvMode::centred)
+                GPUNTT_LAUNCH((kern::ks_mod_up<T, true>), grid, dim3(nt), lds, stream, in, a, consts, up_off, L, M, MP,
+                              alpha, D, n, total, digit_stride);
+            else
+                GPUNTT_LAUNCH((kern::ks_mod_up<T, false>), grid, dim3(nt), lds, stream, in, a, consts, up_off, L, M, MP,
+                              alpha, D, n, total, digit_stride);
+            GPUNTT_HIP_CHECK(hipGetLastError());
+        }
+
+        void mod_down(const T* x, T* out, int stacks, hipStream_t stream) const
+        {
+            ks_check_mod_down<T>(L, M, x, out, n, stacks);
+            if (stacks == 0)
+                return;
+            const unsigned long long poly = 1ull << n, full = static_cast<unsigned long long>(M) << n;
+            const unsigned long long total = static_cast<unsigned long long>(stacks) << n;
+            const unsigned long long tiles = (total + kern::BC_NT - 1) / kern::BC_NT;
+            if (tiles * kern::BC_NT > 0xFFFFFFFFull) // HIP caps a launch at 2^32 - 1 work-items per dimension
+                throw std::invalid_argument("Invalid stacks!");
+            // the input base is {p_k} (K limbs, parked in LDS), the output base {q_j} (L limbs)
+            const int KP = (L + kern::BC_KB - 1) / kern::BC_KB * kern::BC_KB;
+            const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(host::bc_ksplit(tiles, L)));
+            const size_t lds = static_cast<size_t>(K) * kern::BC_NT * sizeof(T);
+            GPUNTT_LAUNCH((kern::base_convert<T, true, true, true>), grid, dim3(kern::BC_NT), lds, stream, x + L * poly, x,
+                          out, reinterpret_cast<const T*>(ws + lay.down), down_off, K, L, KP, n, total,
+                          kern::BcStrides<true>{full, full, static_cast<unsigned long long>(L) << n});
+            GPUNTT_HIP_CHECK(hipGetLastError());
+        }
+
+        void need_transforms() const
+        {
+            if (!ntt_full_f)
+                throw std::invalid_argument("The plan was built without transform tables!");
+        }
+
+        void decompose(const T* c_in, T* a, int count, bool input_ntt, void* scratch, hipStream_t stream) const
+        {
+            need_transforms();
+            const KsScratch s = ks_scratch<T>(L, M, D, n, count, 1);
+            if (c_in == nullptr || a == nullptr || (input_ntt && scratch == nullptr))
+                throw std::invalid_argument("null pointer argument");
+            if (count == 0)
+                return;
+            const T* coeff = c_in;
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const std::uint64_t c_bytes = cols * L * sizeof(T), a_bytes = cols * M * D * sizeof(T);
+            if (ks_overlap(c_in, c_bytes, a, a_bytes)) // every refusal comes before the first launch
+                throw std::invalid_argument("ModUp input and output overlap!");
+            if (input_ntt)
+            {
+                T* tmp = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.c_coeff);
+                if (ks_overlap(tmp, s.inner_out - s.c_coeff, a, a_bytes) ||
+                    ks_overlap(tmp, s.inner_out - s.c_coeff, c_in, c_bytes))
+                    throw std::invalid_argument("The scratch overlaps an operand!");
+                ntt_q_i->execute(c_in, tmp, count * L, stream);
+                coeff = tmp;
+            }
+            mod_up(coeff, a, count, BaseConvMode::centred, stream);
+            ntt_full_f->execute(a, a, D * count * M, stream);
+        }
+
+        void switch_digits(const T* a, const T* key, T* out, int count, int C, bool output_ntt, void* scratch,
+                           hipStream_t stream) const
+        {
+            need_transforms();
+            const KsScratch s = ks_scratch<T>(L, M, D, n, count, C);
+            if (a == nullptr || key == nullptr || out == nullptr || scratch == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            if (count == 0)
+                return;
+            T* acc = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.inner_out);
+            const std::uint64_t acc_bytes = (static_cast<std::uint64_t>(count) << n) * M * C * sizeof(T);
+            if (ks_overlap(acc, acc_bytes, out, (static_cast<std::uint64_t>(count) << n) * L * C * sizeof(T)))
+                throw std::invalid_argument("The scratch overlaps out!");
+            // a or key overlapping the accumulators in the scratch: refused by the inner product's own check of its
+            // output against its inputs, before its launch -- the first of this call
+            inner->multiply_accumulate(a, key, acc, n, D, C, count, false, KM, limbs.data(), stream);
+            ntt_full_i->execute(acc, acc, C * count * M, stream);
+            mod_down(acc, out, C * count, stream);
+            if (output_ntt)
+                ntt_q_f->execute(out, out, C * count * L, stream);
+        }
+    };
+
+    template <typename T> int KeySwitchPlan<T>::digits(int q_count, int alpha)
+    {
+        if (q_count < 1 || alpha < 1)
+            throw std::invalid_argument("Invalid alpha!");
+        return ks_digits(q_count, alpha);
+    }
+
+    template <typename T> size_t KeySwitchPlan<T>::workspace_bytes(int q_count, int p_count, int alpha, int n_power)
+    {
+        return ks_layout<T>(q_count, p_count, alpha, n_power).total;
+    }
+
+    template <typename T>
+    size_t KeySwitchPlan<T>::scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count, int components)
+    {
+        ks_check_counts(q_count, p_count, alpha);
+        ks_check_n_power(n_power);
+        return ks_scratch<T>(q_count, q_count + p_count, ks_digits(q_count, alpha), n_power, count, components).total;
+    }
+
+    template <typename T>
+    KeySwitchPlan<T>::KeySwitchPlan(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* p_moduli_host,
+                                    int p_count, int alpha, int n_power, const Root<T>* forward_table_device,
+                                    const Root<T>* inverse_table_device, const Ninverse<T>* mod_inverse_host,
+                                    ReductionPolynomial reduction_poly, int batch_hint, int key_mod_count,
+                                    const int* key_limbs_host, stream_t stream, void* workspace_device)
+        : p_(nullptr)
+    {
+        const KsHost h = ks_derive<T>(q_moduli_host, q_count, p_moduli_host, p_count, alpha);
+        const KsLayout lay = ks_layout<T>(h.L, h.K, h.alpha, n_power);
+        const bool transforms = forward_table_device != nullptr || inverse_table_device != nullptr;
+        if (transforms && (forward_table_device == nullptr || inverse_table_device == nullptr || mod_inverse_host == nullptr))
+            throw std::invalid_argument("null pointer argument");
+        if (key_mod_count < h.M || key_mod_count > INNERPROD_MAX_KEY_MODULI)
+            throw std::invalid_argument("Invalid key_mod_count!");
+        std::unique_ptr<Impl> p(new Impl);
+        p->L = h.L, p->K = h.K, p->M = h.M, p->alpha = h.alpha, p->D = h.D, p->n = n_power, p->KM = key_mod_count;
+        p->lay = lay;
+        for (int m = 0; m < h.M; m++)
+        {
+            const int l = key_limbs_host != nullptr ? key_limbs_host[m] : m;
+            if (l < 0 || l >= key_mod_count)
+                throw std::invalid_argument("Invalid key_limbs!");
+            p->limbs.push_back(l);
+        }
+        const std::vector<T> up_img = ks_up_image<T>(h, p->up_off);
+        const std::vector<T> down_img = host::bc_image<T>(h.down, p->down_off);
+        std::vector<Modulus<T>> full(q_moduli_host, q_moduli_host + h.L);
+        full.insert(full.end(), p_moduli_host, p_moduli_host + h.K);
+
+        void* raw = workspace_device;
+        if (raw == nullptr)
+        {
+            GPUNTT_HIP_CHECK(hipMalloc(&raw, lay.total));
+            p->owns = true;
+        }
+        p->ws = static_cast<char*>(raw);
+        try
+        {
+            GPUNTT_HIP_CHECK(hipMemcpyAsync(p->ws + lay.up, up_img.data(), up_img.size() * sizeof(T), hipMemcpyHostToDevice,
+                                            stream));
+            GPUNTT_HIP_CHECK(hipMemcpyAsync(p->ws + lay.down, down_img.data(), down_img.size() * sizeof(T),
+                                            hipMemcpyHostToDevice, stream));
+            GPUNTT_HIP_CHECK(hipStreamSynchronize(stream)); // the images die with this scope
+            p->inner.reset(new InnerProductPlan<T>(full.data(), h.M, stream, p->ws + lay.inner));
+            if (transforms)
+            {
+                p->ntt_full_f.reset(new NTTPlan<T>(forward_table_device, full.data(), h.M, n_power, reduction_poly,
+                                                   FORWARD, nullptr, batch_hint, stream, p->ws + lay.ntt_full_f));
+                p->ntt_full_i.reset(new NTTPlan<T>(inverse_table_device, full.data(), h.M, n_power, reduction_poly,
+                                                   INVERSE, mod_inverse_host, batch_hint, stream,
+                                                   p->ws + lay.ntt_full_i));
+                p->ntt_q_i.reset(new NTTPlan<T>(inverse_table_device, full.data(), h.L, n_power, reduction_poly, INVERSE,
+                                                mod_inverse_host, batch_hint, stream, p->ws + lay.ntt_q_i));
+                p->ntt_q_f.reset(new NTTPlan<T>(forward_table_device, full.data(), h.L, n_power, reduction_poly, FORWARD,
+                                                nullptr, batch_hint, stream, p->ws + lay.ntt_q_f));
+            }
+        }
+        catch (...)
+        {
+            p->inner.reset(), p->ntt_full_f.reset(), p->ntt_full_i.reset(), p->ntt_q_i.reset(), p->ntt_q_f.reset();
+            if (p->owns)
+                (void) hipFree(p->ws);
+            throw;
+        }
+        p_ = p.release();
+    }
+
+    template <typename T> KeySwitchPlan<T>::~KeySwitchPlan()
+    {
+        if (p_ == nullptr)
+            return;
+        p_->inner.reset(), p_->ntt_full_f.reset(), p_->ntt_full_i.reset(), p_->ntt_q_i.reset(), p_->ntt_q_f.reset();
+        if (p_->owns)
+            (void) hipFree(p_->ws);
+        delete p_;
+    }
+
+    template <typename T>
+    void KeySwitchPlan<T>::mod_up(const T* device_in, T* device_a, int count, BaseConvMode mode, stream_t stream) const
+    {
+        p_->mod_up(device_in, device_a, count, mode, stream);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::mod_down(const T* device_x, T* device_out, int stacks, stream_t stream) const
+    {
+        p_->mod_down(device_x, device_out, stacks, stream);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::decompose(const T* device_c_in, T* device_a, int count, bool input_ntt, void* scratch_device,
+                                     stream_t stream) const
+    {
+        p_->decompose(device_c_in, device_a, count, input_ntt, scratch_device, stream);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::switch_digits(const T* device_a, const T* device_key, T* device_out, int count,
+                                         int components, bool output_ntt, void* scratch_device, stream_t stream) const
+    {
+        p_->switch_digits(device_a, device_key, device_out, count, components, output_ntt, scratch_device, stream);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::apply(const T* device_c_in, const T* device_key, T* device_out, int count, int components,
+                                 bool input_ntt, bool output_ntt, void* scratch_device, stream_t stream) const
+    {
+        p_->need_transforms();
+        const KsScratch s = ks_scratch<T>(p_->L, p_->M, p_->D, p_->n, count, components);
+        if (scratch_device == nullptr)
+            throw std::invalid_argument("null pointer argument");
+        T* a = reinterpret_cast<T*>(static_cast<char*>(scratch_device) + s.a);
+        if (device_c_in != nullptr && device_out != nullptr && count > 0 &&
+            (ks_overlap(scratch_device, s.total, device_c_in, (static_cast<size_t>(count) << p_->n) * p_->L * sizeof(T)) ||
+             ks_overlap(scratch_device, s.total, device_out,
+                        (static_cast<size_t>(count) << p_->n) * p_->L * components * sizeof(T))))
+            throw std::invalid_argument("The scratch overlaps an operand!");
+        p_->decompose(device_c_in, a, count, input_ntt, scratch_device, stream);
+        p_->switch_digits(a, device_key, device_out, count, components, output_ntt, scratch_device, stream);
+    }
+
+    template <typename T> int KeySwitchPlan<T>::q_count() const { return p_->L; }
+    template <typename T> int KeySwitchPlan<T>::p_count() const { return p_->K; }
+    template <typename T> int KeySwitchPlan<T>::alpha() const { return p_->alpha; }
+    template <typename T> int KeySwitchPlan<T>::digits() const { return p_->D; }
+    template <typename T> int KeySwitchPlan<T>::n_power() const { return p_->n; }
+    template <typename T> bool KeySwitchPlan<T>::has_transforms() const { return static_cast<bool>(p_->ntt_full_f); }
+    template <typename T> bool KeySwitchPlan<T>::owns_workspace() const { return p_->owns; }
+    template <typename T> size_t KeySwitchPlan<T>::scratch_bytes(int count, int components) const
+    {
+        return ks_scratch<T>(p_->L, p_->M, p_->D, p_->n, count, components).total;
+    }
+
+    template <typename T>
+    void KeySwitchPlan<T>::constants(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* p_moduli_host,
+                                     int p_count, int alpha, const KeySwitchConstants<T>& out)
+    {
+        const KsHost h = ks_derive<T>(q_moduli_host, q_count, p_moduli_host, p_count, alpha);
+        for (const T* ptr : {out.up_qhat_inv, out.up_qhat_inv_shoup, out.up_matrix, out.up_q_mod, out.up_recip,
+                             out.up_bit_length, out.down_qhat_inv, out.down_qhat_inv_shoup, out.down_matrix,
+                             out.down_p_mod_q, out.down_p_inv_mod_q, out.down_recip, out.down_bit_length, out.pow_w,
+                             out.pow_w_shoup, out.pow_2w, out.pow_2w_shoup, out.one_shoup})
+            if (ptr == nullptr)
+                throw std::invalid_argument("null pointer argument");
+        const int M = h.M;
+        for (int d = 0; d < h.D; d++)
+        {
+            const host::BcHostConsts& u = h.up[d];
+            for (int i = h.lo(d); i < h.hi(d); i++)
+            {
+                const int li = i - h.lo(d);
+                out.up_qhat_inv[i] = static_cast<T>(u.w[li]), out.up_qhat_inv_shoup[i] = static_cast<T>(u.wp[li]);
+                out.up_recip[i] = static_cast<T>(u.recip[li]), out.up_bit_length[i] = static_cast<T>(u.blen[li]);
+            }
+            for (int m = 0; m < M; m++)
+            {
+                const bool own = m >= h.lo(d) && m < h.hi(d);
+                out.up_q_mod[static_cast<size_t>(d) * M + m] = own ? T(0) : static_cast<T>(u.qmod[ks_column(h, d, m)]);
+                for (int i = h.lo(d); i < h.hi(d); i++)
+                    out.up_matrix[static_cast<size_t>(i) * M + m] =
+                        own ? T(0)
+                            : static_cast<T>(u.matrix[static_cast<size_t>(i - h.lo(d)) * u.K + ks_column(h, d, m)]);
+            }
+        }
+        auto copy = [](const std::vector<std::uint64_t>& v, T* dst) {
+            for (size_t i = 0; i < v.size(); i++)
+                dst[i] = static_cast<T>(v[i]);
+        };
+        copy(h.down.w, out.down_qhat_inv), copy(h.down.wp, out.down_qhat_inv_shoup), copy(h.down.matrix, out.down_matrix);
+        copy(h.down.qmod, out.down_p_mod_q), copy(h.down.qinv, out.down_p_inv_mod_q), copy(h.down.recip, out.down_recip);
+        copy(h.down.blen, out.down_bit_length);
+        copy(h.t1, out.pow_w), copy(h.t1p, out.pow_w_shoup), copy(h.t2, out.pow_2w), copy(h.t2p, out.pow_2w_shoup);
+        copy(h.onep, out.one_shoup);
+    }
+
+    namespace
+    {
+        // base_conversion.cuh's formulas for one column: x[i] (any words) of the input base of `c` -> conv[j], every
+        // step reduced with %
+        template <typename T>
+        void ks_ref_convert(const host::BcHostConsts& c, const std::uint64_t* x, bool centred, std::uint64_t* conv)
+        {
+            constexpr int W = static_cast<int>(8 * sizeof(T));
+            std::uint64_t y[BASECONV_MAX_COUNT];
+            U128 zsum = static_cast<U128>(1) << (W - 1);
+            for (int i = 0; i < c.L; i++)
+            {
+                y[i] = static_cast<std::uint64_t>(static_cast<U128>(x[i] % c.q[i]) * c.w[i] % c.q[i]);
+                const int sh = static_cast<int>(c.blen[i]) - 1;
+                const U128 z = c.recip[i] != 0 ? (static_cast<U128>(y[i]) * c.recip[i]) >> sh
+                                               : static_cast<U128>(y[i]) << (W - sh);
+                zsum += static_cast<T>(z);
+            }
+            const std::uint64_t v = centred ? static_cast<std::uint64_t>(static_cast<T>(zsum >> W)) : 0;
+            for (int j = 0; j < c.K; j++)
+            {
+                const U128 p = c.p[j];
+                U128 s = static_cast<U128>(v % c.p[j]) * c.negq[j] % p;
+                for (int i = 0; i < c.L; i++)
+                    s = (s + static_cast<U128>(y[i] % c.p[j]) * c.matrix[static_cast<size_t>(i) * c.K + j]) % p;
+                conv[j] = static_cast<std::uint64_t>(s);
+            }
+        }
+    } // namespace
+
+    template <typename T>
+    void KeySwitchPlan<T>::reference_mod_up(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* p_moduli_host,
+                                            int p_count, int alpha, const T* in_host, T* a_host, int n_power, int count,
+                                            BaseConvMode mode)
+    {
+        const KsHost h = ks_derive<T>(q_moduli_host, q_count, p_moduli_host, p_count, alpha);
+        ks_check_mod_up<T>(h.L, h.M, h.D, in_host, a_host, n_power, count, mode);
+        const size_t n = size_t(1) << n_power;
+        const int L = h.L, M = h.M;
+        std::uint64_t x[BASECONV_MAX_COUNT], conv[BASECONV_MAX_COUNT];
+        for (int d = 0; d < h.D; d++)
+            for (int r = 0; r < count; r++)
+                for (size_t j = 0; j < n; j++)
+                {
+                    const T* src = in_host + static_cast<size_t>(r) * L * n + j;
+                    T* dst = a_host + (static_cast<size_t>(d) * count + r) * M * n + j;
+                    for (int i = h.lo(d); i < h.hi(d); i++)
+                        x[i - h.lo(d)] = src[i * n];
+                    ks_ref_convert<T>(h.up[d], x, mode == BaseConvMode::centred, conv);
+                    for (int m = 0; m < M; m++)
+                        dst[m * n] = (m >= h.lo(d) && m < h.hi(d)) ? static_cast<T>(src[m * n] % h.mod[m])
+                                                                   : static_cast<T>(conv[ks_column(h, d, m)]);
+                }
+    }
+
+    template <typename T>
+    void KeySwitchPlan<T>::reference_mod_down(const Modulus<T>* q_moduli_host, int q_count,
+                                              const Modulus<T>* p_moduli_host, int p_count, const T* x_host, T* out_host,
+                                              int n_power, int stacks)
+    {
+        const KsHost h = ks_derive<T>(q_moduli_host, q_count, p_moduli_host, p_count, 1, false); // {p} -> {q} only
+        ks_check_mod_down<T>(h.L, h.M, x_host, out_host, n_power, stacks);
+        const size_t n = size_t(1) << n_power;
+        const int L = h.L, K = h.K, M = h.M;
+        std::uint64_t x[BASECONV_MAX_COUNT], conv[BASECONV_MAX_COUNT];
+        for (int s = 0; s < stacks; s++)
+            for (size_t j = 0; j < n; j++)
+            {
+                const T* src = x_host + static_cast<size_t>(s) * M * n + j;
+                for (int k = 0; k < K; k++)
+                    x[k] = src[(L + k) * n];
+                ks_ref_convert<T>(h.down, x, true, conv);
+                for (int i = 0; i < L; i++)
+                {
+                    const std::uint64_t q = h.mod[i];
+                    const std::uint64_t c = src[i * n] % q;
+                    const std::uint64_t diff = c >= conv[i] ? c - conv[i] : c + (q - conv[i]);
+                    out_host[(static_cast<size_t>(s) * L + i) * n + j] =
+                        static_cast<T>(static_cast<U128>(diff) * h.down.qinv[i] % q);
+                }
+            }
+    }
+
+    template class KeySwitchPlan<Data32>;
+    template class KeySwitchPlan<Data64>;
+} // namespace gpuntt

@@ -630,6 +630,7 @@ namespace gpuntt
         // WorkspaceScope, and the outermost scope of a thread takes ONE snapshot of all of them: a call sees the same values
         // from its first decision to its last launch, whatever another thread sets meanwhile.
         void baseconv_set_ksplit(int v); // base_conversion.hip
+        void keyswitch_set_split(int v); // key_switch.hip
         namespace
         {
             struct OptionValues
@@ -708,6 +709,10 @@ namespace gpuntt
                     // snapshot below: a measurement knob of tools/bench_baseconv.py, read once per launch from a
                     // process-wide atomic; whatever it holds, the outputs are the same words
                     baseconv_set_ksplit(iv);
+                else if (test_hooks && k == "keyswitch_split" && is_num && lv >= 0 && lv <= 64)
+                    // key_switch.hip: workgroups per column tile of the multi-digit ModUp, 0 = its own choice; like
+                    // baseconv_ksplit a process-wide knob outside the per-call snapshot that never changes an output word
+                    keyswitch_set_split(iv);
                 else if (test_hooks && k == "reset_predictions" && bit)
                     g_reset_predictions.store(1, std::memory_order_relaxed); // rns_guess forgets every stack it has seen
                 else

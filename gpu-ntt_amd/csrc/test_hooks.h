@@ -10,6 +10,7 @@
  *                                bit 16: the full-tile contiguous pass of larger rings)
  *       two_sweep_big = 0 | 1    experiment: 64-bit rings 2^23 / 2^24 forward in two sweeps on 16384-coefficient tiles
  *       baseconv_ksplit = 0..16  base conversion: workgroups per column tile that share its outputs (0: the library's choice)
+ *       keyswitch_split = 0..64  key switching: workgroups per column tile that share the (digit, block) pairs of the ModUp
  *       reset_predictions = 1    the family prediction of the RNS overloads forgets every stack it has seen
  *   gpuntt_test_launch_log_start()      start recording the kernel of every launch the library enqueues (all threads)
  *   gpuntt_test_launch_log_take(buf, n) stop; the kernels since start, space-separated ("prep_twiddles merge_pass_lazy:31 ..."),

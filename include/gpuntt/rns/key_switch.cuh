@@ -1,0 +1,150 @@
+// gpuntt/rns/key_switch.cuh -- hybrid (RNS-digit) key switching (extension: no counterpart in the reference).
+//
+// The operation the three pieces before it were built for -- Galois automorphisms (ntt_merge/galois.cuh), fast base
+// conversion (rns/base_conversion.cuh) and the RNS inner product (rns/inner_product.cuh) -- as ONE plan that owns the
+// constants, the digit partition and the sequence.  All integers, W = 8 * sizeof(T).
+//
+// Bases.  q-primes q_0 .. q_{L-1}, special primes p_0 .. p_{K-1}; the FULL base is {q_0 .. q_{L-1}, p_0 .. p_{K-1}} in
+// that order, M = L + K limbs, modulus m of the full base is q_m for m < L and p_{m-L} otherwise.  A digit size
+// alpha >= 1 cuts the q-base into D = ceil(L / alpha) digits: digit d owns the limbs S_d = [d alpha, min((d+1) alpha, L))
+// (the last digit may be shorter), Q_d = prod_{i in S_d} q_i, P = prod_k p_k.
+//
+//   mod_up(in, a, count, mode):  in = T[count][L][N] (coefficient form), a = T[D][count][M][N] -- the digit-major
+//     layout InnerProductPlan reads.  For every d < D, r < count, m < M:
+//       m in S_d:   a[d][r][m] = in[r][m] mod q_m                 canonical; ANY input word is accepted
+//       otherwise:  a[d][r][m] = WORD FOR WORD what BaseConvPlan gives for the input base {q_i : i in S_d} (in that
+//                   order), an output base that contains modulus m and the same BaseConvMode, on the limbs in[r][i],
+//                   i in S_d.  The formulas of base_conversion.cuh ARE the definition (y_i, approximate / centred, R_i,
+//                   b_i, v); nothing is restated here
+//     ONE kernel launch for all digits: every input word is read from memory once, every word of a is written once --
+//     unless count * N is too small to fill the part: then the (digit, output block) pairs of a column tile are split
+//     over up to 8 workgroups, each of which re-reads the tile's input (the threshold is an estimate).
+//     `in` must not overlap `a`
+//   mod_down(x, out, stacks):  x = T[stacks][M][N] (coefficient form, full base), out = T[stacks][L][N]:
+//       out[s][j] = what BaseConvPlan({p_k} -> {q_j})::convert_and_divide gives in centred mode with in = limbs
+//                   L .. M-1 of stack s and c = limbs 0 .. L-1 of stack s: round(x / P) in the base q outside that
+//                   header's rounding band
+//     ONE kernel launch for all stacks, the special limbs read in place.  out must NOT overlap x: stacks of x are M N
+//     words apart and those of out L N, so out[s] lies over limbs of earlier stacks that other workgroups may not have
+//     read yet -- in-place operation cannot be made safe without a second pass and is refused
+//   decompose(c_in, a, count, input_ntt, scratch):
+//       [input_ntt: INTT over the count * L polynomials of c_in (q-base) into scratch]  mod_up (centred)  forward NTT in
+//       place over the D * count * M polynomials of a
+//   switch_digits(a, key, out, count, components, output_ntt, scratch):
+//       InnerProductPlan::multiply_accumulate(a, key) with D digits, C = components, accumulate = false and the plan's
+//       key_mod_count / key_limbs into scratch T[C][count][M][N]; INTT over C * count * M; mod_down into
+//       out = T[C][count][L][N]; [output_ntt: forward NTT over C * count * L in place]
+//   apply(c_in, key, out, count, components, input_ntt, output_ntt, scratch) = decompose, then switch_digits, a in scratch
+//     The split is there to hoist: decompose once, permute a with GPU_Automorphism_NTT, switch_digits once per rotation key.
+//     key = T[D_key][C][key_mod_count][N] in NTT form, exactly InnerProductPlan's.
+//
+//   * ranges: 1 <= L, 1 <= K, M = L + K <= 64, alpha >= 1, 1 <= components <= 4, count >= 0 and stacks >= 0 (0: nothing
+//     happens), n_power in [1, 28], M <= key_mod_count <= 256.  A plan is built for ONE level (one L) and one ring; a
+//     caller at a lower level builds another plan and points it at the full-level key through key_mod_count /
+//     key_limbs_host (limb of the key for every modulus of THIS plan's full base; nullptr: limb m)
+//   * transforms: the plan builds four NTTPlan<T> (forward and inverse over the full base, inverse and forward over the
+//     q-base) from ONE caller table pair -- forward_table_device / inverse_table_device as for GPU_NTT / GPU_INTT, slot i
+//     at i << n_power in full-base order, so the q-base is the first L slots -- plus the M host n^-1 values, the
+//     reduction polynomial and a batch_hint.  The tables must outlive the plan (NTTPlan).  Both table pointers nullptr: a
+//     plan without transforms -- mod_up and mod_down work for any moduli Modulus<T> accepts (not necessarily prime), the
+//     pipeline methods throw
+//   * workspace: every constant and every NTTPlan lives in workspace_bytes(L, K, alpha, n_power) bytes of device memory
+//     (nullptr = the plan allocates and owns it; owns_workspace()).  The constructor waits for `stream`: once for its own
+//     constants and once in each plan it builds (the inner product's and the four NTTPlans) -- up to six host waits per
+//     plan, none afterwards
+//   * scratch: scratch_bytes(L, K, alpha, n_power, count, components) bytes owned by the CALLER, 256-byte aligned; the
+//     pipeline methods allocate nothing and never synchronise, so apply can be captured on one stream as it is.
+//     mod_up and mod_down allocate nothing, never synchronise and launch exactly one kernel
+//   * std::invalid_argument: the moduli of the full base are not pairwise coprime, a modulus is not the Modulus<T> of its
+//     value ("Invalid modulus!"), n_power outside [1, 28] ("Invalid n_power range!"), a count outside the ranges above,
+//     alpha < 1, a null pointer, buffers that overlap where the contract forbids it, a pipeline call on a plan
+//     without transforms
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#include "gpuntt/common/common.cuh"
+#include "gpuntt/common/modular_arith.cuh"
+#include "gpuntt/common/nttparameters.cuh"
+#include "gpuntt/rns/base_conversion.cuh"
+#include "gpuntt/rns/inner_product.cuh"
+
+namespace gpuntt
+{
+    // The plan's constants as the host derived them (KeySwitchPlan::constants, gpuntt_keyswitch_constants_*): every
+    // pointer is a caller array of the stated length.  d(i) = i / alpha is the digit of q-limb i.
+    template <typename T> struct KeySwitchConstants
+    {
+        // ModUp, per digit: BaseConvPlan::constants({q_i : i in S_d} -> the other M - |S_d| moduli in full-base order)
+        T* up_qhat_inv;       // [L]    (Q_d(i) / q_i)^-1 mod q_i
+        T* up_qhat_inv_shoup; // [L]    its Shoup companion
+        T* up_matrix;         // [L][M] (Q_d(i) / q_i) mod modulus m; 0 where m is in S_d(i) (never used)
+        T* up_q_mod;          // [D][M] Q_d mod modulus m (0 where m is in S_d)
+        T* up_recip;          // [L]    R_i mod 2^W
+        T* up_bit_length;     // [L]    b_i
+        // ModDown: BaseConvPlan::constants({p_k} -> {q_j})
+        T* down_qhat_inv;       // [K]
+        T* down_qhat_inv_shoup; // [K]
+        T* down_matrix;         // [K][L]
+        T* down_p_mod_q;        // [L] P mod q_j
+        T* down_p_inv_mod_q;    // [L] P^-1 mod q_j
+        T* down_recip;          // [K]
+        T* down_bit_length;     // [K]
+        // the folding constants of the final reductions, per modulus of the full base: InnerProductPlan::constants
+        T* pow_w;        // [M]
+        T* pow_w_shoup;  // [M]
+        T* pow_2w;       // [M]
+        T* pow_2w_shoup; // [M]
+        T* one_shoup;    // [M]
+    };
+
+    template <typename T> class KeySwitchPlan
+    {
+      public:
+        static size_t workspace_bytes(int q_count, int p_count, int alpha, int n_power);
+        static size_t scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count, int components);
+        static int digits(int q_count, int alpha); // D
+
+        KeySwitchPlan(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* p_moduli_host, int p_count,
+                      int alpha, int n_power, const Root<T>* forward_table_device, const Root<T>* inverse_table_device,
+                      const Ninverse<T>* mod_inverse_host, ReductionPolynomial reduction_poly, int batch_hint,
+                      int key_mod_count, const int* key_limbs_host, stream_t stream, void* workspace_device = nullptr);
+        ~KeySwitchPlan();
+        KeySwitchPlan(const KeySwitchPlan&) = delete;
+        KeySwitchPlan& operator=(const KeySwitchPlan&) = delete;
+
+        void mod_up(const T* device_in, T* device_a, int count, BaseConvMode mode, stream_t stream) const;
+        void mod_down(const T* device_x, T* device_out, int stacks, stream_t stream) const;
+        void decompose(const T* device_c_in, T* device_a, int count, bool input_ntt, void* scratch_device,
+                       stream_t stream) const;
+        void switch_digits(const T* device_a, const T* device_key, T* device_out, int count, int components,
+                           bool output_ntt, void* scratch_device, stream_t stream) const;
+        void apply(const T* device_c_in, const T* device_key, T* device_out, int count, int components, bool input_ntt,
+                   bool output_ntt, void* scratch_device, stream_t stream) const;
+
+        int q_count() const;
+        int p_count() const;
+        int alpha() const;
+        int digits() const;
+        int n_power() const;
+        bool has_transforms() const;
+        bool owns_workspace() const; // false: the plan lives in the caller's workspace and has allocated nothing
+        size_t scratch_bytes(int count, int components) const;
+
+        // host only (no GPU): the constants of these bases, with the checks of the constructor
+        static void constants(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* p_moduli_host, int p_count,
+                              int alpha, const KeySwitchConstants<T>& out);
+        // host only (no GPU): mod_up / mod_down on HOST arrays, with unsigned __int128 and %, after the same argument
+        // checks.  What tests and examples compare the kernels with; never a GPU fall-back
+        static void reference_mod_up(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* p_moduli_host,
+                                     int p_count, int alpha, const T* in_host, T* a_host, int n_power, int count,
+                                     BaseConvMode mode);
+        static void reference_mod_down(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* p_moduli_host,
+                                       int p_count, const T* x_host, T* out_host, int n_power, int stacks);
+
+      private:
+        struct Impl;
+        Impl* p_;
+    };
+} // namespace gpuntt

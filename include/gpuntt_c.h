@@ -32,6 +32,9 @@
  *                               ModDown and rescale from one prepared plan, one kernel launch per call
  *   gpuntt_innerprod_*          extension RNS inner product (include/gpuntt/rns/inner_product.cuh): the key-switching
  *                               multiply-accumulate over digits and key components, one kernel launch per call
+ *   gpuntt_keyswitch_*          extension hybrid key switching (include/gpuntt/rns/key_switch.cuh): one plan for the
+ *                               digit partition, ModUp of all digits in one launch, the inner product, the transforms
+ *                               and ModDown in place inside the stacks; host-only constants and references
  *   gpuntt_operator_gpu_*       diagnostic: the public device class OPERATOR_GPU<T>
  *                               (src/include/gpuntt/common/modular_arith.cuh:174-454) applied elementwise
  *
@@ -355,6 +358,90 @@ extern "C"
                                        const uint64_t* key_host, uint64_t* out_host, int n_power, int digits,
                                        int components, int count, int accumulate, int key_mod_count,
                                        const int* key_limbs_host);
+
+    /* ---- extension: hybrid key switching (KeySwitchPlan<T>, include/gpuntt/rns/key_switch.cuh) --------------------
+     * q_moduli_host[q_count] (q_0 .. q_{L-1}) and p_moduli_host[p_count] (the special primes p_0 .. p_{K-1}) are HOST
+     * arrays, pairwise coprime over the full base {q, p}, M = L + K <= 64; alpha >= 1 is the digit size, D = ceil(L /
+     * alpha).  forward_table / inverse_table: DEVICE tables as for gpuntt_ntt_rns_* / gpuntt_intt_rns_*, slot i at
+     * i << n_power in full-base order (both NULL: a plan without transforms -- mod_up and mod_down only);
+     * mod_inverse_host[M]: n^-1 per modulus.  key_mod_count / key_limbs_host (M ints or NULL) as for
+     * gpuntt_innerprod_plan_execute_*.  workspace_device: gpuntt_keyswitch_plan_workspace_bytes_*() bytes owned by the
+     * caller, or NULL (the plan allocates).  scratch: gpuntt_keyswitch_plan_scratch_bytes_*() bytes of DEVICE memory
+     * owned by the caller, 256-byte aligned (decompose reads it only with input_ntt).
+     *   mod_up         in T[count][L][N] -> a T[D][count][M][N]; mode as for gpuntt_baseconv_plan_convert_*; one launch
+     *   mod_down       x T[stacks][M][N] -> out T[stacks][L][N] (centred, divided by P); one launch; out must not overlap x
+     *   decompose      [INTT of c_in] mod_up (centred), forward NTT of a
+     *   switch_digits  inner product of a and key (T[D_key][components][key_mod_count][N]), INTT, mod_down into
+     *                  out T[components][count][L][N], [forward NTT of out]
+     *   apply          decompose into the scratch, then switch_digits
+     * No call allocates or synchronises.
+     * host only (no GPU): constants -- arrays_host holds 18 caller arrays in the order of KeySwitchConstants<T>
+     * (up_qhat_inv[L], up_qhat_inv_shoup[L], up_matrix[L][M], up_q_mod[D][M], up_recip[L], up_bit_length[L],
+     * down_qhat_inv[K], down_qhat_inv_shoup[K], down_matrix[K][L], down_p_mod_q[L], down_p_inv_mod_q[L], down_recip[K],
+     * down_bit_length[K], pow_w[M], pow_w_shoup[M], pow_2w[M], pow_2w_shoup[M], one_shoup[M]); reference_mod_up /
+     * reference_mod_down -- what mod_up / mod_down compute, on HOST arrays in exact integers after the same argument
+     * checks: the value tests and examples compare the kernels with, never a fall-back */
+    typedef struct gpuntt_keyswitch_plan gpuntt_keyswitch_plan;
+    int gpuntt_keyswitch_plan_workspace_bytes_u32(int q_count, int p_count, int alpha, int n_power, uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_scratch_bytes_u32(int q_count, int p_count, int alpha, int n_power, int count,
+                                                int components, uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_create_u32(gpuntt_keyswitch_plan** plan_host, const gpuntt_modulus32* q_moduli_host, int q_count,
+                                         const gpuntt_modulus32* p_moduli_host, int p_count, int alpha, int n_power,
+                                         const uint32_t* forward_table, const uint32_t* inverse_table,
+                                         const uint32_t* mod_inverse_host, int reduction_poly, int batch_hint,
+                                         int key_mod_count, const int* key_limbs_host, void* workspace_device,
+                                         void* stream);
+    int gpuntt_keyswitch_plan_mod_up_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* in, uint32_t* a, int count, int mode,
+                                         void* stream);
+    int gpuntt_keyswitch_plan_mod_down_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* x, uint32_t* out, int stacks,
+                                           void* stream);
+    int gpuntt_keyswitch_plan_decompose_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* c_in, uint32_t* a, int count,
+                                            int input_ntt, void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_switch_digits_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* a, const uint32_t* key,
+                                                uint32_t* out, int count, int components, int output_ntt, void* scratch,
+                                                void* stream);
+    int gpuntt_keyswitch_plan_apply_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* c_in, const uint32_t* key, uint32_t* out,
+                                        int count, int components, int input_ntt, int output_ntt, void* scratch,
+                                        void* stream);
+    int gpuntt_keyswitch_plan_owns_workspace_u32(const gpuntt_keyswitch_plan* plan); /* 1 / 0, negative on error */
+    int gpuntt_keyswitch_plan_destroy_u32(gpuntt_keyswitch_plan* plan);
+    int gpuntt_keyswitch_constants_u32(const gpuntt_modulus32* q_moduli_host, int q_count, const gpuntt_modulus32* p_moduli_host, int p_count,
+                                       int alpha, uint32_t* const* arrays_host);
+    int gpuntt_keyswitch_reference_mod_up_u32(const gpuntt_modulus32* q_moduli_host, int q_count, const gpuntt_modulus32* p_moduli_host,
+                                              int p_count, int alpha, const uint32_t* in_host, uint32_t* a_host, int n_power,
+                                              int count, int mode);
+    int gpuntt_keyswitch_reference_mod_down_u32(const gpuntt_modulus32* q_moduli_host, int q_count, const gpuntt_modulus32* p_moduli_host,
+                                                int p_count, const uint32_t* x_host, uint32_t* out_host, int n_power, int stacks);
+    int gpuntt_keyswitch_plan_workspace_bytes_u64(int q_count, int p_count, int alpha, int n_power, uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_scratch_bytes_u64(int q_count, int p_count, int alpha, int n_power, int count,
+                                                int components, uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_create_u64(gpuntt_keyswitch_plan** plan_host, const gpuntt_modulus64* q_moduli_host, int q_count,
+                                         const gpuntt_modulus64* p_moduli_host, int p_count, int alpha, int n_power,
+                                         const uint64_t* forward_table, const uint64_t* inverse_table,
+                                         const uint64_t* mod_inverse_host, int reduction_poly, int batch_hint,
+                                         int key_mod_count, const int* key_limbs_host, void* workspace_device,
+                                         void* stream);
+    int gpuntt_keyswitch_plan_mod_up_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* in, uint64_t* a, int count, int mode,
+                                         void* stream);
+    int gpuntt_keyswitch_plan_mod_down_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* x, uint64_t* out, int stacks,
+                                           void* stream);
+    int gpuntt_keyswitch_plan_decompose_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* c_in, uint64_t* a, int count,
+                                            int input_ntt, void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_switch_digits_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* a, const uint64_t* key,
+                                                uint64_t* out, int count, int components, int output_ntt, void* scratch,
+                                                void* stream);
+    int gpuntt_keyswitch_plan_apply_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* c_in, const uint64_t* key, uint64_t* out,
+                                        int count, int components, int input_ntt, int output_ntt, void* scratch,
+                                        void* stream);
+    int gpuntt_keyswitch_plan_owns_workspace_u64(const gpuntt_keyswitch_plan* plan); /* 1 / 0, negative on error */
+    int gpuntt_keyswitch_plan_destroy_u64(gpuntt_keyswitch_plan* plan);
+    int gpuntt_keyswitch_constants_u64(const gpuntt_modulus64* q_moduli_host, int q_count, const gpuntt_modulus64* p_moduli_host, int p_count,
+                                       int alpha, uint64_t* const* arrays_host);
+    int gpuntt_keyswitch_reference_mod_up_u64(const gpuntt_modulus64* q_moduli_host, int q_count, const gpuntt_modulus64* p_moduli_host,
+                                              int p_count, int alpha, const uint64_t* in_host, uint64_t* a_host, int n_power,
+                                              int count, int mode);
+    int gpuntt_keyswitch_reference_mod_down_u64(const gpuntt_modulus64* q_moduli_host, int q_count, const gpuntt_modulus64* p_moduli_host,
+                                                int p_count, const uint64_t* x_host, uint64_t* out_host, int n_power, int stacks);
 
     /* ---- extension: prepared 4-step transforms (FourStepPlan<T>, include/gpuntt/ntt_4step/ntt_4step.cuh) ----
      * The Shoup pairs of the n1 / n2 / W tables are derived once, at creation, into workspace_device
