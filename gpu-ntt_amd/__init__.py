@@ -12,8 +12,8 @@ src/include/gpuntt/ntt_4step/ntt_4step.cuh:46-49,278-308):
     BaseConvPlan / baseconv_constants (extension: RNS fast base conversion, gpuntt/rns/base_conversion.cuh)
     InnerProductPlan / innerprod_constants / innerprod_reference (extension: RNS inner product,
     gpuntt/rns/inner_product.cuh)
-    KeySwitchPlan / keyswitch_constants / keyswitch_scratch_bytes / keyswitch_reference_mod_up /
-    keyswitch_reference_mod_down (extension: hybrid
+    KeySwitchPlan / keyswitch_constants / keyswitch_scratch_bytes / keyswitch_hoisted_scratch_bytes /
+    keyswitch_reference_mod_up / keyswitch_reference_mod_down (extension: hybrid
     key switching, gpuntt/rns/key_switch.cuh)
     Modulus, ntt_configuration, ntt_rns_configuration, ntt4step_configuration,
     ntt4step_rns_configuration, NTTParameters, NTTParameters4Step
@@ -112,7 +112,8 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "innerprod_reference",
               "keyswitch_plan_workspace_bytes", "keyswitch_plan_scratch_bytes", "keyswitch_plan_create",
               "keyswitch_plan_mod_up", "keyswitch_plan_mod_down", "keyswitch_plan_decompose",
-              "keyswitch_plan_switch_digits", "keyswitch_plan_apply", "keyswitch_plan_owns_workspace",
+              "keyswitch_plan_switch_digits", "keyswitch_plan_apply", "keyswitch_plan_hoisted_scratch_bytes",
+              "keyswitch_plan_rotate_hoisted", "keyswitch_plan_owns_workspace",
               "keyswitch_plan_destroy", "keyswitch_constants", "keyswitch_reference_mod_up",
               "keyswitch_reference_mod_down")
     for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option", "gpuntt_galois_element_u32",
@@ -125,7 +126,7 @@ ENV_OPTIONS = {"GPUNTT_PATH": ("path", None), "GPUNTT_U32_E32": ("u32_e32", lamb
 
 
 TEST_HOOKS = {"no_scratch", "rns_force_fallback", "u32_e32", "reset_predictions", "two_sweep_big", "baseconv_ksplit",
-              "keyswitch_split"}
+              "keyswitch_split", "keyswitch_hoist_chunk"}
 TEST_PATHS = {"fast-strict", "generic-capped"}
 
 
@@ -875,6 +876,24 @@ def keyswitch_scratch_bytes(q_count, p_count, alpha, n_power, count, components=
     return int(out.value)
 
 
+def keyswitch_hoisted_scratch_bytes(q_count, p_count, alpha, n_power, count, elements, bits=64):
+    """KeySwitchPlan<T>::hoisted_scratch_bytes (host only): the caller-owned scratch of rotate_hoisted, in bytes -- the
+    accumulators T[elements][2][count][M][N], rounded up to 256"""
+    out = ctypes.c_uint64()
+    _check(getattr(load_library(), "gpuntt_keyswitch_plan_hoisted_scratch_bytes_u%d" % bits)(
+        int(q_count), int(p_count), int(alpha), int(n_power), int(count), int(elements), ctypes.byref(out)))
+    return int(out.value)
+
+
+def keyswitch_hoist_chunk(bits, digits, n_power):
+    """test hook read-back (csrc/test_hooks.h, host only): log2 of the source chunk inner_product_galois takes for this
+    word width, digit count and ring under the current value of the hook keyswitch_hoist_chunk"""
+    lc = load_library().gpuntt_test_keyswitch_hoist_chunk(int(bits) // 8, int(digits), int(n_power))
+    if lc < 0:
+        raise ValueError("Invalid argument!")
+    return lc
+
+
 def keyswitch_constants(q_moduli, p_moduli, alpha, bits=64):
     """Host (no GPU): the constants a KeySwitchPlan of these bases uploads (KeySwitchConstants<T>), as a dict of numpy
     arrays -- per digit the ModUp constants up_qhat_inv[L], up_qhat_inv_shoup[L], up_matrix[L][M], up_q_mod[D][M],
@@ -1076,6 +1095,39 @@ class KeySwitchPlan:
         fn = getattr(load_library(), "gpuntt_keyswitch_plan_apply_u%d" % self.bits)
         _check(fn(self._h, _ptr(device_c_in), _ptr(device_key), _ptr(device_out), int(count), int(components),
                   int(bool(input_ntt)), int(bool(output_ntt)), _ptr(scratch), _stream(stream)))
+
+    def hoisted_scratch_bytes(self, count, elements):
+        return keyswitch_hoisted_scratch_bytes(self.q_count, self.p_count, self.alpha, self.n_power, count, elements,
+                                               self.bits)
+
+    def rotate_hoisted(self, a, c0, keys, elements, out, count, output_ntt=False, scratch=None, stream=None):
+        """G = len(elements) Galois automorphisms of one decomposition, each with its own key: a T[D][count][M][N] (what
+        decompose writes), c0 T[count][L][N] in NTT form or None, keys a list of G device tensors (each at least
+        D x 2 x key_mod_count x N words), elements a list of G odd ints, out T[G][2][count][L][N]; scratch: a device
+        tensor of at least hoisted_scratch_bytes(count, G) bytes, 256-byte aligned.  out[g] equals
+        GPU_Automorphism_NTT + switch_digits + the rotated c0, word for word (key_switch.cuh)."""
+        keys, elements = list(keys), [int(k) for k in elements]
+        G, cols = len(elements), self._cols(count)
+        if len(keys) != G:
+            raise ValueError("rotate_hoisted takes one key per Galois element")
+        if not 1 <= G <= 64:
+            raise ValueError("Invalid galois_count!")
+        if a is None or out is None or scratch is None or any(k is None for k in keys):
+            raise ValueError("null pointer argument")
+        sized = [(a, cols * self.mod_count * self.digits, "a (D x count x M x N)"),
+                 (out, cols * self.q_count * 2 * G, "out (G x 2 x count x L x N)")]
+        if c0 is not None:
+            sized.append((c0, cols * self.q_count, "c0 (count x L x N)"))
+        sized += [(k, self._key_words(2) if cols else 0, "key (D x 2 x key_mod_count x N)") for k in keys]
+        self._check_buffers(sized)
+        _require_gpu(scratch)
+        if int(count) >= 0 and scratch.numel() * scratch.element_size() < self.hoisted_scratch_bytes(count, G):
+            raise ValueError("scratch holds fewer than hoisted_scratch_bytes(count, elements) bytes")
+        key_ptrs = (ctypes.c_void_p * G)(*[k.data_ptr() for k in keys])
+        elts = (ctypes.c_uint32 * G)(*[k & 0xFFFFFFFF for k in elements])
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_rotate_hoisted_u%d" % self.bits)
+        _check(fn(self._h, _ptr(a), _ptr(c0), key_ptrs, elts, G, _ptr(out), int(count), int(bool(output_ntt)),
+                  _ptr(scratch), _stream(stream)))
 
     def close(self):
         if self._h:

@@ -1,0 +1,45 @@
+// hoisted_rotation_internal.hpp -- what key_switch.hip needs of hoisted_rotation.hip: the kernel arguments of one
+// rotate_hoisted call and the launcher of inner_product_galois.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "gpuntt/ntt_merge/galois.cuh"
+#include "gpuntt/rns/inner_product.cuh"
+
+namespace gpuntt
+{
+    namespace kern
+    {
+        // Everything of a call that is not a buffer travels as ONE kernel argument (as GaloisArgs and IpLimbs do): no
+        // device copy, nothing a captured graph has to keep alive.  2.1 KiB for u64, inside the 4 KiB argument segment.
+        template <typename T> struct HoistArgs
+        {
+            const T* key[GALOIS_MAX_COUNT];          // key_g: T[D_key][2][key_mod_count][N]
+            T p_mod_q[INNERPROD_MAX_MODULI];         // P mod q_m, m < L ...
+            T p_mod_q_shoup[INNERPROD_MAX_MODULI];   // ... and floor((P mod q_m) 2^W / q_m)
+            std::uint32_t elt[GALOIS_MAX_COUNT];     // k_g, reduced
+            std::uint32_t inv[GALOIS_MAX_COUNT];     // k_g^-1, same modulus
+            unsigned char limb[INNERPROD_MAX_MODULI]; // the key limb of every modulus of the full base
+            int count;                               // G
+        };
+    } // namespace kern
+
+    namespace host
+    {
+        // log2 of the chunk of inner_product_galois for words of `word_bytes`, D digits and a ring of 2^n_power: the
+        // largest power of two with (D + 1) chunk word_bytes inside the LDS budget, at least 64 slots, at most N; the
+        // test hook keyswitch_hoist_chunk replaces the budget rule (not the cap at N)
+        int hoist_chunk_log(size_t word_bytes, int D, int n_power);
+        void keyswitch_set_hoist_chunk(int v); // test hook: 0 = the rule above, 6 .. 13 = log2 of the chunk
+
+        // a: T[D][count][M][N], c0: T[count][L][N] or nullptr, acc: T[G][2][count][M][N]; consts: the workspace image of
+        // InnerProductPlan for the M moduli.  One launch; throws std::invalid_argument beyond the grid limits
+        template <typename T>
+        void hoist_launch(const T* a, const T* c0, T* acc, const T* consts, const kern::HoistArgs<T>& args, int D,
+                          int count, int L, int M, int KM, int n_power, bool negacyclic, hipStream_t stream);
+    } // namespace host
+} // namespace gpuntt

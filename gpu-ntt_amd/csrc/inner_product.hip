@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "gpuntt/rns/inner_product.cuh"
+#include "inner_product_internal.hpp"
 #include "launch.hpp"
 
 namespace gpuntt
@@ -28,59 +29,11 @@ namespace gpuntt
     {
         constexpr int IP_NT = 256; // lanes per workgroup at most (a ring narrower than that gets a narrower workgroup)
 
-        // the key limb of every modulus, as a kernel argument: read at blockIdx.y, a scalar load
-        struct IpLimbs
-        {
-            unsigned char v[INNERPROD_MAX_MODULI];
-        };
-
         // inputs per pass over the key, at most: RB * C * V accumulators of 5 (u64) or 3 (u32) registers are live, and
         // 8 (r, c) pairs are what the register file holds at 3 waves per SIMD for u64
         constexpr int ip_block(int C) { return C <= 2 ? 4 : 2; }
 
-        template <typename T> struct IpWide;
-        template <> struct IpWide<Data32>
-        {
-            using type = Data64;
-        };
-        template <> struct IpWide<Data64>
-        {
-            using type = unsigned __int128;
-        };
-
-        __device__ __forceinline__ Data32 ip_mulhi(Data32 a, Data32 b) { return __umulhi(a, b); }
-        __device__ __forceinline__ Data64 ip_mulhi(Data64 a, Data64 b) { return __umul64hi(a, b); }
-        __device__ __forceinline__ Data32 ip_addc(Data32 a, Data32 b, Data32 cin, Data32* cout)
-        {
-            return __builtin_addc(a, b, cin, cout);
-        }
-        __device__ __forceinline__ Data64 ip_addc(Data64 a, Data64 b, Data64 cin, Data64* cout)
-        {
-            return __builtin_addcl(a, b, cin, cout);
-        }
-
-        // (x * w) mod m, canonical, for ANY word x, w < m < 2^(W-1) and wp = floor(w 2^W / m) (base_conversion.hip)
-        template <typename T> __device__ __forceinline__ T ip_shoup(T x, T w, T wp, T m)
-        {
-            const T r = x * w - ip_mulhi(x, wp) * m;
-            return r >= m ? r - m : r;
-        }
-
-        template <typename T> struct IpAcc
-        {
-            T lo, hi;
-            unsigned carry;
-            // += x * y, exact
-            __device__ __forceinline__ void mac(T x, T y)
-            {
-                using W2 = typename IpWide<T>::type;
-                const W2 p = static_cast<W2>(x) * y;
-                T k0, k1;
-                lo = ip_addc(lo, static_cast<T>(p), T(0), &k0);
-                hi = ip_addc(hi, static_cast<T>(p >> (8 * sizeof(T))), k0, &k1);
-                carry += static_cast<unsigned>(k1);
-            }
-        };
+        // IpLimbs, IpWide, ip_mulhi, ip_addc, ip_shoup, IpAcc, IpFold: inner_product_internal.hpp
 
         // the plan's constants in the workspace: six arrays of M words (q, 2^W mod q and its Shoup companion, 2^2W mod q
         // and its companion, the companion of 1), read through the CONSTANT address space -- nothing writes the workspace
@@ -91,7 +44,6 @@ namespace gpuntt
                                                                IpLimbs limbs, int D, int count, int M, int KM,
                                                                int n_power, unsigned tiles, int accumulate)
         {
-            using CP = const T __attribute__((address_space(4)))*;
             struct alignas(V * sizeof(T)) Vec
             {
                 T x[V];
@@ -155,9 +107,7 @@ namespace gpuntt
                 pk += key_digit;
             }
 
-            const CP k = (CP) (consts);
-            const T q = k[m], t1 = k[M + m], t1p = k[2 * M + m], t2 = k[3 * M + m], t2p = k[4 * M + m],
-                    onep = k[5 * M + m];
+            const IpFold<T> fold(consts, M, m);
 #pragma unroll
             for (int r = 0; r < RB; r++)
                 if (r < nr)
@@ -169,13 +119,7 @@ namespace gpuntt
 #pragma unroll
                         for (int v = 0; v < V; v++)
                         {
-                            const IpAcc<T>& s = acc[r][c][v];
-                            T x = ip_shoup<T>(s.hi, t1, t1p, q);
-                            x += ip_shoup<T>(static_cast<T>(s.carry), t2, t2p, q);
-                            x += ip_shoup<T>(s.lo, T(1), onep, q); // x < 3 q < 2^W
-                            x = x >= q ? x - q : x;
-                            x = x >= q ? x - q : x;
-                            o.x[v] = x;
+                            o.x[v] = fold.reduce(fold.sum(acc[r][c][v])); // the sum is below 3 q < 2^W
                         }
                         *reinterpret_cast<Vec*>(po + c * a_digit + r * stack) = o;
                     }

@@ -20,17 +20,23 @@
 // constants image (bc_image) -- with the stack strides of the full base: the special limbs and the q-limbs are read where
 // the inner product left them, inside the M-limb stacks.  The strides are a compile-time form of the kernel, so the dense
 // instantiations behind BaseConvPlan keep their registers.
+//
+// rotate_hoisted: inner_product_galois of hoisted_rotation.hip (the inner product that permutes while it multiplies, all
+// G elements in one launch), then the plan's own full-base INTT, mod_down and q-base NTT over G * 2 * count stacks
+// (DESIGN.md 3.13).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
 #include <memory>
 #include <stdexcept>
+#include <utility>
 #include <vector>
 
 #include "base_conversion_internal.hpp"
 #include "gpuntt/ntt_merge/ntt.cuh"
 #include "gpuntt/rns/key_switch.cuh"
+#include "hoisted_rotation_internal.hpp"
 #include "launch.hpp"
 
 namespace gpuntt
@@ -424,12 +430,24 @@ namespace gpuntt
             s.total = s.inner_out + ks_align(poly * M * components);
             return s;
         }
+
+        // the scratch of rotate_hoisted, in bytes: the accumulators T[G][2][count][M][N]
+        template <typename T> size_t ks_hoisted_scratch(int M, int n_power, int count, int elements)
+        {
+            if (count < 0)
+                throw std::invalid_argument("Invalid count!");
+            if (elements < 1 || elements > GALOIS_MAX_COUNT)
+                throw std::invalid_argument("Invalid galois_count!");
+            return ks_align((static_cast<size_t>(count) << n_power) * sizeof(T) * M * 2 * elements);
+        }
     } // namespace
 
     template <typename T> struct KeySwitchPlan<T>::Impl
     {
         int L = 0, K = 0, M = 0, alpha = 0, D = 0, n = 0, KM = 0;
+        bool negacyclic = true;
         std::vector<int> limbs;
+        std::vector<T> p_mod_q, p_mod_q_shoup; // [L] P mod q_j and its Shoup companion: the c0 term of rotate_hoisted
         char* ws = nullptr;
         bool owns = false;
         KsLayout lay{};
@@ -537,6 +555,65 @@ namespace gpuntt
             if (output_ntt)
                 ntt_q_f->execute(out, out, C * count * L, stream);
         }
+
+        void rotate_hoisted(const T* a, const T* c0, const T* const* keys, const std::uint32_t* elts, int G, T* out,
+                            int count, bool output_ntt, void* scratch, hipStream_t stream) const
+        {
+            need_transforms();
+            const size_t acc_bytes = ks_hoisted_scratch<T>(M, n, count, G); // checks count and G
+            if (a == nullptr || keys == nullptr || elts == nullptr || out == nullptr || scratch == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
+                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            kern::HoistArgs<T> args{};
+            args.count = G;
+            const std::uint32_t mask = negacyclic ? (2u << n) - 1u : (1u << n) - 1u; // as GPU_Automorphism_NTT reduces
+            for (int g = 0; g < G; g++)
+            {
+                const std::uint32_t k = elts[g] & mask;
+                if ((k & 1u) == 0u)
+                    throw std::invalid_argument("Invalid Galois element (must be odd)!");
+                if (keys[g] == nullptr)
+                    throw std::invalid_argument("null pointer argument");
+                args.elt[g] = k, args.inv[g] = galois_inverse(k) & mask, args.key[g] = keys[g];
+            }
+            for (int m = 0; m < M; m++)
+                args.limb[m] = static_cast<unsigned char>(limbs[m]);
+            for (int j = 0; j < L; j++)
+                args.p_mod_q[j] = p_mod_q[j], args.p_mod_q_shoup[j] = p_mod_q_shoup[j];
+            if (count == 0)
+                return;
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const std::uint64_t a_bytes = cols * M * D * sizeof(T), c0_bytes = cols * L * sizeof(T);
+            const std::uint64_t out_bytes = cols * L * 2 * G * sizeof(T);
+            const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
+            for (const auto& w : {std::pair<const void*, std::uint64_t>{out, out_bytes}, {scratch, acc_bytes}})
+            {
+                bool hit = ks_overlap(w.first, w.second, a, a_bytes) ||
+                           (c0 != nullptr && ks_overlap(w.first, w.second, c0, c0_bytes));
+                for (int g = 0; g < G; g++)
+                    hit = hit || ks_overlap(w.first, w.second, keys[g], key_bytes);
+                if (hit)
+                    throw std::invalid_argument("out or the scratch overlaps an operand!");
+            }
+            if (ks_overlap(out, out_bytes, scratch, acc_bytes))
+                throw std::invalid_argument("The scratch overlaps out!");
+            const unsigned long long stacks = 2ull * static_cast<unsigned long long>(G) * static_cast<unsigned>(count);
+            if (stacks * static_cast<unsigned>(M) > 0x7FFFFFFFull) // the batch of the transforms is an int
+                throw std::invalid_argument("Invalid count!");
+            // mod_down's own grid limit, checked before the first launch
+            if ((((stacks << n) + kern::BC_NT - 1) / kern::BC_NT) * kern::BC_NT > 0xFFFFFFFFull)
+                throw std::invalid_argument("Invalid count!");
+            T* acc = static_cast<T*>(scratch);
+            // the first launch of the call: its own grid check throws before it
+            host::hoist_launch<T>(a, c0, acc, reinterpret_cast<const T*>(ws + lay.inner), args, D, count, L, M, KM, n,
+                                  negacyclic, stream);
+            const int s = static_cast<int>(stacks);
+            ntt_full_i->execute(acc, acc, s * M, stream);
+            mod_down(acc, out, s, stream);
+            if (output_ntt)
+                ntt_q_f->execute(out, out, s * L, stream);
+        }
     };
 
     template <typename T> int KeySwitchPlan<T>::digits(int q_count, int alpha)
@@ -560,6 +637,15 @@ namespace gpuntt
     }
 
     template <typename T>
+    size_t KeySwitchPlan<T>::hoisted_scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count,
+                                                   int elements)
+    {
+        ks_check_counts(q_count, p_count, alpha);
+        ks_check_n_power(n_power);
+        return ks_hoisted_scratch<T>(q_count + p_count, n_power, count, elements);
+    }
+
+    template <typename T>
     KeySwitchPlan<T>::KeySwitchPlan(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* p_moduli_host,
                                     int p_count, int alpha, int n_power, const Root<T>* forward_table_device,
                                     const Root<T>* inverse_table_device, const Ninverse<T>* mod_inverse_host,
@@ -577,6 +663,14 @@ namespace gpuntt
         std::unique_ptr<Impl> p(new Impl);
         p->L = h.L, p->K = h.K, p->M = h.M, p->alpha = h.alpha, p->D = h.D, p->n = n_power, p->KM = key_mod_count;
         p->lay = lay;
+        p->negacyclic = reduction_poly == ReductionPolynomial::X_N_plus;
+        for (int j = 0; j < h.L; j++)
+        {
+            const std::uint64_t pq = h.down.qmod[j]; // P mod q_j, what constants() returns as down_p_mod_q
+            p->p_mod_q.push_back(static_cast<T>(pq));
+            p->p_mod_q_shoup.push_back(
+                static_cast<T>((static_cast<U128>(pq) << (8 * sizeof(T))) / h.mod[j]));
+        }
         for (int m = 0; m < h.M; m++)
         {
             const int l = key_limbs_host != nullptr ? key_limbs_host[m] : m;
@@ -660,6 +754,14 @@ namespace gpuntt
         p_->switch_digits(device_a, device_key, device_out, count, components, output_ntt, scratch_device, stream);
     }
     template <typename T>
+    void KeySwitchPlan<T>::rotate_hoisted(const T* device_a, const T* device_c0, const T* const* device_keys_host,
+                                          const std::uint32_t* galois_elements_host, int elements, T* device_out,
+                                          int count, bool output_ntt, void* scratch_device, stream_t stream) const
+    {
+        p_->rotate_hoisted(device_a, device_c0, device_keys_host, galois_elements_host, elements, device_out, count,
+                           output_ntt, scratch_device, stream);
+    }
+    template <typename T>
     void KeySwitchPlan<T>::apply(const T* device_c_in, const T* device_key, T* device_out, int count, int components,
                                  bool input_ntt, bool output_ntt, void* scratch_device, stream_t stream) const
     {
@@ -687,6 +789,10 @@ namespace gpuntt
     template <typename T> size_t KeySwitchPlan<T>::scratch_bytes(int count, int components) const
     {
         return ks_scratch<T>(p_->L, p_->M, p_->D, p_->n, count, components).total;
+    }
+    template <typename T> size_t KeySwitchPlan<T>::hoisted_scratch_bytes(int count, int elements) const
+    {
+        return ks_hoisted_scratch<T>(p_->M, p_->n, count, elements);
     }
 
     template <typename T>

@@ -631,6 +631,7 @@ namespace gpuntt
         // from its first decision to its last launch, whatever another thread sets meanwhile.
         void baseconv_set_ksplit(int v); // base_conversion.hip
         void keyswitch_set_split(int v); // key_switch.hip
+        void keyswitch_set_hoist_chunk(int v); // hoisted_rotation.hip
         namespace
         {
             struct OptionValues
@@ -713,6 +714,10 @@ namespace gpuntt
                     // key_switch.hip: workgroups per column tile of the multi-digit ModUp, 0 = its own choice; like
                     // baseconv_ksplit a process-wide knob outside the per-call snapshot that never changes an output word
                     keyswitch_set_split(iv);
+                else if (test_hooks && k == "keyswitch_hoist_chunk" && is_num && (lv == 0 || (lv >= 6 && lv <= 13)))
+                    // hoisted_rotation.hip: log2 of the source chunk of inner_product_galois, 0 = its LDS budget rule;
+                    // like keyswitch_split a process-wide knob outside the per-call snapshot that changes no output word
+                    keyswitch_set_hoist_chunk(iv);
                 else if (test_hooks && k == "reset_predictions" && bit)
                     g_reset_predictions.store(1, std::memory_order_relaxed); // rns_guess forgets every stack it has seen
                 else

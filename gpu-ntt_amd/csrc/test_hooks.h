@@ -11,6 +11,8 @@
  *       two_sweep_big = 0 | 1    experiment: 64-bit rings 2^23 / 2^24 forward in two sweeps on 16384-coefficient tiles
  *       baseconv_ksplit = 0..16  base conversion: workgroups per column tile that share its outputs (0: the library's choice)
  *       keyswitch_split = 0..64  key switching: workgroups per column tile that share the (digit, block) pairs of the ModUp
+ *       keyswitch_hoist_chunk = 0 | 6..13  rotate_hoisted: log2 of the slots of a source chunk of inner_product_galois
+ *                                (0: the LDS budget rule; a forced chunk is still capped at N and at what LDS can hold)
  *       reset_predictions = 1    the family prediction of the RNS overloads forgets every stack it has seen
  *   gpuntt_test_launch_log_start()      start recording the kernel of every launch the library enqueues (all threads)
  *   gpuntt_test_launch_log_take(buf, n) stop; the kernels since start, space-separated ("prep_twiddles merge_pass_lazy:31 ..."),
@@ -18,6 +20,8 @@
  *   gpuntt_test_scratch_stats(out[6])   the twiddle scratch of captured calls, which their graph owns (prep.hip): buffers handed to
  *                                       a graph, of those reported dead by their graph, buffers pooled now, buffers re-used from
  *                                       the pool, chains erased, chains alive
+ *   gpuntt_test_keyswitch_hoist_chunk(word_bytes, digits, n_power)  host only: log2 of the chunk inner_product_galois takes
+ *                                       for this word size, D and ring under the hook's current value; -1: bad argument
  * Options are snapshot once per API call (prep.hip), so a hook set while another thread's call is in flight does not change
  * that call. */
 #ifndef GPUNTT_TEST_HOOKS_H
@@ -30,6 +34,7 @@ extern "C"
     int gpuntt_test_launch_log_start(void);
     int gpuntt_test_launch_log_take(char* buf, int capacity);
     int gpuntt_test_scratch_stats(unsigned long long out[6]);
+    int gpuntt_test_keyswitch_hoist_chunk(int word_bytes, int digits, int n_power);
 #ifdef __cplusplus
 }
 #endif

@@ -35,8 +35,39 @@
 //       key_mod_count / key_limbs into scratch T[C][count][M][N]; INTT over C * count * M; mod_down into
 //       out = T[C][count][L][N]; [output_ntt: forward NTT over C * count * L in place]
 //   apply(c_in, key, out, count, components, input_ntt, output_ntt, scratch) = decompose, then switch_digits, a in scratch
-//     The split is there to hoist: decompose once, permute a with GPU_Automorphism_NTT, switch_digits once per rotation key.
+//     The split is there to hoist: decompose once, then rotate_hoisted -- many rotation keys applied to one decomposition.
 //     key = T[D_key][C][key_mod_count][N] in NTT form, exactly InnerProductPlan's.
+//   rotate_hoisted(a, c0, keys, galois_elements, G, out, count, output_ntt, scratch):  G rotations (or any Galois
+//     automorphisms) of the count ciphertexts whose second components were decomposed into a = T[D][count][M][N] (what
+//     decompose writes), each with its own switching key; c0 = T[count][L][N] in NTT form, the first components, or
+//     nullptr; keys = a HOST array of G device pointers, each T[D_key][2][key_mod_count][N], read through the plan's
+//     key_mod_count / key_limbs; galois_elements = a HOST array of G odd elements k_g, reduced mod 2N (X_N_plus) or mod N
+//     (X_N_minus) as GPU_Automorphism_NTT reduces them, 1 <= G <= 64, duplicates and the identity allowed;
+//     out = T[G][2][count][L][N].  DEFINITION, word for word: out[g] is what the existing public calls give --
+//       1. GPU_Automorphism_NTT(a, k_g) over the D * count * M polynomials of a,
+//       2. switch_digits(that, keys[g], components = 2, output_ntt),
+//       3. c0 != nullptr: component 0 plus GPU_Automorphism_NTT(c0, k_g), added mod q_m; with output_ntt false the
+//          NTT-form operand is inverse-transformed before the addition.
+//     What runs instead, each step ONE launch over the whole batch (plus the transforms' own):
+//       inner_product_galois: acc[g][c][r][m][j] = (sum_d a[d][r][m][pi_g(j)] * keys[g][d][c][limb(m)][j]
+//                             + [c = 0, m < L, c0 != nullptr] (P mod q_m) * c0[r][m][pi_g(j)]) mod q_m into the scratch,
+//                             pi_g = galois_ntt_source(., k_g), the permutation of GPU_Automorphism_NTT -- the permuted
+//                             digits are never written to memory, every word of a and c0 is read once per call;
+//       the full-base INTT over G * 2 * count * M polynomials; mod_down with stacks = G * 2 * count into out;
+//       [output_ntt: the q-base forward NTT over G * 2 * count * L polynomials].
+//     Folding c0 in as P * c0 BEFORE the ModDown is exact, not approximate.  sigma_k and the transforms are linear, so the
+//     q-limbs of the stack that reaches mod_down hold c_j + P y (mod q_j), with c the accumulators of step 2 and
+//     y = sigma_k(c0) in coefficient form, while the special limbs are untouched (P = 0 mod p_k): the conversion term
+//     conv_j of mod_down is computed from the special limbs only and is identical.  Then
+//       (c_j + P y - conv_j) P^-1 = y + (c_j - conv_j) P^-1  (mod q_j),
+//     the right side is step 3's sum, and both sides are canonical residues, so they are the same word.  With output_ntt
+//     the forward NTT is linear and its outputs canonical, so the words agree there too.
+//     Every input word of a and c0 may hold any value (it is read modulo q_m); the keys are read the same way.
+//     Allocates nothing, never synchronises: one stream, capturable into a hipGraph as it is.  count = 0: nothing is
+//     launched.  The scratch is hoisted_scratch_bytes(count, G) bytes (the accumulators T[G][2][count][M][N]), 256-byte
+//     aligned; out and the scratch must not overlap a, c0, any key or each other.  std::invalid_argument, before anything
+//     is launched: G outside [1, 64], count < 0, an even element, a null a / out / key pointer / scratch, a scratch that
+//     is not 256-byte aligned, an overlap, a plan built without transforms
 //
 //   * ranges: 1 <= L, 1 <= K, M = L + K <= 64, alpha >= 1, 1 <= components <= 4, count >= 0 and stacks >= 0 (0: nothing
 //     happens), n_power in [1, 28], M <= key_mod_count <= 256.  A plan is built for ONE level (one L) and one ring; a
@@ -104,6 +135,7 @@ namespace gpuntt
       public:
         static size_t workspace_bytes(int q_count, int p_count, int alpha, int n_power);
         static size_t scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count, int components);
+        static size_t hoisted_scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count, int elements);
         static int digits(int q_count, int alpha); // D
 
         KeySwitchPlan(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* p_moduli_host, int p_count,
@@ -122,6 +154,9 @@ namespace gpuntt
                            bool output_ntt, void* scratch_device, stream_t stream) const;
         void apply(const T* device_c_in, const T* device_key, T* device_out, int count, int components, bool input_ntt,
                    bool output_ntt, void* scratch_device, stream_t stream) const;
+        void rotate_hoisted(const T* device_a, const T* device_c0, const T* const* device_keys_host,
+                            const std::uint32_t* galois_elements_host, int elements, T* device_out, int count,
+                            bool output_ntt, void* scratch_device, stream_t stream) const;
 
         int q_count() const;
         int p_count() const;
@@ -131,6 +166,7 @@ namespace gpuntt
         bool has_transforms() const;
         bool owns_workspace() const; // false: the plan lives in the caller's workspace and has allocated nothing
         size_t scratch_bytes(int count, int components) const;
+        size_t hoisted_scratch_bytes(int count, int elements) const;
 
         // host only (no GPU): the constants of these bases, with the checks of the constructor
         static void constants(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* p_moduli_host, int p_count,

@@ -374,6 +374,13 @@ extern "C"
      *   switch_digits  inner product of a and key (T[D_key][components][key_mod_count][N]), INTT, mod_down into
      *                  out T[components][count][L][N], [forward NTT of out]
      *   apply          decompose into the scratch, then switch_digits
+     *   rotate_hoisted G rotations from one decomposition: a T[D][count][M][N] (what decompose writes), c0 T[count][L][N] in
+     *                  NTT form or NULL, keys_host a HOST array of G device pointers (each T[D_key][2][key_mod_count][N]),
+     *                  galois_elements_host G odd elements (HOST, reduced as gpuntt_automorphism_ntt_* reduces them),
+     *                  1 <= G <= 64, out T[G][2][count][L][N]; the scratch is
+     *                  gpuntt_keyswitch_plan_hoisted_scratch_bytes_*() bytes, 256-byte aligned.  One inner product launch
+     *                  that applies the permutations while it multiplies, INTT, mod_down, [forward NTT] over the whole
+     *                  batch; out[g] equals automorphism + switch_digits + the rotated c0 word for word (key_switch.cuh)
      * No call allocates or synchronises.
      * host only (no GPU): constants -- arrays_host holds 18 caller arrays in the order of KeySwitchConstants<T>
      * (up_qhat_inv[L], up_qhat_inv_shoup[L], up_matrix[L][M], up_q_mod[D][M], up_recip[L], up_bit_length[L],
@@ -403,6 +410,12 @@ extern "C"
     int gpuntt_keyswitch_plan_apply_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* c_in, const uint32_t* key, uint32_t* out,
                                         int count, int components, int input_ntt, int output_ntt, void* scratch,
                                         void* stream);
+    int gpuntt_keyswitch_plan_hoisted_scratch_bytes_u32(int q_count, int p_count, int alpha, int n_power, int count,
+                                                        int elements, uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_rotate_hoisted_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* a, const uint32_t* c0,
+                                                 const uint32_t* const* keys_host, const uint32_t* galois_elements_host,
+                                                 int elements, uint32_t* out, int count, int output_ntt, void* scratch,
+                                                 void* stream);
     int gpuntt_keyswitch_plan_owns_workspace_u32(const gpuntt_keyswitch_plan* plan); /* 1 / 0, negative on error */
     int gpuntt_keyswitch_plan_destroy_u32(gpuntt_keyswitch_plan* plan);
     int gpuntt_keyswitch_constants_u32(const gpuntt_modulus32* q_moduli_host, int q_count, const gpuntt_modulus32* p_moduli_host, int p_count,
@@ -433,6 +446,12 @@ extern "C"
     int gpuntt_keyswitch_plan_apply_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* c_in, const uint64_t* key, uint64_t* out,
                                         int count, int components, int input_ntt, int output_ntt, void* scratch,
                                         void* stream);
+    int gpuntt_keyswitch_plan_hoisted_scratch_bytes_u64(int q_count, int p_count, int alpha, int n_power, int count,
+                                                        int elements, uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_rotate_hoisted_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* a, const uint64_t* c0,
+                                                 const uint64_t* const* keys_host, const uint32_t* galois_elements_host,
+                                                 int elements, uint64_t* out, int count, int output_ntt, void* scratch,
+                                                 void* stream);
     int gpuntt_keyswitch_plan_owns_workspace_u64(const gpuntt_keyswitch_plan* plan); /* 1 / 0, negative on error */
     int gpuntt_keyswitch_plan_destroy_u64(gpuntt_keyswitch_plan* plan);
     int gpuntt_keyswitch_constants_u64(const gpuntt_modulus64* q_moduli_host, int q_count, const gpuntt_modulus64* p_moduli_host, int p_count,
