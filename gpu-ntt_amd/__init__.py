@@ -13,7 +13,7 @@ src/include/gpuntt/ntt_4step/ntt_4step.cuh:46-49,278-308):
     InnerProductPlan / innerprod_constants / innerprod_reference (extension: RNS inner product,
     gpuntt/rns/inner_product.cuh)
     KeySwitchPlan / keyswitch_constants / keyswitch_scratch_bytes / keyswitch_hoisted_scratch_bytes /
-    keyswitch_reference_mod_up / keyswitch_reference_mod_down (extension: hybrid
+    keyswitch_hoisted_sum_scratch_bytes / keyswitch_reference_mod_up / keyswitch_reference_mod_down (extension: hybrid
     key switching, gpuntt/rns/key_switch.cuh)
     Modulus, ntt_configuration, ntt_rns_configuration, ntt4step_configuration,
     ntt4step_rns_configuration, NTTParameters, NTTParameters4Step
@@ -113,7 +113,8 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "keyswitch_plan_workspace_bytes", "keyswitch_plan_scratch_bytes", "keyswitch_plan_create",
               "keyswitch_plan_mod_up", "keyswitch_plan_mod_down", "keyswitch_plan_decompose",
               "keyswitch_plan_switch_digits", "keyswitch_plan_apply", "keyswitch_plan_hoisted_scratch_bytes",
-              "keyswitch_plan_rotate_hoisted", "keyswitch_plan_owns_workspace",
+              "keyswitch_plan_rotate_hoisted", "keyswitch_plan_hoisted_sum_scratch_bytes",
+              "keyswitch_plan_rotate_hoisted_sum", "keyswitch_plan_owns_workspace",
               "keyswitch_plan_destroy", "keyswitch_constants", "keyswitch_reference_mod_up",
               "keyswitch_reference_mod_down")
     for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option", "gpuntt_galois_element_u32",
@@ -894,6 +895,24 @@ def keyswitch_hoist_chunk(bits, digits, n_power):
     return lc
 
 
+def keyswitch_hoisted_sum_scratch_bytes(q_count, p_count, alpha, n_power, count, bits=64):
+    """KeySwitchPlan<T>::hoisted_sum_scratch_bytes (host only): the caller-owned scratch of rotate_hoisted_sum, in bytes
+    -- the accumulators T[2][count][M][N], rounded up to 256; it does not depend on the number of elements"""
+    out = ctypes.c_uint64()
+    _check(getattr(load_library(), "gpuntt_keyswitch_plan_hoisted_sum_scratch_bytes_u%d" % bits)(
+        int(q_count), int(p_count), int(alpha), int(n_power), int(count), ctypes.byref(out)))
+    return int(out.value)
+
+
+def keyswitch_hoist_sum_chunk(bits, digits, n_power):
+    """test hook read-back (csrc/test_hooks.h, host only): log2 of the destination chunk inner_product_galois_sum takes
+    for this word width, digit count and ring under the current value of the hook keyswitch_hoist_chunk"""
+    lc = load_library().gpuntt_test_keyswitch_hoist_sum_chunk(int(bits) // 8, int(digits), int(n_power))
+    if lc < 0:
+        raise ValueError("Invalid argument!")
+    return lc
+
+
 def keyswitch_constants(q_moduli, p_moduli, alpha, bits=64):
     """Host (no GPU): the constants a KeySwitchPlan of these bases uploads (KeySwitchConstants<T>), as a dict of numpy
     arrays -- per digit the ModUp constants up_qhat_inv[L], up_qhat_inv_shoup[L], up_matrix[L][M], up_q_mod[D][M],
@@ -1128,6 +1147,47 @@ class KeySwitchPlan:
         fn = getattr(load_library(), "gpuntt_keyswitch_plan_rotate_hoisted_u%d" % self.bits)
         _check(fn(self._h, _ptr(a), _ptr(c0), key_ptrs, elts, G, _ptr(out), int(count), int(bool(output_ntt)),
                   _ptr(scratch), _stream(stream)))
+
+    def hoisted_sum_scratch_bytes(self, count):
+        return keyswitch_hoisted_sum_scratch_bytes(self.q_count, self.p_count, self.alpha, self.n_power, count,
+                                                   self.bits)
+
+    def rotate_hoisted_sum(self, a, c0, keys, elements, weights, out, count, output_ntt=False, scratch=None,
+                           stream=None):
+        """The weighted sum of G = len(elements) Galois automorphisms of one decomposition, taken before the ModDown:
+        a, c0, keys and elements as for rotate_hoisted; weights None (all 1) or a list of G entries, each None (1) or a
+        device tensor of at least M x N words -- the plaintext diagonal in NTT form over the plan's full base; out
+        T[2][count][L][N]; scratch: a device tensor of at least hoisted_sum_scratch_bytes(count) bytes, 256-byte
+        aligned.  One INTT, one mod_down and one NTT whatever G is; the result rounds once (key_switch.cuh)."""
+        keys, elements = list(keys), [int(k) for k in elements]
+        G, cols = len(elements), self._cols(count)
+        if len(keys) != G:
+            raise ValueError("rotate_hoisted_sum takes one key per Galois element")
+        weights = None if weights is None else list(weights)
+        if weights is not None and len(weights) != G:
+            raise ValueError("rotate_hoisted_sum takes one weight (or None) per Galois element")
+        if not 1 <= G <= 64:
+            raise ValueError("Invalid galois_count!")
+        if a is None or out is None or scratch is None or any(k is None for k in keys):
+            raise ValueError("null pointer argument")
+        sized = [(a, cols * self.mod_count * self.digits, "a (D x count x M x N)"),
+                 (out, cols * self.q_count * 2, "out (2 x count x L x N)")]
+        if c0 is not None:
+            sized.append((c0, cols * self.q_count, "c0 (count x L x N)"))
+        sized += [(k, self._key_words(2) if cols else 0, "key (D x 2 x key_mod_count x N)") for k in keys]
+        sized += [(w, self.mod_count << self.n_power if cols else 0, "weight (M x N)")
+                  for w in (weights or ()) if w is not None]
+        self._check_buffers(sized)
+        _require_gpu(scratch)
+        if int(count) >= 0 and scratch.numel() * scratch.element_size() < self.hoisted_sum_scratch_bytes(count):
+            raise ValueError("scratch holds fewer than hoisted_sum_scratch_bytes(count) bytes")
+        key_ptrs = (ctypes.c_void_p * G)(*[k.data_ptr() for k in keys])
+        weight_ptrs = None if weights is None else \
+            (ctypes.c_void_p * G)(*[None if w is None else w.data_ptr() for w in weights])
+        elts = (ctypes.c_uint32 * G)(*[k & 0xFFFFFFFF for k in elements])
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_rotate_hoisted_sum_u%d" % self.bits)
+        _check(fn(self._h, _ptr(a), _ptr(c0), key_ptrs, elts, weight_ptrs, G, _ptr(out), int(count),
+                  int(bool(output_ntt)), _ptr(scratch), _stream(stream)))
 
     def close(self):
         if self._h:

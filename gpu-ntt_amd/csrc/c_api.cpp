@@ -28,6 +28,7 @@ namespace gpuntt
         std::string launch_log_take();
         void scratch_stats(unsigned long long out[6]);
         int hoist_chunk_log(size_t word_bytes, int D, int n_power); // hoisted_rotation.hip
+        int hoist_sum_chunk_log(size_t word_bytes, int D, int n_power); // hoisted_sum.hip
     } // namespace host
 } // namespace gpuntt
 
@@ -523,6 +524,13 @@ extern "C"
             return -1;
         return host::hoist_chunk_log(static_cast<size_t>(word_bytes), digits, n_power);
     }
+    int gpuntt_test_keyswitch_hoist_sum_chunk(int word_bytes, int digits, int n_power)
+    {
+        if ((word_bytes != 4 && word_bytes != 8) || digits < 1 || digits > INNERPROD_MAX_DIGITS || n_power < 1 ||
+            n_power > 28)
+            return -1;
+        return host::hoist_sum_chunk_log(static_cast<size_t>(word_bytes), digits, n_power);
+    }
 
     int gpuntt_galois_element_u32(int steps, int n_power, int conjugation, uint32_t* elt_host)
     {
@@ -962,6 +970,27 @@ extern "C"
             reinterpret_cast<const KeySwitchPlan<T>*>(plan)->rotate_hoisted(                      \
                 a, c0, keys_host, galois_elements_host, elements, out, count, output_ntt != 0, scratch,           \
                 static_cast<hipStream_t>(stream));                                                \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_hoisted_sum_scratch_bytes_##S(int q_count, int p_count, int alpha, int n_power,     \
+                                                            int count, uint64_t* bytes_host)       \
+    {                                                                                             \
+        GPUNTT_NEED(bytes_host)                                                                   \
+        return guarded([&] {                                                                      \
+            *bytes_host = KeySwitchPlan<T>::hoisted_sum_scratch_bytes(q_count, p_count, alpha, n_power, count);   \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_rotate_hoisted_sum_##S(const gpuntt_keyswitch_plan* plan, const T* a, const T* c0,   \
+                                                     const T* const* keys_host,                   \
+                                                     const uint32_t* galois_elements_host,        \
+                                                     const T* const* weights_host, int elements, T* out,          \
+                                                     int count, int output_ntt, void* scratch, void* stream)      \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->rotate_hoisted_sum(                  \
+                a, c0, keys_host, galois_elements_host, weights_host, elements, out, count, output_ntt != 0,      \
+                scratch, static_cast<hipStream_t>(stream));                                       \
         });                                                                                       \
     }                                                                                             \
     int gpuntt_keyswitch_plan_owns_workspace_##S(const gpuntt_keyswitch_plan* plan)               \

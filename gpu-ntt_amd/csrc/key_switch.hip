@@ -24,6 +24,10 @@
 // rotate_hoisted: inner_product_galois of hoisted_rotation.hip (the inner product that permutes while it multiplies, all
 // G elements in one launch), then the plan's own full-base INTT, mod_down and q-base NTT over G * 2 * count stacks
 // (DESIGN.md 3.13).
+//
+// rotate_hoisted_sum: inner_product_galois_sum of hoisted_sum.hip (the same inner product, weighted and summed over the G
+// elements in the extended base), then ONE full-base INTT, mod_down and q-base NTT over 2 * count stacks whatever G is
+// (DESIGN.md 3.14).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +41,7 @@
 #include "gpuntt/ntt_merge/ntt.cuh"
 #include "gpuntt/rns/key_switch.cuh"
 #include "hoisted_rotation_internal.hpp"
+#include "hoisted_sum_internal.hpp"
 #include "launch.hpp"
 
 namespace gpuntt
@@ -440,6 +445,14 @@ namespace gpuntt
                 throw std::invalid_argument("Invalid galois_count!");
             return ks_align((static_cast<size_t>(count) << n_power) * sizeof(T) * M * 2 * elements);
         }
+
+        // the scratch of rotate_hoisted_sum, in bytes: the accumulators T[2][count][M][N], whatever G is
+        template <typename T> size_t ks_hoisted_sum_scratch(int M, int n_power, int count)
+        {
+            if (count < 0)
+                throw std::invalid_argument("Invalid count!");
+            return ks_align((static_cast<size_t>(count) << n_power) * sizeof(T) * M * 2);
+        }
     } // namespace
 
     template <typename T> struct KeySwitchPlan<T>::Impl
@@ -614,6 +627,71 @@ namespace gpuntt
             if (output_ntt)
                 ntt_q_f->execute(out, out, s * L, stream);
         }
+
+        void rotate_hoisted_sum(const T* a, const T* c0, const T* const* keys, const std::uint32_t* elts,
+                                const T* const* weights, int G, T* out, int count, bool output_ntt, void* scratch,
+                                hipStream_t stream) const
+        {
+            need_transforms();
+            const size_t acc_bytes = ks_hoisted_sum_scratch<T>(M, n, count); // checks count
+            if (G < 1 || G > GALOIS_MAX_COUNT)
+                throw std::invalid_argument("Invalid galois_count!");
+            if (a == nullptr || keys == nullptr || elts == nullptr || out == nullptr || scratch == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
+                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            kern::HoistSumArgs<T> args{};
+            args.h.count = G;
+            const std::uint32_t mask = negacyclic ? (2u << n) - 1u : (1u << n) - 1u; // as GPU_Automorphism_NTT reduces
+            for (int g = 0; g < G; g++)
+            {
+                const std::uint32_t k = elts[g] & mask;
+                if ((k & 1u) == 0u)
+                    throw std::invalid_argument("Invalid Galois element (must be odd)!");
+                if (keys[g] == nullptr)
+                    throw std::invalid_argument("null pointer argument");
+                args.h.elt[g] = k, args.h.inv[g] = galois_inverse(k) & mask, args.h.key[g] = keys[g];
+                args.weight[g] = weights != nullptr ? weights[g] : nullptr;
+            }
+            for (int m = 0; m < M; m++)
+                args.h.limb[m] = static_cast<unsigned char>(limbs[m]);
+            for (int j = 0; j < L; j++)
+                args.h.p_mod_q[j] = p_mod_q[j], args.h.p_mod_q_shoup[j] = p_mod_q_shoup[j];
+            if (count == 0)
+                return;
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const std::uint64_t a_bytes = cols * M * D * sizeof(T), c0_bytes = cols * L * sizeof(T);
+            const std::uint64_t out_bytes = cols * L * 2 * sizeof(T);
+            const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
+            const std::uint64_t weight_bytes = (static_cast<std::uint64_t>(M) << n) * sizeof(T);
+            for (const auto& w : {std::pair<const void*, std::uint64_t>{out, out_bytes}, {scratch, acc_bytes}})
+            {
+                bool hit = ks_overlap(w.first, w.second, a, a_bytes) ||
+                           (c0 != nullptr && ks_overlap(w.first, w.second, c0, c0_bytes));
+                for (int g = 0; g < G; g++)
+                    hit = hit || ks_overlap(w.first, w.second, keys[g], key_bytes) ||
+                          (args.weight[g] != nullptr && ks_overlap(w.first, w.second, args.weight[g], weight_bytes));
+                if (hit)
+                    throw std::invalid_argument("out or the scratch overlaps an operand!");
+            }
+            if (ks_overlap(out, out_bytes, scratch, acc_bytes))
+                throw std::invalid_argument("The scratch overlaps out!");
+            const unsigned long long stacks = 2ull * static_cast<unsigned>(count);
+            if (stacks * static_cast<unsigned>(M) > 0x7FFFFFFFull) // the batch of the transforms is an int
+                throw std::invalid_argument("Invalid count!");
+            // mod_down's own grid limit, checked before the first launch
+            if ((((stacks << n) + kern::BC_NT - 1) / kern::BC_NT) * kern::BC_NT > 0xFFFFFFFFull)
+                throw std::invalid_argument("Invalid count!");
+            T* acc = static_cast<T*>(scratch);
+            // the first launch of the call: its own grid check throws before it
+            host::hoist_sum_launch<T>(a, c0, acc, reinterpret_cast<const T*>(ws + lay.inner), args, D, count, L, M, KM, n,
+                                      negacyclic, stream);
+            const int s = static_cast<int>(stacks);
+            ntt_full_i->execute(acc, acc, s * M, stream);
+            mod_down(acc, out, s, stream);
+            if (output_ntt)
+                ntt_q_f->execute(out, out, s * L, stream);
+        }
     };
 
     template <typename T> int KeySwitchPlan<T>::digits(int q_count, int alpha)
@@ -643,6 +721,14 @@ namespace gpuntt
         ks_check_counts(q_count, p_count, alpha);
         ks_check_n_power(n_power);
         return ks_hoisted_scratch<T>(q_count + p_count, n_power, count, elements);
+    }
+
+    template <typename T>
+    size_t KeySwitchPlan<T>::hoisted_sum_scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count)
+    {
+        ks_check_counts(q_count, p_count, alpha);
+        ks_check_n_power(n_power);
+        return ks_hoisted_sum_scratch<T>(q_count + p_count, n_power, count);
     }
 
     template <typename T>
@@ -762,6 +848,15 @@ namespace gpuntt
                            output_ntt, scratch_device, stream);
     }
     template <typename T>
+    void KeySwitchPlan<T>::rotate_hoisted_sum(const T* device_a, const T* device_c0, const T* const* device_keys_host,
+                                              const std::uint32_t* galois_elements_host,
+                                              const T* const* device_weights_host, int elements, T* device_out, int count,
+                                              bool output_ntt, void* scratch_device, stream_t stream) const
+    {
+        p_->rotate_hoisted_sum(device_a, device_c0, device_keys_host, galois_elements_host, device_weights_host, elements,
+                               device_out, count, output_ntt, scratch_device, stream);
+    }
+    template <typename T>
     void KeySwitchPlan<T>::apply(const T* device_c_in, const T* device_key, T* device_out, int count, int components,
                                  bool input_ntt, bool output_ntt, void* scratch_device, stream_t stream) const
     {
@@ -793,6 +888,10 @@ namespace gpuntt
     template <typename T> size_t KeySwitchPlan<T>::hoisted_scratch_bytes(int count, int elements) const
     {
         return ks_hoisted_scratch<T>(p_->M, p_->n, count, elements);
+    }
+    template <typename T> size_t KeySwitchPlan<T>::hoisted_sum_scratch_bytes(int count) const
+    {
+        return ks_hoisted_sum_scratch<T>(p_->M, p_->n, count);
     }
 
     template <typename T>

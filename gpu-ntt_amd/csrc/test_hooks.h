@@ -22,6 +22,9 @@
  *                                       the pool, chains erased, chains alive
  *   gpuntt_test_keyswitch_hoist_chunk(word_bytes, digits, n_power)  host only: log2 of the chunk inner_product_galois takes
  *                                       for this word size, D and ring under the hook's current value; -1: bad argument
+ *   gpuntt_test_keyswitch_hoist_sum_chunk(word_bytes, digits, n_power)  the same for the destination chunk of
+ *                                       inner_product_galois_sum (rotate_hoisted_sum): its own rule -- one slot per lane, at
+ *                                       most 256 slots -- which the hook keyswitch_hoist_chunk forces as well, inside that cap
  * Options are snapshot once per API call (prep.hip), so a hook set while another thread's call is in flight does not change
  * that call. */
 #ifndef GPUNTT_TEST_HOOKS_H
@@ -35,6 +38,7 @@ extern "C"
     int gpuntt_test_launch_log_take(char* buf, int capacity);
     int gpuntt_test_scratch_stats(unsigned long long out[6]);
     int gpuntt_test_keyswitch_hoist_chunk(int word_bytes, int digits, int n_power);
+    int gpuntt_test_keyswitch_hoist_sum_chunk(int word_bytes, int digits, int n_power);
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,39 @@
 //     aligned; out and the scratch must not overlap a, c0, any key or each other.  std::invalid_argument, before anything
 //     is launched: G outside [1, 64], count < 0, an even element, a null a / out / key pointer / scratch, a scratch that
 //     is not 256-byte aligned, an overlap, a plan built without transforms
+//   rotate_hoisted_sum(a, c0, keys, galois_elements, weights, G, out, count, output_ntt, scratch):  the weighted sum of
+//     those G rotations, sum_g pt_g (.) sigma_{k_g}(ct) -- a linear transform (a matrix diagonal per rotation, a
+//     baby-step/giant-step product, CoeffToSlot) -- taken in the extended base P Q BEFORE the ModDown ("double hoisting").
+//     a, c0, keys, galois_elements and G are exactly rotate_hoisted's (1 <= G <= 64, duplicates and the identity allowed,
+//     elements reduced as GPU_Automorphism_NTT reduces them, key_mod_count / key_limbs from the plan).
+//     weights = a HOST array of G device pointers, or nullptr (every weight is 1: the plain sum of the rotations);
+//     weights[g] = T[M][N], the plaintext diagonal pt_g in NTT form over the FULL base, limb m under modulus m of the
+//     plan's full base -- any word is accepted, it is read modulo q_m -- or nullptr (weight 1).
+//     out = T[2][count][L][N].  DEFINITION, with pi_g = galois_ntt_source(., k_g) and w_g[m][j] = weights[g][m][j] mod q_m
+//     (1 where the pointer is null):
+//       u_g[c][r][m][j] = (sum_d a[d][r][m][pi_g(j)] * keys[g][d][c][limb(m)][j]
+//                          + [c = 0, m < L, c0 != nullptr] (P mod q_m) * c0[r][m][pi_g(j)]) mod q_m  -- rotate_hoisted's acc
+//       acc[c][r][m][j] = (sum_g w_g[m][j] * u_g[c][r][m][j]) mod q_m                               -- canonical
+//     into the scratch (inner_product_galois_sum, ONE launch), then the plan's own steps, each ONE launch over the whole
+//     batch plus the transforms' own: the full-base INTT over 2 * count * M polynomials; mod_down with stacks = 2 * count
+//     into out; [output_ntt: the q-base forward NTT over 2 * count * L polynomials].  One INTT, one mod_down and one NTT
+//     over 2 * count stacks whatever G is, where rotate_hoisted runs them over G * 2 * count.
+//     NOT word for word sum_g pt_g (.) rotate_hoisted(...)[g]: that expression rounds G times, this one once.  With U_g
+//     the coefficient-form stack of u_g (full base, the value X_g = CRT(U_g) taken mod P Q) and pt_g the weight as a
+//     polynomial, rotate_hoisted returns r_g = (X_g - [X_g]_P) / P (mod Q), [.]_P the centred residue mod P that
+//     mod_down converts -- round(X_g / P) outside base_conversion.cuh's rounding band -- while this call returns
+//     (S - [S]_P) / P (mod Q) for S = sum_g pt_g X_g mod P Q.  Both sides are exact in the q-limbs, so
+//       out - sum_g pt_g r_g = (sum_g pt_g [X_g]_P - [S]_P) / P  (mod Q),
+//     a multiple of P divided by P: an integer polynomial of infinity norm at most (1 + sum_g |pt_g|_1) / 2 (plus the
+//     rounding band of each conversion).  That difference is the rounding noise the G-fold expression carries and this
+//     one does not: here the error against the exact sum_g pt_g X_g / P is that of ONE mod_down, whatever G and pt_g are.
+//     The c0 term is exact as above (P c0 is 0 mod P and leaves [.]_P alone); the weight applies to it too.
+//     Contract as for rotate_hoisted: allocates nothing, never synchronises, one stream, capturable as it is; count = 0
+//     launches nothing.  The scratch is hoisted_sum_scratch_bytes(count) bytes (the accumulators T[2][count][M][N] --
+//     it does not grow with G), 256-byte aligned; out and the scratch must not overlap a, c0, any key, any non-null weight
+//     or each other.  std::invalid_argument, before anything is launched: G outside [1, 64], count < 0, an even element
+//     (also one that is even once reduced), a null a / out / key pointer / scratch, a scratch that is not 256-byte aligned,
+//     an overlap, a count beyond the grid and batch limits rotate_hoisted checks, a plan built without transforms
 //
 //   * ranges: 1 <= L, 1 <= K, M = L + K <= 64, alpha >= 1, 1 <= components <= 4, count >= 0 and stacks >= 0 (0: nothing
 //     happens), n_power in [1, 28], M <= key_mod_count <= 256.  A plan is built for ONE level (one L) and one ring; a
@@ -136,6 +169,7 @@ namespace gpuntt
         static size_t workspace_bytes(int q_count, int p_count, int alpha, int n_power);
         static size_t scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count, int components);
         static size_t hoisted_scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count, int elements);
+        static size_t hoisted_sum_scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count);
         static int digits(int q_count, int alpha); // D
 
         KeySwitchPlan(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* p_moduli_host, int p_count,
@@ -157,6 +191,10 @@ namespace gpuntt
         void rotate_hoisted(const T* device_a, const T* device_c0, const T* const* device_keys_host,
                             const std::uint32_t* galois_elements_host, int elements, T* device_out, int count,
                             bool output_ntt, void* scratch_device, stream_t stream) const;
+        void rotate_hoisted_sum(const T* device_a, const T* device_c0, const T* const* device_keys_host,
+                                const std::uint32_t* galois_elements_host, const T* const* device_weights_host,
+                                int elements, T* device_out, int count, bool output_ntt, void* scratch_device,
+                                stream_t stream) const;
 
         int q_count() const;
         int p_count() const;
@@ -167,6 +205,7 @@ namespace gpuntt
         bool owns_workspace() const; // false: the plan lives in the caller's workspace and has allocated nothing
         size_t scratch_bytes(int count, int components) const;
         size_t hoisted_scratch_bytes(int count, int elements) const;
+        size_t hoisted_sum_scratch_bytes(int count) const;
 
         // host only (no GPU): the constants of these bases, with the checks of the constructor
         static void constants(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* p_moduli_host, int p_count,

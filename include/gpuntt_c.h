@@ -381,6 +381,13 @@ extern "C"
      *                  gpuntt_keyswitch_plan_hoisted_scratch_bytes_*() bytes, 256-byte aligned.  One inner product launch
      *                  that applies the permutations while it multiplies, INTT, mod_down, [forward NTT] over the whole
      *                  batch; out[g] equals automorphism + switch_digits + the rotated c0 word for word (key_switch.cuh)
+     *   rotate_hoisted_sum  the weighted sum of those G rotations taken before the ModDown: a, c0, keys_host,
+     *                  galois_elements_host and G as for rotate_hoisted; weights_host a HOST array of G device pointers or
+     *                  NULL (all weights 1), each T[M][N] in NTT form over the plan's full base (any words, read modulo
+     *                  q_m) or NULL (weight 1); out T[2][count][L][N]; the scratch is
+     *                  gpuntt_keyswitch_plan_hoisted_sum_scratch_bytes_*() bytes (independent of G), 256-byte aligned.  One
+     *                  inner product launch, then ONE INTT, mod_down and [forward NTT] over 2 * count stacks; the result
+     *                  rounds once and is NOT word for word the weighted sum of rotate_hoisted's outputs (key_switch.cuh)
      * No call allocates or synchronises.
      * host only (no GPU): constants -- arrays_host holds 18 caller arrays in the order of KeySwitchConstants<T>
      * (up_qhat_inv[L], up_qhat_inv_shoup[L], up_matrix[L][M], up_q_mod[D][M], up_recip[L], up_bit_length[L],
@@ -416,6 +423,12 @@ extern "C"
                                                  const uint32_t* const* keys_host, const uint32_t* galois_elements_host,
                                                  int elements, uint32_t* out, int count, int output_ntt, void* scratch,
                                                  void* stream);
+    int gpuntt_keyswitch_plan_hoisted_sum_scratch_bytes_u32(int q_count, int p_count, int alpha, int n_power, int count,
+                                                            uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_rotate_hoisted_sum_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* a, const uint32_t* c0,
+                                                     const uint32_t* const* keys_host, const uint32_t* galois_elements_host,
+                                                     const uint32_t* const* weights_host, int elements, uint32_t* out,
+                                                     int count, int output_ntt, void* scratch, void* stream);
     int gpuntt_keyswitch_plan_owns_workspace_u32(const gpuntt_keyswitch_plan* plan); /* 1 / 0, negative on error */
     int gpuntt_keyswitch_plan_destroy_u32(gpuntt_keyswitch_plan* plan);
     int gpuntt_keyswitch_constants_u32(const gpuntt_modulus32* q_moduli_host, int q_count, const gpuntt_modulus32* p_moduli_host, int p_count,
@@ -452,6 +465,12 @@ extern "C"
                                                  const uint64_t* const* keys_host, const uint32_t* galois_elements_host,
                                                  int elements, uint64_t* out, int count, int output_ntt, void* scratch,
                                                  void* stream);
+    int gpuntt_keyswitch_plan_hoisted_sum_scratch_bytes_u64(int q_count, int p_count, int alpha, int n_power, int count,
+                                                            uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_rotate_hoisted_sum_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* a, const uint64_t* c0,
+                                                     const uint64_t* const* keys_host, const uint32_t* galois_elements_host,
+                                                     const uint64_t* const* weights_host, int elements, uint64_t* out,
+                                                     int count, int output_ntt, void* scratch, void* stream);
     int gpuntt_keyswitch_plan_owns_workspace_u64(const gpuntt_keyswitch_plan* plan); /* 1 / 0, negative on error */
     int gpuntt_keyswitch_plan_destroy_u64(gpuntt_keyswitch_plan* plan);
     int gpuntt_keyswitch_constants_u64(const gpuntt_modulus64* q_moduli_host, int q_count, const gpuntt_modulus64* p_moduli_host, int p_count,
