@@ -61,7 +61,7 @@ def composition_sum(g, plan, st, a, c0, keys, elts, weights, count, output_ntt, 
         g.GPU_Automorphism_NTT(pc0, c0_rot, elts, n_power, poly, count * L)
         c0_rot = c0_rot.view(G, count, L, n)
         qt = g.to_device(np.array(qs[:L], dtype=dt)).view(1, 1, L, 1)
-        s = u[:, 0, :, :L, :] + c0_rot  # both below q < 2^(W-3): no wrap in the signed type
+        s = u[:, 0, :, :L, :] + c0_rot  # both below q < 2^(W-2): 2 q - 2 < 2^(W-1), no wrap in the signed type
         u[:, 0, :, :L, :] = torch.where(s >= qt, s - qt, s)
     wkey = np.ones((G, M, n), dtype=dt)  # T[G][1][M][N]; all-ones limbs for null entries
     for i in range(G):

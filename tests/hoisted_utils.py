@@ -6,6 +6,9 @@ import numpy as np
 from gpu_utils import MergeCase, distinct_factors_scaled
 
 _rings = {}
+DEFAULT_WIDTHS = {64: (60, 59, 58, 57), 32: (30, 29, 28, 27)}
+# the top of what Modulus<T> accepts: 3 q < 2^W is all the kernels' bounds rest on
+WIDE_WIDTHS = {64: (62, 61, 62, 60), 32: (30, 29, 30, 28)}
 
 
 def tdtype(bits):
@@ -13,14 +16,40 @@ def tdtype(bits):
     return torch.int64 if bits == 64 else torch.int32
 
 
-class Ring:
-    """M NTT primes (below 2^(W-3), so that a sum of two residues fits the signed torch type) with their tables for one
-    (bits, n_power, reduction polynomial)"""
+def spread_factors(bits, M, logn):
+    """(q, omega, psi) for M NTT primes of bits - 2 bits spread over the eighth below 2^(bits-2).  The primes a search
+    from the top finds lie within ~2^(logn+10) of the power of two: there 2^W mod q and 2^2W mod q are tiny, the three-
+    product fold puts all its weight on two terms and its sum never passes 2 q.  Only moduli further down drive the
+    sum into [2^(W-1), 3 q), where a signed comparison or a lost top carry shows."""
+    from gpu_utils import _is_probable_prime
+    w, step, out = bits - 2, 1 << (logn + 1), []
+    for i in range(M):
+        q = ((1 << w) - ((1 << (w - 3)) * (i + 1)) // (M + 1)) // step * step + 1
+        while not _is_probable_prime(q):
+            q -= step
+        assert q.bit_length() == w and all(q != f[0] for f in out)
+        b = 2
+        while True:
+            psi = pow(b, (q - 1) >> (logn + 1), q)
+            if pow(psi, 1 << logn, q) == q - 1:
+                break
+            b += 1
+        out.append((q, psi * psi % q, psi))
+    return out
 
-    def __init__(self, g, bits, n_power, M, poly):
-        widths = (60, 59, 58, 57) if bits == 64 else (30, 29, 28, 27)
-        self.cases = [MergeCase(g, bits, n_power, poly, f)
-                      for f in distinct_factors_scaled([widths[i % 4] for i in range(M)], n_power)]
+
+class Ring:
+    """M NTT primes of the given widths, cycled (below 2^(W-2), so that a sum of two residues, at most 2 q - 2 <
+    2^(W-1), fits the signed torch type) with their tables for one (bits, n_power, reduction polynomial)"""
+
+    def __init__(self, g, bits, n_power, M, poly, widths=None):
+        if widths == "spread":
+            factors = spread_factors(bits, M, n_power)
+        else:
+            widths = DEFAULT_WIDTHS[bits] if widths is None else tuple(widths)
+            assert max(widths) <= bits - 2
+            factors = distinct_factors_scaled([widths[i % len(widths)] for i in range(M)], n_power)
+        self.cases = [MergeCase(g, bits, n_power, poly, f) for f in factors]
         n = 1 << n_power
         dt = g.np_dtype(bits)
         fwd, inv = np.zeros(M * n, dtype=dt), np.zeros(M * n, dtype=dt)
@@ -44,11 +73,15 @@ class Ring:
                     d_ninv=g.to_device(np.array(ninv, dtype=g.np_dtype(self.bits))))
 
 
-def ring(g, bits, n_power, M=8, poly=None):
+def ring(g, bits, n_power, M=8, poly=None, widths=None):
+    """widths: None (DEFAULT_WIDTHS), "wide" (WIDE_WIDTHS), "spread" (spread_factors) or a tuple of prime widths, cycled
+    over the M primes"""
     poly = g.X_N_plus if poly is None else poly
-    key = (bits, n_power, M, poly)
+    if widths != "spread":
+        widths = DEFAULT_WIDTHS[bits] if widths is None else WIDE_WIDTHS[bits] if widths == "wide" else tuple(widths)
+    key = (bits, n_power, M, poly, widths)
     if key not in _rings:
-        _rings[key] = Ring(g, bits, n_power, M, poly)
+        _rings[key] = Ring(g, bits, n_power, M, poly, widths)
     return _rings[key]
 
 
@@ -120,7 +153,7 @@ def composition(g, plan, st, a, c0, keys, elts, count, output_ntt):
     for i in range(G):
         plan.switch_digits(a_rot[i], keys[i], out[i].view(-1), count, 2, output_ntt, scratch)
         if c0 is not None:
-            s = out[i, 0] + c0_rot[i]  # both below q < 2^(W-3): no wrap in the signed type
+            s = out[i, 0] + c0_rot[i]  # both below q < 2^(W-2): 2 q - 2 < 2^(W-1), no wrap in the signed type
             out[i, 0] = torch.where(s >= qt, s - qt, s)
     torch.cuda.synchronize()
     return out.view(-1)

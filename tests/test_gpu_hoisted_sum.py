@@ -79,24 +79,39 @@ COMBOS = [(1, 1), (5, 3), (1, 3), (5, 1)]
 @pytest.mark.parametrize("bits", [64, 32])
 @pytest.mark.parametrize("n_power", [1, 2, 5, 6, 7, 9])
 @pytest.mark.parametrize("L,K,alpha", [(3, 2, 2), (6, 2, 2)])
-def test_every_output_word_with_chunks_of_64_slots(g, chunk6, bits, n_power, L, K, alpha):
+def test_every_output_word_with_chunks_of_64_slots(g, chunk6, bits, n_power, L, K, alpha, widths=None):
     """sub-chunk rings (one polynomial per workgroup, lanes without a slot), one chunk exactly, then 2 and 8 chunks: the
     source chunk differs per element, which is where a stale LDS tile or a missing barrier shows"""
     M = L + K
-    st = ring(g, bits, n_power).sub(list(range(M)))
+    st = ring(g, bits, n_power, widths=widths).sub(list(range(M)))
     plan = make_plan(g, st, L, alpha, n_power, bits)
     assert g.keyswitch_hoist_sum_chunk(bits, plan.digits, n_power) == min(6, n_power)
     check_against_the_composition(g, plan, st, np.random.default_rng(100 * n_power + L + bits), COMBOS)
 
 
 @pytest.mark.parametrize("bits", [64, 32])
+@pytest.mark.parametrize("n_power", [6, 7])
 @pytest.mark.parametrize("L,K,alpha", [(3, 2, 2), (6, 2, 2)])
-def test_every_output_word_with_the_automatic_chunk(g, bits, L, K, alpha):
+def test_chunks_of_64_slots_on_the_widest_primes(g, chunk6, bits, n_power, L, K, alpha):
+    """primes of 62/61 and 30/29 bits (hoisted_utils.WIDE_WIDTHS), one chunk exactly and two chunks: 2 q passes
+    2^(W-1), where a signed comparison or a carry lost from the top bit shows"""
+    test_every_output_word_with_chunks_of_64_slots(g, chunk6, bits, n_power, L, K, alpha, "wide")
+
+
+@pytest.mark.parametrize("bits", [64, 32])
+@pytest.mark.parametrize("L,K,alpha", [(3, 2, 2), (6, 2, 2)])
+def test_every_output_word_with_the_automatic_chunk(g, bits, L, K, alpha, widths=None):
     n_power, M = 12, L + K
-    st = ring(g, bits, n_power).sub(list(range(M)))
+    st = ring(g, bits, n_power, widths=widths).sub(list(range(M)))
     plan = make_plan(g, st, L, alpha, n_power, bits)
     assert n_power - g.keyswitch_hoist_sum_chunk(bits, plan.digits, n_power) >= 1  # at least 2 chunks per polynomial
     check_against_the_composition(g, plan, st, np.random.default_rng(L + bits), COMBOS)
+
+
+@pytest.mark.parametrize("bits", [64, 32])
+@pytest.mark.parametrize("L,K,alpha", [(3, 2, 2), (6, 2, 2)])
+def test_the_automatic_chunk_on_the_widest_primes(g, bits, L, K, alpha):
+    test_every_output_word_with_the_automatic_chunk(g, bits, L, K, alpha, "wide")
 
 
 @pytest.mark.parametrize("bits", [64, 32])
@@ -112,14 +127,19 @@ def test_sixty_four_elements(g, chunk6, bits):
 
 
 @pytest.mark.parametrize("bits", [64, 32])
-def test_many_digits_force_a_small_chunk(g, bits):
+def test_many_digits_force_a_small_chunk(g, bits, widths=None):
     """(L, K, alpha) = (20, 2, 1): D = 20, 21 rows of LDS per chunk slot"""
     n_power, L, K, alpha = 9, 20, 2, 1
-    st = ring(g, bits, n_power, M=L + K).sub(list(range(L + K)))
+    st = ring(g, bits, n_power, M=L + K, widths=widths).sub(list(range(L + K)))
     plan = make_plan(g, st, L, alpha, n_power, bits)
     # 21 rows x 256 slots x 8 bytes = 42 KiB is over the 32 KiB budget: 128 slots; 32-bit words fit 256
     assert plan.digits == 20 and g.keyswitch_hoist_sum_chunk(bits, 20, n_power) == (7 if bits == 64 else 8)
     check_against_the_composition(g, plan, st, np.random.default_rng(20 + bits), [(5, 3)])
+
+
+@pytest.mark.parametrize("bits", [64, 32])
+def test_many_digits_on_the_widest_primes(g, bits):
+    test_many_digits_force_a_small_chunk(g, bits, "wide")
 
 
 @pytest.mark.parametrize("bits", [64, 32])

@@ -192,12 +192,12 @@ _rings = {}
 
 
 class Ring:
-    """M NTT primes with their tables for one (bits, n_power), negacyclic: what the pipeline tests share"""
+    """M NTT primes of the given widths (cycled) with their tables for one (bits, n_power), negacyclic: what the
+    pipeline tests share"""
 
-    def __init__(self, g, bits, n_power, M):
-        widths = [(60, 59, 58, 57) if bits == 64 else (30, 29, 28, 27)][0]
+    def __init__(self, g, bits, n_power, M, widths):
         self.cases = [MergeCase(g, bits, n_power, g.X_N_plus, f)
-                      for f in distinct_factors_scaled([widths[i % 4] for i in range(M)], n_power)]
+                      for f in distinct_factors_scaled([widths[i % len(widths)] for i in range(M)], n_power)]
         n = 1 << n_power
         dt = g.np_dtype(bits)
         fwd, inv = np.zeros(M * n, dtype=dt), np.zeros(M * n, dtype=dt)
@@ -222,10 +222,14 @@ class Ring:
                     d_ninv=g.to_device(np.array(ninv, dtype=g.np_dtype(self.bits))))
 
 
-def ring(g, bits, n_power, M=8):
-    key = (bits, n_power, M)
+WIDTHS = {64: (60, 59, 58, 57), 32: (30, 29, 28, 27)}
+WIDE_WIDTHS = {64: (62, 61, 62, 60), 32: (30, 29, 30, 28)}  # the top of what Modulus<T> accepts
+
+
+def ring(g, bits, n_power, M=8, wide=False):
+    key = (bits, n_power, M, wide)
     if key not in _rings:
-        _rings[key] = Ring(g, bits, n_power, M)
+        _rings[key] = Ring(g, bits, n_power, M, (WIDE_WIDTHS if wide else WIDTHS)[bits])
     return _rings[key]
 
 
@@ -267,10 +271,10 @@ def scratch_for(plan, count, C, short=0):
 @pytest.mark.parametrize("bits", [64, 32])
 @pytest.mark.parametrize("n_power", [3, 9, 12])
 @pytest.mark.parametrize("L,K,alpha", [(3, 2, 2), (6, 2, 2)])
-def test_apply_equals_the_sequence_of_public_calls(g, bits, n_power, L, K, alpha):
+def test_apply_equals_the_sequence_of_public_calls(g, bits, n_power, L, K, alpha, wide=False):
     import torch
     M, n = L + K, 1 << n_power
-    st = ring(g, bits, n_power).sub(list(range(M)))
+    st = ring(g, bits, n_power, wide=wide).sub(list(range(M)))
     plan = make_plan(g, st, L, alpha, n_power, bits)
     inner = g.InnerProductPlan(st["moduli"], bits)
     D = plan.digits
@@ -299,6 +303,14 @@ def test_apply_equals_the_sequence_of_public_calls(g, bits, n_power, L, K, alpha
 
 
 @pytest.mark.parametrize("bits", [64, 32])
+@pytest.mark.parametrize("n_power", [3, 9, 12])
+@pytest.mark.parametrize("L,K,alpha", [(3, 2, 2), (6, 2, 2)])
+def test_apply_equals_the_sequence_of_public_calls_on_the_widest_primes(g, bits, n_power, L, K, alpha):
+    """primes of 62/61 and 30/29 bits: 2 q passes 2^(W-1)"""
+    test_apply_equals_the_sequence_of_public_calls(g, bits, n_power, L, K, alpha, wide=True)
+
+
+@pytest.mark.parametrize("bits", [64, 32])
 def test_a_lower_level_plan_uses_the_full_level_key_in_place(g, bits):
     """L = 4 of a key built for 6 + 2 limbs: key_mod_count = 8, key_limbs = [0, 1, 2, 3, 6, 7]"""
     import torch
@@ -321,7 +333,7 @@ def test_a_lower_level_plan_uses_the_full_level_key_in_place(g, bits):
 
 
 @pytest.mark.parametrize("bits", [64, 32])
-def test_it_really_switches_keys(g, bits):
+def test_it_really_switches_keys(g, bits, wide=False):
     """A noiseless switching key from s to s': key[d] = (-a_d s' + P g_d s, a_d), g_d = (Q / Q_d) [(Q / Q_d)^-1 mod Q_d].
     Then sum_d x'_d g_d = c (mod Q) whatever multiple of Q_d the approximate ModUp adds, the inner product is
     P (c s mod Q) (mod P Q) in the combination out_0 + out_1 s', and each centred ModDown is off by at most
@@ -329,7 +341,7 @@ def test_it_really_switches_keys(g, bits):
     import torch
     n_power, L, K, alpha, C = 5, 3, 2, 2, 2
     M, n = L + K, 1 << n_power
-    st = ring(g, bits, n_power).sub(list(range(M)))
+    st = ring(g, bits, n_power, wide=wide).sub(list(range(M)))
     full, qs, ps = st["moduli"], st["moduli"][:L], st["moduli"][L:]
     Q, P = math.prod(qs), math.prod(ps)
     plan = make_plan(g, st, L, alpha, n_power, bits)
@@ -377,6 +389,11 @@ def test_it_really_switches_keys(g, bits):
         plan.mod_down(acc, out, C)
         torch.cuda.synchronize()
         assert max(error_of(out)) <= bound, mode
+
+
+@pytest.mark.parametrize("bits", [64, 32])
+def test_it_really_switches_keys_on_the_widest_primes(g, bits):
+    test_it_really_switches_keys(g, bits, wide=True)
 
 
 def test_launches_scratch_workspace_and_count_zero(g):

@@ -1,5 +1,6 @@
 """Host side of KeySwitchPlan.rotate_hoisted (include/gpuntt/rns/key_switch.cuh), no GPU: the scratch size, the identity
-that lets the kernel fold c0 in before the ModDown, and the chunk property at every chunk size the kernel can choose."""
+that lets the kernel fold c0 in before the ModDown, the chunk property at every chunk size the kernel can choose, and the
+kernel's own text run on CPU threads under the sanitizers."""
 import math
 import os
 
@@ -120,3 +121,23 @@ def test_the_chunk_hook_is_read_back(g):
                 g.set_test_hook("keyswitch_hoist_chunk", bad)
     finally:
         g.set_test_hook("keyswitch_hoist_chunk", 0)
+
+
+def test_the_kernel_text_on_cpu_threads_under_the_sanitizers(tmp_path):
+    """tests/cpp/emulate_hoisted_rotation.cpp: the kern namespace of csrc/hoisted_rotation.hip compiled for the HOST (a
+    stand-alone program, one thread per lane) with AddressSanitizer and UBSan, against the definition in exact integers,
+    with moduli below 2^(W-3) and just below 2^(W-2) and with every operand word 2^W - 1 at 64 elements and 64 digits"""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, "gpu-ntt_amd", "csrc", "hoisted_rotation.hip")).read()
+    first, last = text.index("        constexpr int HOIST_NT"), text.index("    } // namespace kern")
+    (tmp_path / "kernel_extract.inc").write_text(text[first:last])
+    cpp = os.path.join(root, "tests", "cpp")
+    exe = str(tmp_path / "emulate_hoisted_rotation")
+    subprocess.check_call(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", "-pthread", "-I" + os.path.join(cpp, "host_shim"),
+                           "-I" + str(tmp_path), "-I" + os.path.join(root, "include"),
+                           "-I" + os.path.join(root, "gpu-ntt_amd", "csrc"),
+                           os.path.join(cpp, "emulate_hoisted_rotation.cpp"), "-o", exe], timeout=300)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
