@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "gpuntt/rns/base_conversion.cuh"
+#include "rns_arith.hpp"
 
 namespace gpuntt
 {
@@ -38,26 +39,7 @@ namespace gpuntt
             unsigned onep;   // [KP] floor(2^W / p_j): the Shoup companion of 1
         };
 
-        template <typename T> struct BcWide;
-        template <> struct BcWide<Data32>
-        {
-            using type = Data64;
-        };
-        template <> struct BcWide<Data64>
-        {
-            using type = unsigned __int128;
-        };
-
-        __device__ __forceinline__ Data32 bc_mulhi(Data32 a, Data32 b) { return __umulhi(a, b); }
-        __device__ __forceinline__ Data64 bc_mulhi(Data64 a, Data64 b) { return __umul64hi(a, b); }
-
-        // (x * w) mod m, canonical, for ANY word x, w < m < 2^(W-1) and wp = floor(w 2^W / m): the quotient estimate
-        // hi(x * wp) is floor(x w / m) or one less, so the remainder lies in [0, 2m)
-        template <typename T> __device__ __forceinline__ T bc_shoup(T x, T w, T wp, T m)
-        {
-            const T r = x * w - bc_mulhi(x, wp) * m;
-            return r >= m ? r - m : r;
-        }
+        // RnsWide, rns_mulhi, rns_shoup: rns_arith.hpp
 
         // the same as pointers into the workspace `base`, in the CONSTANT address space: nothing writes the workspace
         // while a conversion runs, and a load from that address space at a wave-uniform address is a scalar load
@@ -98,7 +80,7 @@ namespace gpuntt
                                                               unsigned long long total, BcStrides<STRIDED> strides)
         {
             const BcConsts<T> k(consts, off);
-            using W2 = typename BcWide<T>::type;
+            using W2 = typename RnsWide<T>::type;
             constexpr int W = static_cast<int>(8 * sizeof(T));
             extern __shared__ __align__(16) unsigned char bc_smem[];
             T* ys = reinterpret_cast<T*>(bc_smem) + threadIdx.x;
@@ -118,7 +100,7 @@ namespace gpuntt
             for (int i = 0; i < L; i++)
             {
                 const T q = k.q[i];
-                const T y = bc_shoup<T>(src[static_cast<unsigned long long>(i) << n_power], k.w[i], k.wp[i], q);
+                const T y = rns_shoup<T>(src[static_cast<unsigned long long>(i) << n_power], k.w[i], k.wp[i], q);
                 ys[i * BC_NT] = y;
                 if constexpr (CENTRED)
                 {
@@ -181,9 +163,9 @@ namespace gpuntt
                     if (j < K)
                     {
                         const T p = k.p[j];
-                        T r = bc_shoup<T>(static_cast<T>(acc[b] >> W), k.t1[j], k.t1p[j], p);
-                        r += bc_shoup<T>(carry[b], k.t2[j], k.t2p[j], p);
-                        r += bc_shoup<T>(static_cast<T>(acc[b]), T(1), k.onep[j], p); // r < 3 p < 2^W
+                        T r = rns_shoup<T>(static_cast<T>(acc[b] >> W), k.t1[j], k.t1p[j], p);
+                        r += rns_shoup<T>(carry[b], k.t2[j], k.t2p[j], p);
+                        r += rns_shoup<T>(static_cast<T>(acc[b]), T(1), k.onep[j], p); // r < 3 p < 2^W
                         r = r >= p ? r - p : r;
                         r = r >= p ? r - p : r;
                         const unsigned long long o = obase + (static_cast<unsigned long long>(j) << n_power);
@@ -192,7 +174,7 @@ namespace gpuntt
                             const T cj = c_in[cbase + (static_cast<unsigned long long>(j) << n_power)];
                             // c - conv as a word that is congruent to it: any word c is read modulo p
                             const T d = cj >= r ? cj - r : cj + (p - r);
-                            r = bc_shoup<T>(d, k.qinv[j], k.qinvp[j], p);
+                            r = rns_shoup<T>(d, k.qinv[j], k.qinvp[j], p);
                         }
                         out[o] = r;
                     }

@@ -14,6 +14,7 @@
 #include "gpuntt/rns/inner_product.cuh"
 #include "gpuntt/rns/key_switch.cuh"
 #include "gpuntt_c.h"
+#include "hoisted_rotation_internal.hpp"
 #include "test_hooks.h"
 
 namespace gpuntt
@@ -27,8 +28,6 @@ namespace gpuntt
         void launch_log_start();
         std::string launch_log_take();
         void scratch_stats(unsigned long long out[6]);
-        int hoist_chunk_log(size_t word_bytes, int D, int n_power); // hoisted_rotation.hip
-        int hoist_sum_chunk_log(size_t word_bytes, int D, int n_power); // hoisted_sum.hip
     } // namespace host
 } // namespace gpuntt
 
@@ -522,14 +521,14 @@ extern "C"
         if ((word_bytes != 4 && word_bytes != 8) || digits < 1 || digits > INNERPROD_MAX_DIGITS || n_power < 1 ||
             n_power > 28)
             return -1;
-        return host::hoist_chunk_log(static_cast<size_t>(word_bytes), digits, n_power);
+        return host::hoist_chunk_log(static_cast<size_t>(word_bytes), digits, n_power, host::HOIST_LOG_MAX);
     }
     int gpuntt_test_keyswitch_hoist_sum_chunk(int word_bytes, int digits, int n_power)
     {
         if ((word_bytes != 4 && word_bytes != 8) || digits < 1 || digits > INNERPROD_MAX_DIGITS || n_power < 1 ||
             n_power > 28)
             return -1;
-        return host::hoist_sum_chunk_log(static_cast<size_t>(word_bytes), digits, n_power);
+        return host::hoist_chunk_log(static_cast<size_t>(word_bytes), digits, n_power, host::HOIST_SUM_LOG_MAX);
     }
 
     int gpuntt_galois_element_u32(int steps, int n_power, int conjugation, uint32_t* elt_host)

@@ -1,5 +1,6 @@
 // hoisted_rotation_internal.hpp -- what key_switch.hip needs of hoisted_rotation.hip: the kernel arguments of one
-// rotate_hoisted call and the launcher of inner_product_galois.
+// rotate_hoisted or rotate_hoisted_sum call, the chunk rule and the launchers of inner_product_galois and
+// inner_product_galois_sum.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -26,20 +27,37 @@ namespace gpuntt
             unsigned char limb[INNERPROD_MAX_MODULI]; // the key limb of every modulus of the full base
             int count;                               // G
         };
+
+        // HoistArgs plus the G weight pointers, still ONE kernel argument: 2632 bytes for u64, 2120 for u32, inside the
+        // 4 KiB argument segment with the kernel's other 72 bytes
+        template <typename T> struct HoistSumArgs
+        {
+            HoistArgs<T> h;
+            const T* weight[GALOIS_MAX_COUNT]; // pt_g: T[M][N] over the full base, or nullptr (weight 1)
+        };
+        static_assert(sizeof(HoistSumArgs<Data64>) == 2632 && sizeof(HoistSumArgs<Data32>) == 2120,
+                      "HoistSumArgs has to stay inside the 4 KiB argument segment");
     } // namespace kern
 
     namespace host
     {
-        // log2 of the chunk of inner_product_galois for words of `word_bytes`, D digits and a ring of 2^n_power: the
-        // largest power of two with (D + 1) chunk word_bytes inside the LDS budget, at least 64 slots, at most N; the
-        // test hook keyswitch_hoist_chunk replaces the budget rule (not the cap at N)
-        int hoist_chunk_log(size_t word_bytes, int D, int n_power);
+        constexpr int HOIST_LOG_MAX = 13;    // inner_product_galois: lanes walk the chunk, any chunk the hook can name
+        constexpr int HOIST_SUM_LOG_MAX = 8; // inner_product_galois_sum: one slot per lane, at most 256 lanes
+
+        // log2 of the chunk for words of `word_bytes`, D digits and a ring of 2^n_power: the largest power of two with
+        // (D + 1) chunk word_bytes inside the LDS budget, at least 64 slots, at most 2^max_log and at most N.  The test
+        // hook keyswitch_hoist_chunk replaces the budget rule (not the caps at N, at 2^max_log and at 64 KiB of LDS)
+        int hoist_chunk_log(size_t word_bytes, int D, int n_power, int max_log);
         void keyswitch_set_hoist_chunk(int v); // test hook: 0 = the rule above, 6 .. 13 = log2 of the chunk
 
-        // a: T[D][count][M][N], c0: T[count][L][N] or nullptr, acc: T[G][2][count][M][N]; consts: the workspace image of
-        // InnerProductPlan for the M moduli.  One launch; throws std::invalid_argument beyond the grid limits
+        // a: T[D][count][M][N], c0: T[count][L][N] or nullptr; consts: the workspace image of InnerProductPlan for the M
+        // moduli.  acc: T[G][2][count][M][N] (hoist_launch) or T[2][count][M][N] (hoist_sum_launch).  One launch; throws
+        // std::invalid_argument beyond the grid limits
         template <typename T>
         void hoist_launch(const T* a, const T* c0, T* acc, const T* consts, const kern::HoistArgs<T>& args, int D,
                           int count, int L, int M, int KM, int n_power, bool negacyclic, hipStream_t stream);
+        template <typename T>
+        void hoist_sum_launch(const T* a, const T* c0, T* acc, const T* consts, const kern::HoistSumArgs<T>& args, int D,
+                              int count, int L, int M, int KM, int n_power, bool negacyclic, hipStream_t stream);
     } // namespace host
 } // namespace gpuntt

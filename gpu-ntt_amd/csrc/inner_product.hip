@@ -33,7 +33,7 @@ namespace gpuntt
         // 8 (r, c) pairs are what the register file holds at 3 waves per SIMD for u64
         constexpr int ip_block(int C) { return C <= 2 ? 4 : 2; }
 
-        // IpLimbs, IpWide, ip_mulhi, ip_addc, ip_shoup, IpAcc, IpFold: inner_product_internal.hpp
+        // IpLimbs, ip_addc, IpAcc, IpFold: inner_product_internal.hpp; RnsWide, rns_shoup: rns_arith.hpp
 
         // the plan's constants in the workspace: six arrays of M words (q, 2^W mod q and its Shoup companion, 2^2W mod q
         // and its companion, the companion of 1), read through the CONSTANT address space -- nothing writes the workspace

@@ -1,11 +1,13 @@
 // inner_product_internal.hpp -- the device arithmetic of the RNS inner product, shared by inner_product.hip and
-// hoisted_rotation.hip (the inner product that permutes while it multiplies): the exact three-word accumulator, the Shoup
-// product and the three-product fold.  One copy, so both kernels compute the same words.
+// hoisted_rotation.hip (the inner products that permute while they multiply): the exact three-word accumulator and the
+// three-product fold, over the Shoup product of rns_arith.hpp.  One copy, so all kernels compute the same words (DESIGN.md
+// 3.11, 3.13).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "gpuntt/rns/inner_product.cuh"
+#include "rns_arith.hpp"
 
 namespace gpuntt
 {
@@ -17,18 +19,8 @@ namespace gpuntt
             unsigned char v[INNERPROD_MAX_MODULI];
         };
 
-        template <typename T> struct IpWide;
-        template <> struct IpWide<Data32>
-        {
-            using type = Data64;
-        };
-        template <> struct IpWide<Data64>
-        {
-            using type = unsigned __int128;
-        };
+        // RnsWide, rns_mulhi, rns_shoup: rns_arith.hpp
 
-        __device__ __forceinline__ Data32 ip_mulhi(Data32 a, Data32 b) { return __umulhi(a, b); }
-        __device__ __forceinline__ Data64 ip_mulhi(Data64 a, Data64 b) { return __umul64hi(a, b); }
         __device__ __forceinline__ Data32 ip_addc(Data32 a, Data32 b, Data32 cin, Data32* cout)
         {
             return __builtin_addc(a, b, cin, cout);
@@ -38,13 +30,6 @@ namespace gpuntt
             return __builtin_addcl(a, b, cin, cout);
         }
 
-        // (x * w) mod m, canonical, for ANY word x, w < m < 2^(W-1) and wp = floor(w 2^W / m) (base_conversion.hip)
-        template <typename T> __device__ __forceinline__ T ip_shoup(T x, T w, T wp, T m)
-        {
-            const T r = x * w - ip_mulhi(x, wp) * m;
-            return r >= m ? r - m : r;
-        }
-
         template <typename T> struct IpAcc
         {
             T lo, hi;
@@ -52,7 +37,7 @@ namespace gpuntt
             // += x * y, exact
             __device__ __forceinline__ void mac(T x, T y)
             {
-                using W2 = typename IpWide<T>::type;
+                using W2 = typename RnsWide<T>::type;
                 const W2 p = static_cast<W2>(x) * y;
                 T k0, k1;
                 lo = ip_addc(lo, static_cast<T>(p), T(0), &k0);
@@ -77,9 +62,9 @@ namespace gpuntt
             // (h [2^W]_q + c [2^2W]_q + l), three exact Shoup products, each canonical: the sum is below 3 q < 2^W
             __device__ __forceinline__ T sum(const IpAcc<T>& s) const
             {
-                T x = ip_shoup<T>(s.hi, t1, t1p, q);
-                x += ip_shoup<T>(static_cast<T>(s.carry), t2, t2p, q);
-                x += ip_shoup<T>(s.lo, T(1), onep, q);
+                T x = rns_shoup<T>(s.hi, t1, t1p, q);
+                x += rns_shoup<T>(static_cast<T>(s.carry), t2, t2p, q);
+                x += rns_shoup<T>(s.lo, T(1), onep, q);
                 return x;
             }
             // x < 3 q -> x mod q

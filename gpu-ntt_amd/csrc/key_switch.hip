@@ -21,13 +21,14 @@
 // the inner product left them, inside the M-limb stacks.  The strides are a compile-time form of the kernel, so the dense
 // instantiations behind BaseConvPlan keep their registers.
 //
-// rotate_hoisted: inner_product_galois of hoisted_rotation.hip (the inner product that permutes while it multiplies, all
-// G elements in one launch), then the plan's own full-base INTT, mod_down and q-base NTT over G * 2 * count stacks
-// (DESIGN.md 3.13).
+// Every switch ends in Impl::finish: the plan's own full-base INTT, mod_down and the optional q-base NTT.
 //
-// rotate_hoisted_sum: inner_product_galois_sum of hoisted_sum.hip (the same inner product, weighted and summed over the G
-// elements in the extended base), then ONE full-base INTT, mod_down and q-base NTT over 2 * count stacks whatever G is
-// (DESIGN.md 3.14).
+// rotate_hoisted: inner_product_galois of hoisted_rotation.hip (the inner product that permutes while it multiplies, all
+// G elements in one launch), then finish over G * 2 * count stacks.
+//
+// rotate_hoisted_sum: inner_product_galois_sum of hoisted_rotation.hip (the same inner product, weighted and summed over
+// the G elements in the extended base), then finish over 2 * count stacks whatever G is.  The two share
+// Impl::hoist_prepare: every refusal of the call and the kernel arguments.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,7 +42,6 @@
 #include "gpuntt/ntt_merge/ntt.cuh"
 #include "gpuntt/rns/key_switch.cuh"
 #include "hoisted_rotation_internal.hpp"
-#include "hoisted_sum_internal.hpp"
 #include "launch.hpp"
 
 namespace gpuntt
@@ -52,7 +52,7 @@ namespace gpuntt
         constexpr int KS_KB = 4;      // moduli per pass over the y_i of a digit
         constexpr size_t KS_LDS = 65536;
 
-        // BcWide, bc_shoup, BC_CHUNK: base_conversion_internal.hpp
+        // RnsWide, rns_shoup: rns_arith.hpp; BC_CHUNK: base_conversion_internal.hpp
 
         // where the ModUp constants lie in the workspace, in words; MP = M rounded up to KS_KB (padding: zero)
         struct KsOffsets
@@ -92,7 +92,7 @@ namespace gpuntt
                                                            unsigned long long total, unsigned long long digit_stride)
         {
             const KsConsts<T> k(consts, off);
-            using W2 = typename BcWide<T>::type;
+            using W2 = typename RnsWide<T>::type;
             constexpr int W = static_cast<int>(8 * sizeof(T));
             extern __shared__ __align__(16) unsigned char ks_smem[];
             const int nt = static_cast<int>(blockDim.x);
@@ -109,8 +109,8 @@ namespace gpuntt
             {
                 const T q = k.q[i];
                 const T x = src[static_cast<unsigned long long>(i) << n_power];
-                ys[i * nt] = bc_shoup<T>(x, k.w[i], k.wp[i], q);
-                cs[i * nt] = bc_shoup<T>(x, T(1), k.onep[i], q);
+                ys[i * nt] = rns_shoup<T>(x, k.w[i], k.wp[i], q);
+                cs[i * nt] = rns_shoup<T>(x, T(1), k.onep[i], q);
             }
 
             const unsigned long long abase = ((e * static_cast<unsigned>(M)) << n_power) + col;
@@ -191,9 +191,9 @@ namespace gpuntt
                         else
                         {
                             const T p = k.mod[m];
-                            r = bc_shoup<T>(static_cast<T>(acc[b] >> W), k.t1[m], k.t1p[m], p);
-                            r += bc_shoup<T>(carry[b], k.t2[m], k.t2p[m], p);
-                            r += bc_shoup<T>(static_cast<T>(acc[b]), T(1), k.onep[m], p); // r < 3 p < 2^W
+                            r = rns_shoup<T>(static_cast<T>(acc[b] >> W), k.t1[m], k.t1p[m], p);
+                            r += rns_shoup<T>(carry[b], k.t2[m], k.t2p[m], p);
+                            r += rns_shoup<T>(static_cast<T>(acc[b]), T(1), k.onep[m], p); // r < 3 p < 2^W
                             r = r >= p ? r - p : r;
                             r = r >= p ? r - p : r;
                         }
@@ -449,9 +449,7 @@ namespace gpuntt
         // the scratch of rotate_hoisted_sum, in bytes: the accumulators T[2][count][M][N], whatever G is
         template <typename T> size_t ks_hoisted_sum_scratch(int M, int n_power, int count)
         {
-            if (count < 0)
-                throw std::invalid_argument("Invalid count!");
-            return ks_align((static_cast<size_t>(count) << n_power) * sizeof(T) * M * 2);
+            return ks_hoisted_scratch<T>(M, n_power, count, 1);
         }
     } // namespace
 
@@ -563,22 +561,34 @@ namespace gpuntt
             // a or key overlapping the accumulators in the scratch: refused by the inner product's own check of its
             // output against its inputs, before its launch -- the first of this call
             inner->multiply_accumulate(a, key, acc, n, D, C, count, false, KM, limbs.data(), stream);
-            ntt_full_i->execute(acc, acc, C * count * M, stream);
-            mod_down(acc, out, C * count, stream);
-            if (output_ntt)
-                ntt_q_f->execute(out, out, C * count * L, stream);
+            finish(acc, out, C * count, output_ntt, stream);
         }
 
-        void rotate_hoisted(const T* a, const T* c0, const T* const* keys, const std::uint32_t* elts, int G, T* out,
-                            int count, bool output_ntt, void* scratch, hipStream_t stream) const
+        // the tail of every switch: acc T[stacks][M][N] in the NTT domain -> out T[stacks][L][N]
+        void finish(T* acc, T* out, int stacks, bool output_ntt, hipStream_t stream) const
+        {
+            ntt_full_i->execute(acc, acc, stacks * M, stream);
+            mod_down(acc, out, stacks, stream);
+            if (output_ntt)
+                ntt_q_f->execute(out, out, stacks * L, stream);
+        }
+
+        // What rotate_hoisted (groups = G, no weights) and rotate_hoisted_sum (groups = 1) share up to the launch: every
+        // refusal of the call, in one order, and the kernel arguments.  out: T[groups][2][count][L][N], the scratch:
+        // T[groups][2][count][M][N]; weights: G device pointers (each may be null) or null.  Returns the stacks the tail
+        // runs over, 2 * groups * count; 0: count is 0 and nothing is to be launched
+        int hoist_prepare(const T* a, const T* c0, const T* const* keys, const std::uint32_t* elts,
+                          const T* const* weights, int G, int groups, const T* out, int count, const void* scratch,
+                          kern::HoistArgs<T>& args) const
         {
             need_transforms();
-            const size_t acc_bytes = ks_hoisted_scratch<T>(M, n, count, G); // checks count and G
+            const size_t acc_bytes = ks_hoisted_scratch<T>(M, n, count, groups); // checks count (and G = groups)
+            if (G < 1 || G > GALOIS_MAX_COUNT)
+                throw std::invalid_argument("Invalid galois_count!");
             if (a == nullptr || keys == nullptr || elts == nullptr || out == nullptr || scratch == nullptr)
                 throw std::invalid_argument("null pointer argument");
             if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
                 throw std::invalid_argument("The scratch is not 256-byte aligned!");
-            kern::HoistArgs<T> args{};
             args.count = G;
             const std::uint32_t mask = negacyclic ? (2u << n) - 1u : (1u << n) - 1u; // as GPU_Automorphism_NTT reduces
             for (int g = 0; g < G; g++)
@@ -595,73 +605,10 @@ namespace gpuntt
             for (int j = 0; j < L; j++)
                 args.p_mod_q[j] = p_mod_q[j], args.p_mod_q_shoup[j] = p_mod_q_shoup[j];
             if (count == 0)
-                return;
+                return 0;
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
             const std::uint64_t a_bytes = cols * M * D * sizeof(T), c0_bytes = cols * L * sizeof(T);
-            const std::uint64_t out_bytes = cols * L * 2 * G * sizeof(T);
-            const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
-            for (const auto& w : {std::pair<const void*, std::uint64_t>{out, out_bytes}, {scratch, acc_bytes}})
-            {
-                bool hit = ks_overlap(w.first, w.second, a, a_bytes) ||
-                           (c0 != nullptr && ks_overlap(w.first, w.second, c0, c0_bytes));
-                for (int g = 0; g < G; g++)
-                    hit = hit || ks_overlap(w.first, w.second, keys[g], key_bytes);
-                if (hit)
-                    throw std::invalid_argument("out or the scratch overlaps an operand!");
-            }
-            if (ks_overlap(out, out_bytes, scratch, acc_bytes))
-                throw std::invalid_argument("The scratch overlaps out!");
-            const unsigned long long stacks = 2ull * static_cast<unsigned long long>(G) * static_cast<unsigned>(count);
-            if (stacks * static_cast<unsigned>(M) > 0x7FFFFFFFull) // the batch of the transforms is an int
-                throw std::invalid_argument("Invalid count!");
-            // mod_down's own grid limit, checked before the first launch
-            if ((((stacks << n) + kern::BC_NT - 1) / kern::BC_NT) * kern::BC_NT > 0xFFFFFFFFull)
-                throw std::invalid_argument("Invalid count!");
-            T* acc = static_cast<T*>(scratch);
-            // the first launch of the call: its own grid check throws before it
-            host::hoist_launch<T>(a, c0, acc, reinterpret_cast<const T*>(ws + lay.inner), args, D, count, L, M, KM, n,
-                                  negacyclic, stream);
-            const int s = static_cast<int>(stacks);
-            ntt_full_i->execute(acc, acc, s * M, stream);
-            mod_down(acc, out, s, stream);
-            if (output_ntt)
-                ntt_q_f->execute(out, out, s * L, stream);
-        }
-
-        void rotate_hoisted_sum(const T* a, const T* c0, const T* const* keys, const std::uint32_t* elts,
-                                const T* const* weights, int G, T* out, int count, bool output_ntt, void* scratch,
-                                hipStream_t stream) const
-        {
-            need_transforms();
-            const size_t acc_bytes = ks_hoisted_sum_scratch<T>(M, n, count); // checks count
-            if (G < 1 || G > GALOIS_MAX_COUNT)
-                throw std::invalid_argument("Invalid galois_count!");
-            if (a == nullptr || keys == nullptr || elts == nullptr || out == nullptr || scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
-            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
-            kern::HoistSumArgs<T> args{};
-            args.h.count = G;
-            const std::uint32_t mask = negacyclic ? (2u << n) - 1u : (1u << n) - 1u; // as GPU_Automorphism_NTT reduces
-            for (int g = 0; g < G; g++)
-            {
-                const std::uint32_t k = elts[g] & mask;
-                if ((k & 1u) == 0u)
-                    throw std::invalid_argument("Invalid Galois element (must be odd)!");
-                if (keys[g] == nullptr)
-                    throw std::invalid_argument("null pointer argument");
-                args.h.elt[g] = k, args.h.inv[g] = galois_inverse(k) & mask, args.h.key[g] = keys[g];
-                args.weight[g] = weights != nullptr ? weights[g] : nullptr;
-            }
-            for (int m = 0; m < M; m++)
-                args.h.limb[m] = static_cast<unsigned char>(limbs[m]);
-            for (int j = 0; j < L; j++)
-                args.h.p_mod_q[j] = p_mod_q[j], args.h.p_mod_q_shoup[j] = p_mod_q_shoup[j];
-            if (count == 0)
-                return;
-            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
-            const std::uint64_t a_bytes = cols * M * D * sizeof(T), c0_bytes = cols * L * sizeof(T);
-            const std::uint64_t out_bytes = cols * L * 2 * sizeof(T);
+            const std::uint64_t out_bytes = cols * L * 2 * groups * sizeof(T);
             const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
             const std::uint64_t weight_bytes = (static_cast<std::uint64_t>(M) << n) * sizeof(T);
             for (const auto& w : {std::pair<const void*, std::uint64_t>{out, out_bytes}, {scratch, acc_bytes}})
@@ -670,27 +617,51 @@ namespace gpuntt
                            (c0 != nullptr && ks_overlap(w.first, w.second, c0, c0_bytes));
                 for (int g = 0; g < G; g++)
                     hit = hit || ks_overlap(w.first, w.second, keys[g], key_bytes) ||
-                          (args.weight[g] != nullptr && ks_overlap(w.first, w.second, args.weight[g], weight_bytes));
+                          (weights != nullptr && weights[g] != nullptr &&
+                           ks_overlap(w.first, w.second, weights[g], weight_bytes));
                 if (hit)
                     throw std::invalid_argument("out or the scratch overlaps an operand!");
             }
             if (ks_overlap(out, out_bytes, scratch, acc_bytes))
                 throw std::invalid_argument("The scratch overlaps out!");
-            const unsigned long long stacks = 2ull * static_cast<unsigned>(count);
+            const unsigned long long stacks = 2ull * static_cast<unsigned>(groups) * static_cast<unsigned>(count);
             if (stacks * static_cast<unsigned>(M) > 0x7FFFFFFFull) // the batch of the transforms is an int
                 throw std::invalid_argument("Invalid count!");
             // mod_down's own grid limit, checked before the first launch
             if ((((stacks << n) + kern::BC_NT - 1) / kern::BC_NT) * kern::BC_NT > 0xFFFFFFFFull)
                 throw std::invalid_argument("Invalid count!");
+            return static_cast<int>(stacks);
+        }
+
+        void rotate_hoisted(const T* a, const T* c0, const T* const* keys, const std::uint32_t* elts, int G, T* out,
+                            int count, bool output_ntt, void* scratch, hipStream_t stream) const
+        {
+            kern::HoistArgs<T> args{};
+            const int stacks = hoist_prepare(a, c0, keys, elts, nullptr, G, G, out, count, scratch, args);
+            if (stacks == 0)
+                return;
+            T* acc = static_cast<T*>(scratch);
+            // the first launch of the call: its own grid check throws before it
+            host::hoist_launch<T>(a, c0, acc, reinterpret_cast<const T*>(ws + lay.inner), args, D, count, L, M, KM, n,
+                                  negacyclic, stream);
+            finish(acc, out, stacks, output_ntt, stream);
+        }
+
+        void rotate_hoisted_sum(const T* a, const T* c0, const T* const* keys, const std::uint32_t* elts,
+                                const T* const* weights, int G, T* out, int count, bool output_ntt, void* scratch,
+                                hipStream_t stream) const
+        {
+            kern::HoistSumArgs<T> args{};
+            const int stacks = hoist_prepare(a, c0, keys, elts, weights, G, 1, out, count, scratch, args.h);
+            if (stacks == 0)
+                return;
+            for (int g = 0; g < G && weights != nullptr; g++)
+                args.weight[g] = weights[g];
             T* acc = static_cast<T*>(scratch);
             // the first launch of the call: its own grid check throws before it
             host::hoist_sum_launch<T>(a, c0, acc, reinterpret_cast<const T*>(ws + lay.inner), args, D, count, L, M, KM, n,
                                       negacyclic, stream);
-            const int s = static_cast<int>(stacks);
-            ntt_full_i->execute(acc, acc, s * M, stream);
-            mod_down(acc, out, s, stream);
-            if (output_ntt)
-                ntt_q_f->execute(out, out, s * L, stream);
+            finish(acc, out, stacks, output_ntt, stream);
         }
     };
 

@@ -632,7 +632,6 @@ namespace gpuntt
         void baseconv_set_ksplit(int v); // base_conversion.hip
         void keyswitch_set_split(int v); // key_switch.hip
         void keyswitch_set_hoist_chunk(int v); // hoisted_rotation.hip
-        void keyswitch_set_hoist_sum_chunk(int v); // hoisted_sum.hip
         namespace
         {
             struct OptionValues
@@ -718,8 +717,8 @@ namespace gpuntt
                 else if (test_hooks && k == "keyswitch_hoist_chunk" && is_num && (lv == 0 || (lv >= 6 && lv <= 13)))
                     // hoisted_rotation.hip: log2 of the source chunk of inner_product_galois, 0 = its LDS budget rule;
                     // like keyswitch_split a process-wide knob outside the per-call snapshot that changes no output word.
-                    // hoisted_sum.hip: the same value forces the destination chunk of inner_product_galois_sum
-                    keyswitch_set_hoist_chunk(iv), keyswitch_set_hoist_sum_chunk(iv);
+                    // The same value forces the destination chunk of inner_product_galois_sum, inside its cap of 256 slots
+                    keyswitch_set_hoist_chunk(iv);
                 else if (test_hooks && k == "reset_predictions" && bit)
                     g_reset_predictions.store(1, std::memory_order_relaxed); // rns_guess forgets every stack it has seen
                 else

@@ -11,8 +11,9 @@
  *       two_sweep_big = 0 | 1    experiment: 64-bit rings 2^23 / 2^24 forward in two sweeps on 16384-coefficient tiles
  *       baseconv_ksplit = 0..16  base conversion: workgroups per column tile that share its outputs (0: the library's choice)
  *       keyswitch_split = 0..64  key switching: workgroups per column tile that share the (digit, block) pairs of the ModUp
- *       keyswitch_hoist_chunk = 0 | 6..13  rotate_hoisted: log2 of the slots of a source chunk of inner_product_galois
- *                                (0: the LDS budget rule; a forced chunk is still capped at N and at what LDS can hold)
+ *       keyswitch_hoist_chunk = 0 | 6..13  rotate_hoisted / rotate_hoisted_sum: log2 of the slots of a chunk of the two kernels
+ *                                of hoisted_rotation.hip (0: the LDS budget rule; a forced chunk is still capped at N, at what
+ *                                LDS can hold and, for inner_product_galois_sum, at 256 slots)
  *       reset_predictions = 1    the family prediction of the RNS overloads forgets every stack it has seen
  *   gpuntt_test_launch_log_start()      start recording the kernel of every launch the library enqueues (all threads)
  *   gpuntt_test_launch_log_take(buf, n) stop; the kernels since start, space-separated ("prep_twiddles merge_pass_lazy:31 ..."),
@@ -23,8 +24,8 @@
  *   gpuntt_test_keyswitch_hoist_chunk(word_bytes, digits, n_power)  host only: log2 of the chunk inner_product_galois takes
  *                                       for this word size, D and ring under the hook's current value; -1: bad argument
  *   gpuntt_test_keyswitch_hoist_sum_chunk(word_bytes, digits, n_power)  the same for the destination chunk of
- *                                       inner_product_galois_sum (rotate_hoisted_sum): its own rule -- one slot per lane, at
- *                                       most 256 slots -- which the hook keyswitch_hoist_chunk forces as well, inside that cap
+ *                                       inner_product_galois_sum (rotate_hoisted_sum): the same rule capped at one slot per
+ *                                       lane, 256 slots, which the hook keyswitch_hoist_chunk forces as well, inside that cap
  * Options are snapshot once per API call (prep.hip), so a hook set while another thread's call is in flight does not change
  * that call. */
 #ifndef GPUNTT_TEST_HOOKS_H

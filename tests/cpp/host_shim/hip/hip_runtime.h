@@ -1,5 +1,5 @@
 // host_shim/hip/hip_runtime.h -- NOT the HIP runtime: the few names a kernel's text needs to compile for the HOST, so that
-// tests/cpp/emulate_hoisted_sum.cpp and emulate_hoisted_rotation.cpp can run it on CPU threads under AddressSanitizer.
+// tests/cpp/emulate_hoisted.cpp can run it on CPU threads under AddressSanitizer.
 // One workgroup = one std::thread per lane, __syncthreads = a std::barrier; threadIdx / blockIdx / blockDim are thread-local.  Put this directory in
 // front of the include path of a plain clang++ (never hipcc).
 #pragma once

@@ -207,7 +207,7 @@ def largest_sum_operands(fill):
 def test_the_largest_sums_the_contract_allows(g, kernel, L, K, alpha, G, fill, kind, bits):
     """across digits: D = 63 products per three-word accumulator, M = 64 limbs; across elements: G = 64, for the sum 64
     products of the unreduced fold sum (below 3 q) with a weight word 2^W - 1 in the second pair of accumulators --
-    "at most 64 terms leave the carry word at 64" (csrc/hoisted_sum.hip)"""
+    "at most 64 terms leave the carry word at 64" (csrc/hoisted_rotation.hip)"""
     c = whole(g, bits, 6, L, K, alpha, kind, None, G, 1, host=largest_sum_operands(fill))
     assert c.D == (63 if L == 63 else 2)
     assert c.KM == c.M

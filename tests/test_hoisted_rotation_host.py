@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from innerprod_utils import from_words, moduli, random_words, words
+from hoisted_emulator import run_emulator
 from keyswitch_utils import ref_mod_down
 
 
@@ -124,20 +125,8 @@ def test_the_chunk_hook_is_read_back(g):
 
 
 def test_the_kernel_text_on_cpu_threads_under_the_sanitizers(tmp_path):
-    """tests/cpp/emulate_hoisted_rotation.cpp: the kern namespace of csrc/hoisted_rotation.hip compiled for the HOST (a
+    """tests/cpp/emulate_hoisted.cpp rotation: the kern namespace of csrc/hoisted_rotation.hip compiled for the HOST (a
     stand-alone program, one thread per lane) with AddressSanitizer and UBSan, against the definition in exact integers,
     with moduli below 2^(W-3) and just below 2^(W-2) and with every operand word 2^W - 1 at 64 elements and 64 digits"""
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = open(os.path.join(root, "gpu-ntt_amd", "csrc", "hoisted_rotation.hip")).read()
-    first, last = text.index("        constexpr int HOIST_NT"), text.index("    } // namespace kern")
-    (tmp_path / "kernel_extract.inc").write_text(text[first:last])
-    cpp = os.path.join(root, "tests", "cpp")
-    exe = str(tmp_path / "emulate_hoisted_rotation")
-    subprocess.check_call(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-pthread", "-I" + os.path.join(cpp, "host_shim"),
-                           "-I" + str(tmp_path), "-I" + os.path.join(root, "include"),
-                           "-I" + os.path.join(root, "gpu-ntt_amd", "csrc"),
-                           os.path.join(cpp, "emulate_hoisted_rotation.cpp"), "-o", exe], timeout=300)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+    out = run_emulator(tmp_path, "rotation")
+    assert out.count("rotation W=") == 40 and "sum W=" not in out  # 10 cases, two widths of the moduli, u64 and u32

@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from hoisted_emulator import run_emulator
+
 
 @pytest.fixture(scope="module")
 def g(pkg):
@@ -133,19 +135,7 @@ def test_every_destination_chunk_has_one_source_chunk_per_element(g, poly):
 
 
 def test_the_kernel_text_on_cpu_threads_under_the_sanitizers(tmp_path):
-    """tests/cpp/emulate_hoisted_sum.cpp: the kern namespace of csrc/hoisted_sum.hip compiled for the HOST (a stand-alone
-    program, one thread per lane) with AddressSanitizer and UBSan, against the definition in exact integers"""
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = open(os.path.join(root, "gpu-ntt_amd", "csrc", "hoisted_sum.hip")).read()
-    first, last = text.index("        constexpr int HSUM_NT"), text.index("    } // namespace kern")
-    (tmp_path / "kernel_extract.inc").write_text(text[first:last])
-    cpp = os.path.join(root, "tests", "cpp")
-    exe = str(tmp_path / "emulate_hoisted_sum")
-    subprocess.check_call(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-pthread", "-I" + os.path.join(cpp, "host_shim"),
-                           "-I" + str(tmp_path), "-I" + os.path.join(root, "include"),
-                           "-I" + os.path.join(root, "gpu-ntt_amd", "csrc"),
-                           os.path.join(cpp, "emulate_hoisted_sum.cpp"), "-o", exe], timeout=300)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+    """tests/cpp/emulate_hoisted.cpp sum: the kern namespace of csrc/hoisted_rotation.hip compiled for the HOST (a
+    stand-alone program, one thread per lane) with AddressSanitizer and UBSan, against the definition in exact integers"""
+    out = run_emulator(tmp_path, "sum")
+    assert out.count("sum W=") == 34 and "rotation W=" not in out  # 17 cases, u64 and u32
