@@ -114,7 +114,8 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "keyswitch_plan_mod_up", "keyswitch_plan_mod_down", "keyswitch_plan_decompose",
               "keyswitch_plan_switch_digits", "keyswitch_plan_apply", "keyswitch_plan_hoisted_scratch_bytes",
               "keyswitch_plan_rotate_hoisted", "keyswitch_plan_hoisted_sum_scratch_bytes",
-              "keyswitch_plan_rotate_hoisted_sum", "keyswitch_plan_owns_workspace",
+              "keyswitch_plan_rotate_hoisted_sum", "keyswitch_plan_multiply_relinearize",
+              "keyswitch_plan_owns_workspace",
               "keyswitch_plan_destroy", "keyswitch_constants", "keyswitch_reference_mod_up",
               "keyswitch_reference_mod_down")
     for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option", "gpuntt_galois_element_u32",
@@ -1188,6 +1189,26 @@ class KeySwitchPlan:
         fn = getattr(load_library(), "gpuntt_keyswitch_plan_rotate_hoisted_sum_u%d" % self.bits)
         _check(fn(self._h, _ptr(a), _ptr(c0), key_ptrs, elts, weight_ptrs, G, _ptr(out), int(count),
                   int(bool(output_ntt)), _ptr(scratch), _stream(stream)))
+
+    def multiply_relinearize(self, x, y, key, out, count, output_ntt, scratch, stream=None):
+        """The product of `count` pairs of two-component ciphertexts, relinearized in ONE key switch: x, y
+        T[2][count][L][N] in NTT form (any words; y may be x), key the relinearization key, at least
+        D x 2 x key_mod_count x N words, out T[2][count][L][N] (may be exactly x or exactly y); scratch: a device tensor
+        of at least scratch_bytes(count, 2) bytes, 256-byte aligned.  out equals the three pointwise products, apply on
+        x1 y1 and the two additions word for word (key_switch.cuh)."""
+        if x is None or y is None or key is None or out is None or scratch is None:
+            raise ValueError("null pointer argument")
+        cols = self._cols(count)
+        self._check_buffers(((x, cols * self.q_count * 2, "x (2 x count x L x N)"),
+                             (y, cols * self.q_count * 2, "y (2 x count x L x N)"),
+                             (key, self._key_words(2) if cols else 0, "key (D x 2 x key_mod_count x N)"),
+                             (out, cols * self.q_count * 2, "out (2 x count x L x N)")))
+        _require_gpu(scratch)
+        if int(count) >= 0 and scratch.numel() * scratch.element_size() < self.scratch_bytes(count, 2):
+            raise ValueError("scratch holds fewer than scratch_bytes(count, 2) bytes")
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_multiply_relinearize_u%d" % self.bits)
+        _check(fn(self._h, _ptr(x), _ptr(y), _ptr(key), _ptr(out), int(count), int(bool(output_ntt)), _ptr(scratch),
+                  _stream(stream)))
 
     def close(self):
         if self._h:

@@ -992,6 +992,16 @@ extern "C"
                 scratch, static_cast<hipStream_t>(stream));                                       \
         });                                                                                       \
     }                                                                                             \
+    int gpuntt_keyswitch_plan_multiply_relinearize_##S(const gpuntt_keyswitch_plan* plan, const T* x, const T* y,  \
+                                                       const T* key, T* out, int count, int output_ntt,           \
+                                                       void* scratch, void* stream)               \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->multiply_relinearize(                \
+                x, y, key, out, count, output_ntt != 0, scratch, static_cast<hipStream_t>(stream));               \
+        });                                                                                       \
+    }                                                                                             \
     int gpuntt_keyswitch_plan_owns_workspace_##S(const gpuntt_keyswitch_plan* plan)               \
     {                                                                                             \
         GPUNTT_NEED(plan)                                                                         \

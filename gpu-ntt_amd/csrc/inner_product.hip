@@ -27,13 +27,7 @@ namespace gpuntt
 {
     namespace kern
     {
-        constexpr int IP_NT = 256; // lanes per workgroup at most (a ring narrower than that gets a narrower workgroup)
-
-        // inputs per pass over the key, at most: RB * C * V accumulators of 5 (u64) or 3 (u32) registers are live, and
-        // 8 (r, c) pairs are what the register file holds at 3 waves per SIMD for u64
-        constexpr int ip_block(int C) { return C <= 2 ? 4 : 2; }
-
-        // IpLimbs, ip_addc, IpAcc, IpFold: inner_product_internal.hpp; RnsWide, rns_shoup: rns_arith.hpp
+        // IP_NT, ip_block, IpLimbs, ip_addc, IpAcc, IpFold: inner_product_internal.hpp; RnsWide, rns_shoup: rns_arith.hpp
 
         // the plan's constants in the workspace: six arrays of M words (q, 2^W mod q and its Shoup companion, 2^2W mod q
         // and its companion, the companion of 1), read through the CONSTANT address space -- nothing writes the workspace
@@ -44,86 +38,8 @@ namespace gpuntt
                                                                IpLimbs limbs, int D, int count, int M, int KM,
                                                                int n_power, unsigned tiles, int accumulate)
         {
-            struct alignas(V * sizeof(T)) Vec
-            {
-                T x[V];
-            };
-            const unsigned tile = blockIdx.x % tiles, rblock = blockIdx.x / tiles;
-            const unsigned m = blockIdx.y;
-            const unsigned long long col = (static_cast<unsigned long long>(tile) * blockDim.x + threadIdx.x) * V;
-            if (col >= (1ull << n_power))
-                return;
-            const int r0 = static_cast<int>(rblock) * RB;
-            const int nr = min(RB, count - r0); // inputs of this block: wave-uniform
-
-            // all index arithmetic in 64 bits: D_key * C * key_mod_count * N passes 2^32 words at real sizes
-            const unsigned long long poly = 1ull << n_power;
-            const unsigned long long stack = static_cast<unsigned long long>(M) << n_power;         // one input's limbs
-            const unsigned long long a_digit = static_cast<unsigned long long>(count) * stack;       // a: [D][count][M][N]
-            const unsigned long long key_comp = static_cast<unsigned long long>(KM) << n_power;      // key: [D][C][KM][N]
-            const unsigned long long key_digit = static_cast<unsigned long long>(C) * key_comp;
-            const unsigned long long at = static_cast<unsigned long long>(r0) * stack + m * poly + col;
-            const T* pa = a + at;
-            const T* pk = key + static_cast<unsigned long long>(limbs.v[m]) * poly + col;
-            T* po = out + at; // out: [C][count][M][N], component stride = a_digit
-
-            IpAcc<T> acc[RB][C][V];
-#pragma unroll
-            for (int r = 0; r < RB; r++)
-#pragma unroll
-                for (int c = 0; c < C; c++)
-                {
-                    Vec o{};
-                    if (accumulate != 0 && r < nr)
-                        o = *reinterpret_cast<const Vec*>(po + c * a_digit + r * stack);
-#pragma unroll
-                    for (int v = 0; v < V; v++)
-                        acc[r][c][v] = IpAcc<T>{o.x[v], T(0), 0u};
-                }
-
-            // the loads of one digit carry no condition, so all RB + C of them are in flight before the first product:
-            // an input past the end of the last block re-reads the block's last one (its results are never stored)
-            unsigned long long a_in[RB];
-#pragma unroll
-            for (int r = 0; r < RB; r++)
-                a_in[r] = static_cast<unsigned long long>(min(r, nr - 1)) * stack;
-            for (int d = 0; d < D; d++)
-            {
-                Vec kv[C], av[RB];
-#pragma unroll
-                for (int c = 0; c < C; c++)
-                    kv[c] = *reinterpret_cast<const Vec*>(pk + c * key_comp);
-#pragma unroll
-                for (int r = 0; r < RB; r++)
-                    av[r] = *reinterpret_cast<const Vec*>(pa + a_in[r]);
-#pragma unroll
-                for (int r = 0; r < RB; r++)
-#pragma unroll
-                    for (int c = 0; c < C; c++)
-#pragma unroll
-                        for (int v = 0; v < V; v++)
-                            acc[r][c][v].mac(av[r].x[v], kv[c].x[v]);
-                pa += a_digit;
-                pk += key_digit;
-            }
-
-            const IpFold<T> fold(consts, M, m);
-#pragma unroll
-            for (int r = 0; r < RB; r++)
-                if (r < nr)
-                {
-#pragma unroll
-                    for (int c = 0; c < C; c++)
-                    {
-                        Vec o;
-#pragma unroll
-                        for (int v = 0; v < V; v++)
-                        {
-                            o.x[v] = fold.reduce(fold.sum(acc[r][c][v])); // the sum is below 3 q < 2^W
-                        }
-                        *reinterpret_cast<Vec*>(po + c * a_digit + r * stack) = o;
-                    }
-                }
+            ip_digit_loop<T, V, C, RB>(a, key, out, consts, limbs, D, count, M, KM, n_power, tiles,
+                                       IpSeedOut<T>{accumulate});
         }
     } // namespace kern
 

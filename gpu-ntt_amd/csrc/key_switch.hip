@@ -29,6 +29,10 @@
 // rotate_hoisted_sum: inner_product_galois_sum of hoisted_rotation.hip (the same inner product, weighted and summed over
 // the G elements in the extended base), then finish over 2 * count stacks whatever G is.  The two share
 // Impl::hoist_prepare: every refusal of the call and the kernel arguments.
+//
+// multiply_relinearize: tensor_top of relinearize.hip (x1 y1 into the scratch), the plan's own decompose steps on it,
+// inner_product_tensor (the inner product seeded with P (x0 y0) and P (x0 y1 + x1 y0)), then finish over 2 * count stacks
+// (DESIGN.md 3.15).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,6 +47,7 @@
 #include "gpuntt/rns/key_switch.cuh"
 #include "hoisted_rotation_internal.hpp"
 #include "launch.hpp"
+#include "relinearize_internal.hpp"
 
 namespace gpuntt
 {
@@ -663,6 +668,61 @@ namespace gpuntt
                                       negacyclic, stream);
             finish(acc, out, stacks, output_ntt, stream);
         }
+
+        // x, y, out: T[2][count][L][N]; key: T[D_key][2][KM][N]; the scratch: ks_scratch(count, 2)
+        void multiply_relinearize(const T* x, const T* y, const T* key, T* out, int count, bool output_ntt, void* scratch,
+                                  hipStream_t stream) const
+        {
+            need_transforms();
+            const KsScratch s = ks_scratch<T>(L, M, D, n, count, 2); // checks count
+            if (x == nullptr || y == nullptr || key == nullptr || out == nullptr || scratch == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
+                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            if (count == 0)
+                return;
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T);
+            const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
+            for (const auto& op : {std::pair<const void*, std::uint64_t>{x, ct_bytes}, {y, ct_bytes}, {key, key_bytes}})
+            {
+                if (ks_overlap(scratch, s.total, op.first, op.second))
+                    throw std::invalid_argument("out or the scratch overlaps an operand!");
+                // out may be exactly x or exactly y: the last read of both (inner_product_tensor) precedes mod_down's
+                // first write on the stream.  Any other overlap is refused
+                if (ks_overlap(out, ct_bytes, op.first, op.second) && (op.first == key || op.first != out))
+                    throw std::invalid_argument("out or the scratch overlaps an operand!");
+            }
+            if (ks_overlap(out, ct_bytes, scratch, s.total))
+                throw std::invalid_argument("The scratch overlaps out!");
+            // the batches of the transforms are ints; the grids of mod_up and mod_down: as their own launches check
+            if (static_cast<unsigned long long>(D) * static_cast<unsigned>(count) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
+                throw std::invalid_argument("Invalid count!");
+            if (((cols + kern::KS_NT - 1) / kern::KS_NT) * kern::KS_NT > 0xFFFFFFFFull ||
+                ((2 * cols + kern::BC_NT - 1) / kern::BC_NT) * kern::BC_NT > 0xFFFFFFFFull)
+                throw std::invalid_argument("Invalid count!");
+            kern::RelinArgs<T> args{};
+            for (int m = 0; m < M; m++)
+                args.limbs.v[m] = static_cast<unsigned char>(limbs[m]);
+            for (int j = 0; j < L; j++)
+                args.p_mod_q[j] = p_mod_q[j], args.p_mod_q_shoup[j] = p_mod_q_shoup[j];
+            T* a = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.a);
+            T* d2 = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.c_coeff);
+            T* acc = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.inner_out);
+            const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
+            const T* x1 = x + cols * L;
+            const T* y1 = y + cols * L;
+            // the grid limits of both kernels, before the first launch
+            host::relin_top_launch<T>(x1, y1, d2, consts, count, L, M, n, false, stream);
+            host::relin_inner_launch<T>(a, key, acc, consts, x, y, args, D, count, L, M, KM, n, false, stream);
+
+            host::relin_top_launch<T>(x1, y1, d2, consts, count, L, M, n, true, stream);
+            ntt_q_i->execute(d2, d2, count * L, stream);
+            mod_up(d2, a, count, BaseConvMode::centred, stream);
+            ntt_full_f->execute(a, a, D * count * M, stream);
+            host::relin_inner_launch<T>(a, key, acc, consts, x, y, args, D, count, L, M, KM, n, true, stream);
+            finish(acc, out, 2 * count, output_ntt, stream);
+        }
     };
 
     template <typename T> int KeySwitchPlan<T>::digits(int q_count, int alpha)
@@ -826,6 +886,12 @@ namespace gpuntt
     {
         p_->rotate_hoisted_sum(device_a, device_c0, device_keys_host, galois_elements_host, device_weights_host, elements,
                                device_out, count, output_ntt, scratch_device, stream);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::multiply_relinearize(const T* device_x, const T* device_y, const T* device_key, T* device_out,
+                                                int count, bool output_ntt, void* scratch_device, stream_t stream) const
+    {
+        p_->multiply_relinearize(device_x, device_y, device_key, device_out, count, output_ntt, scratch_device, stream);
     }
     template <typename T>
     void KeySwitchPlan<T>::apply(const T* device_c_in, const T* device_key, T* device_out, int count, int components,

@@ -101,6 +101,41 @@
 //     or each other.  std::invalid_argument, before anything is launched: G outside [1, 64], count < 0, an even element
 //     (also one that is even once reduced), a null a / out / key pointer / scratch, a scratch that is not 256-byte aligned,
 //     an overlap, a count beyond the grid and batch limits rotate_hoisted checks, a plan built without transforms
+//   multiply_relinearize(x, y, key, out, count, output_ntt, scratch):  the product of `count` pairs of two-component
+//     ciphertexts, relinearized: ct x ct in ONE key switch.  x, y = T[2][count][L][N], the component-major layout every
+//     plan call writes (so results chain), in NTT form over the q-base; every word may hold any value and is read modulo
+//     q_m.  y may equal x (a squaring).  key = T[D_key][2][key_mod_count][N], the relinearization key (s^2 -> s), read
+//     through the plan's key_mod_count / key_limbs exactly as apply reads it.  out = T[2][count][L][N].
+//     DEFINITION, word for word, through the calls that exist beside it:
+//       1. for every r, m < L and column j the canonical residues
+//            d0 = x0 y0 mod q_m,   d1 = (x0 y1 + x1 y0) mod q_m,   d2 = x1 y1 mod q_m
+//          -- each what a q-base InnerProductPlan::multiply_accumulate gives for that one input (D = 1 for d0 and d2,
+//          D = 2 for d1, C = 1, the polynomials of y in the key's place),
+//       2. k = apply(d2, key, count, components = 2, input_ntt = true, output_ntt),
+//       3. out[c] = (k[c] + d_c) mod q_m; with output_ntt false d_c is inverse-transformed over the q-base before the
+//          addition.
+//     What runs instead, each step ONE launch over the whole batch (plus the transforms' own):
+//       tensor_top: d2[r][m][j] = x1 y1 mod q_m into the scratch's c_coeff region (one exact mac, the fold);
+//       the plan's own decompose steps on that region: the q-base INTT in place, mod_up (centred) into the `a` region,
+//       the full-base NTT over D * count * M polynomials;
+//       inner_product_tensor: acc[c][r][m][j] = (sum_d a[d][r][m][j] * key[d][c][limb(m)][j]
+//                             + [m < L] (P mod q_m) * d_c[r][m][j]) mod q_m into the inner_out region -- d0 and d1 are
+//                             formed on the fly from the four input words and never written to memory; the K special
+//                             limbs load nothing of x or y;
+//       finish over 2 * count stacks: the full-base INTT, mod_down, [output_ntt: the q-base NTT].
+//     Folding d_c in as P * d_c BEFORE the ModDown is exact: it is rotate_hoisted's c0 argument applied to both
+//     components.  The transforms are linear, so the q-limbs of the stack that reaches mod_down hold c_j + P d (mod q_j),
+//     c the accumulators of step 2 and d = d_c in coefficient form, while the special limbs are untouched (P d vanishes
+//     mod p_k): conv_j is computed from the special limbs only and is unchanged.  Then
+//       (c_j + P d - conv_j) P^-1 = d + (c_j - conv_j) P^-1  (mod q_j),
+//     the right side is step 3's sum and both sides are canonical residues, so they are the same word; with output_ntt
+//     the forward NTT is linear and its outputs canonical, so the words agree there too.
+//     Allocates nothing, never synchronises: one stream, capturable as it is.  count = 0: nothing is launched.  The
+//     scratch is the existing scratch_bytes(count, 2) bytes, 256-byte aligned.  out may be exactly x or exactly y: on the
+//     stream the last read of both (inner_product_tensor) precedes mod_down's first write.  std::invalid_argument, before
+//     anything is launched: any other overlap of out or the scratch with an operand or with each other, a null pointer, a
+//     scratch that is not 256-byte aligned, count < 0, a count beyond the grid and batch limits rotate_hoisted checks, a
+//     plan built without transforms
 //
 //   * ranges: 1 <= L, 1 <= K, M = L + K <= 64, alpha >= 1, 1 <= components <= 4, count >= 0 and stacks >= 0 (0: nothing
 //     happens), n_power in [1, 28], M <= key_mod_count <= 256.  A plan is built for ONE level (one L) and one ring; a
@@ -195,6 +230,9 @@ namespace gpuntt
                                 const std::uint32_t* galois_elements_host, const T* const* device_weights_host,
                                 int elements, T* device_out, int count, bool output_ntt, void* scratch_device,
                                 stream_t stream) const;
+
+        void multiply_relinearize(const T* device_x, const T* device_y, const T* device_key, T* device_out, int count,
+                                  bool output_ntt, void* scratch_device, stream_t stream) const;
 
         int q_count() const;
         int p_count() const;

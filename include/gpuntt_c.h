@@ -388,6 +388,12 @@ extern "C"
      *                  gpuntt_keyswitch_plan_hoisted_sum_scratch_bytes_*() bytes (independent of G), 256-byte aligned.  One
      *                  inner product launch, then ONE INTT, mod_down and [forward NTT] over 2 * count stacks; the result
      *                  rounds once and is NOT word for word the weighted sum of rotate_hoisted's outputs (key_switch.cuh)
+     *   multiply_relinearize  the product of count pairs of two-component ciphertexts with the top component switched
+     *                  under the relinearization key, in ONE key switch: x, y T[2][count][L][N] in NTT form (any words,
+     *                  read modulo q_m; y may equal x), key T[D_key][2][key_mod_count][N], out T[2][count][L][N] (may be
+     *                  exactly x or exactly y); the scratch is gpuntt_keyswitch_plan_scratch_bytes_*(count, 2) bytes,
+     *                  256-byte aligned.  out equals the three pointwise products, apply on x1 y1 and the two additions
+     *                  word for word (key_switch.cuh)
      * No call allocates or synchronises.
      * host only (no GPU): constants -- arrays_host holds 18 caller arrays in the order of KeySwitchConstants<T>
      * (up_qhat_inv[L], up_qhat_inv_shoup[L], up_matrix[L][M], up_q_mod[D][M], up_recip[L], up_bit_length[L],
@@ -429,6 +435,9 @@ extern "C"
                                                      const uint32_t* const* keys_host, const uint32_t* galois_elements_host,
                                                      const uint32_t* const* weights_host, int elements, uint32_t* out,
                                                      int count, int output_ntt, void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_multiply_relinearize_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* x, const uint32_t* y,
+                                                       const uint32_t* key, uint32_t* out, int count, int output_ntt,
+                                                       void* scratch, void* stream);
     int gpuntt_keyswitch_plan_owns_workspace_u32(const gpuntt_keyswitch_plan* plan); /* 1 / 0, negative on error */
     int gpuntt_keyswitch_plan_destroy_u32(gpuntt_keyswitch_plan* plan);
     int gpuntt_keyswitch_constants_u32(const gpuntt_modulus32* q_moduli_host, int q_count, const gpuntt_modulus32* p_moduli_host, int p_count,
@@ -471,6 +480,9 @@ extern "C"
                                                      const uint64_t* const* keys_host, const uint32_t* galois_elements_host,
                                                      const uint64_t* const* weights_host, int elements, uint64_t* out,
                                                      int count, int output_ntt, void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_multiply_relinearize_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* x, const uint64_t* y,
+                                                       const uint64_t* key, uint64_t* out, int count, int output_ntt,
+                                                       void* scratch, void* stream);
     int gpuntt_keyswitch_plan_owns_workspace_u64(const gpuntt_keyswitch_plan* plan); /* 1 / 0, negative on error */
     int gpuntt_keyswitch_plan_destroy_u64(gpuntt_keyswitch_plan* plan);
     int gpuntt_keyswitch_constants_u64(const gpuntt_modulus64* q_moduli_host, int q_count, const gpuntt_modulus64* p_moduli_host, int p_count,
