@@ -128,7 +128,7 @@ ENV_OPTIONS = {"GPUNTT_PATH": ("path", None), "GPUNTT_U32_E32": ("u32_e32", lamb
 
 
 TEST_HOOKS = {"no_scratch", "rns_force_fallback", "u32_e32", "reset_predictions", "two_sweep_big", "baseconv_ksplit",
-              "keyswitch_split", "keyswitch_hoist_chunk"}
+              "keyswitch_split", "keyswitch_hoist_chunk", "contig_p4"}
 TEST_PATHS = {"fast-strict", "generic-capped"}
 
 
@@ -146,6 +146,14 @@ def set_option(name, value):
 def set_test_hook(name, value):
     """gpuntt_test_set_hook (csrc/test_hooks.h)."""
     _check(load_library().gpuntt_test_set_hook(str(name).encode(), str(value).encode()))
+
+
+def contig_p4_launches():
+    """gpuntt_test_contig_p4_launches (csrc/test_hooks.h): launches of the four-polynomial tile of the forward 64-bit
+    contiguous pass since the library was loaded."""
+    fn = load_library().gpuntt_test_contig_p4_launches
+    fn.restype = ctypes.c_ulonglong
+    return int(fn())
 
 
 def scratch_stats():

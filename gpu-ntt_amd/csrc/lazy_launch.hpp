@@ -35,6 +35,14 @@ namespace gpuntt
         // one strided pass of 9 / 10 stages and the 14-stage contiguous pass, both on 16384-coefficient tiles -- instead of
         // three.  Bit-exact, a third less traffic, and no faster: profiles/r06_two_sweep_big_pmc.txt names the limiter.
         bool lazy_two_sweep_big();
+        // Forward 64-bit Merge transforms of the ring 2^16: the 10-stage contiguous last pass on tiles of FOUR polynomials x
+        // one 1024-coefficient segment (kern::merge_pass_lazy<..., P4>, contig_p4_map.hpp) -- twiddles of stage bits 7..4
+        // in scalar registers, a quarter of the per-lane twiddle traffic of stage bits 3..0.  Test hook contig_p4 = 0 | 1.
+        bool lazy_contig_p4();
+        void note_contig_p4_launch();               // test hook: counts the launches of that tile (prep.hip)
+        unsigned long long contig_p4_launches();
+        // the ring whose K = 10 pass takes that tile (other rings with a 10-stage pass: each by its own measurement)
+        constexpr int LAZY_P4_N_POWER = 16;
         // 32-bit ring 2^13: every call takes the 8192-coefficient tile
         constexpr unsigned long long lazy_u32_small_batch() { return 0x7fffffffull; }
         // `inverse` and `polys` (transforms in the call) must be the same wherever one call asks:
@@ -602,6 +610,16 @@ namespace gpuntt
                            (polys << base.n) == base.total)
                               ? static_cast<int>(polys)
                               : 0;
+                if constexpr (sizeof(T) == 8 && !INV)
+                {
+                    // plain Merge call or plan (no *_Ordered, no fused product, no 4-step route), whole groups of four
+                    // polynomials per modulus; everything else keeps the one-polynomial tile, no tail launch
+                    const unsigned long long mc = base.mods != nullptr ? static_cast<unsigned long long>(base.mod_count) : 1ull;
+                    p.p4 = p.contig && p.k == 10 && tlp == 12 && i == pl.count - 1 && pl.count > 1 && !partial &&
+                           base.n == LAZY_P4_N_POWER && base.poly_shift == base.n && mc >= 1 && polys % (4ull * mc) == 0 &&
+                           (polys << base.n) == base.total && base.poly_order == nullptr && base.mod_order == nullptr &&
+                           base.mul_in == nullptr && a.batch == 0 && lazy_contig_p4();
+                }
                 if constexpr (sizeof(T) == 4)
                 {
                     // the full-tile contiguous pass of a 32-bit plan (forward: last, on lazy input; inverse: first) on the

@@ -7,10 +7,12 @@ namespace gpuntt
 {
     namespace host
     {
-        template <typename T, int TLOG, bool INV, bool CONTIG, int K, int IN_BOUND, bool LAST, int LIMSEL = 0>
+        template <typename T, int TLOG, bool INV, bool CONTIG, int K, int IN_BOUND, bool LAST, int LIMSEL = 0, bool P4 = false>
         inline void launch_lazy_one(const kern::LazyArgsT<T>& a, unsigned grid, hipStream_t stream)
         {
-            GPUNTT_LAUNCH_FAMILY(LIMSEL, (kern::merge_pass_lazy<T, TLOG, INV, CONTIG, K, IN_BOUND, LAST, LIMSEL>), dim3(grid),
+            if constexpr (P4)
+                note_contig_p4_launch();
+            GPUNTT_LAUNCH_FAMILY(LIMSEL, (kern::merge_pass_lazy<T, TLOG, INV, CONTIG, K, IN_BOUND, LAST, LIMSEL, 0, P4>), dim3(grid),
                                dim3(kern::LTile<TLOG>::NT), 0, stream, a);
             GPUNTT_HIP_CHECK(hipGetLastError());
         }
@@ -113,6 +115,16 @@ namespace gpuntt
                                 case 8: GPUNTT_ONE(true, 8, LIM, true);
                                 case 9: GPUNTT_ONE(true, 9, LIM, true);
                                 case 10:
+                                    // four-polynomial tile (Pass::p4, run_transform_lazy: whole groups of
+                                    // 4 * mod_count polynomials): same grid, same bounds
+                                    if constexpr (sizeof(T) == 8)
+                                        if (p.p4)
+                                        {
+                                            if constexpr (LIM == 31)
+                                                if (p.in_b > 0 && p.in_b <= 27)
+                                                    return launch_lazy_one<T, TLOG, INV, true, 10, 27, true, LIMSEL, true>(a, grid, stream);
+                                            return launch_lazy_one<T, TLOG, INV, true, 10, LIM, true, LIMSEL, true>(a, grid, stream);
+                                        }
                                     // 31 q range behind a strided pass that hands over <= 27 q (two-pass plans
                                     // of 2^14 .. 2^16: 17 / 21 / 25 q): three rounds of range corrections, not four
                                     if constexpr (LIM == 31)

@@ -11,6 +11,7 @@
 // (src/lib/ntt_merge/ntt.cu:596-761, 1086-1318).
 #pragma once
 
+#include "contig_p4_map.hpp"
 #include "lazy.hpp"
 #include "merge_kernels.hpp"
 
@@ -406,7 +407,8 @@ namespace gpuntt
         // windows of strided passes never dip below the contiguous-run bits), so a thread keeps one modulus for the pass
         // and only the operand classes change: q, -q, twiddles and n^-1 in vector registers (lazy::Mod<T, LIM, true>).
         template <typename T, int TLOG, bool INV, bool CONTIG, int K, int IN_BOUND, bool LAST,
-                  Fst FST = Fst::none, int LIM = 0, Xp XP = Xp::none, int SKIP = 0, bool VQ = false, int ROWLEN = 0>
+                  Fst FST = Fst::none, int LIM = 0, Xp XP = Xp::none, int SKIP = 0, bool VQ = false, int ROWLEN = 0,
+                  bool P4 = false>
         __device__ __forceinline__ void pass_body(const LazyArgsT<T>& a, T* lds, T q_value, T q_bit, T q_mu,
                                                   int mi, unsigned long long fst_poly = 0,
                                                   unsigned fst_tile = 0, long long blk_override = -1,
@@ -419,10 +421,21 @@ namespace gpuntt
             static_assert(!VQ || (FST == Fst::none && XP == Xp::none && SKIP == 0), "per-lane moduli: plain passes");
             static_assert(!(VQ && CONTIG) || (K >= R && K < TLOG && IN_BOUND == 1 && LAST),
                           "per-lane moduli, contiguous: single-pass transforms of rings of 16 .. tile/2 coefficients");
+            // P4: the tile is four polynomials x one 1024-coefficient segment (contig_p4_map.hpp); fst_poly = flat index of
+            // the tile's first coefficient, fst_tile = the segment
+            static_assert(!P4 || (sizeof(T) == 8 && TLOG == p4::TLOG && !INV && CONTIG && K == p4::K && IN_BOUND != 1 && LAST &&
+                                  FST == Fst::none && XP == Xp::none && SKIP == 0 && !VQ),
+                          "four-polynomial tile: the forward 64-bit 10-stage last pass");
             constexpr bool HAS_FST = (FST != Fst::none);
             constexpr int TL = TLOG;
             constexpr int NT = LTile<TLOG>::NT;
             constexpr int NR_ = SCH::NR;
+            // the P4 maps hard-code the schedule of this pass: three rounds, stages 2 / 4 / 4, register windows 6 / 4 / 0
+            static_assert(!P4 || (SCH::NR == p4::ROUNDS && SCH::wl_of(0) == p4::window(0) && SCH::wl_of(1) == p4::window(1) &&
+                                  SCH::wl_of(P4 ? 2 : 0) == p4::window(2) && SCH::stages_of(0) == 2 && SCH::stages_of(1) == 4 &&
+                                  SCH::stages_of(P4 ? 2 : 0) == 4 && SCH::first_pos(0) == 9 && SCH::first_pos(1) == 7 &&
+                                  SCH::first_pos(P4 ? 2 : 0) == 3),
+                          "contig_p4_map.hpp assumes this round schedule");
 
             // single-pass transforms of rings smaller than a tile: the tile holds several polynomials
             constexpr bool MULTI_POLY = CONTIG && (K < TL) && (IN_BOUND == 1) && (LAST || HAS_FST);
@@ -439,7 +452,8 @@ namespace gpuntt
             const int t = threadIdx.x;
             constexpr bool SEG = (FST == Fst::nat_rows);
             using Map = LTileMap<TLOG, CONTIG, K, SEG>;
-            Map map = SEG   ? Map((fst_poly << a.poly_shift) +
+            Map map = P4    ? Map(fst_poly)
+                      : SEG ? Map((fst_poly << a.poly_shift) +
                                       ((static_cast<unsigned long long>(fst_tile) << (TL - K)) << a.row_log) +
                                       (static_cast<unsigned long long>(fst_seg) << K),
                                   a.row_log)
@@ -449,9 +463,19 @@ namespace gpuntt
                                                     : static_cast<unsigned long long>(blockIdx.x));
             // whole tile inside the batch (always true for N >= 4096); taken before *_Poly_Ordered moves
             // the tile to its memory slot, which may lie beyond batch * N
-            const bool tile_in_range = (CONTIG && !HAS_FST) ? ((map.base + LTile<TLOG>::TILE) <= a.total) : true;
-            if (a.poly_order != nullptr)
-                map.remap_poly(a.poly_order, a.n); // twiddle indices use flat & (N-1): unaffected
+            // (P4: the host sends whole groups of four polynomials only, and no *_Poly_Ordered call)
+            const bool tile_in_range = (CONTIG && !HAS_FST && !P4) ? ((map.base + LTile<TLOG>::TILE) <= a.total) : true;
+            if constexpr (!P4)
+                if (a.poly_order != nullptr)
+                    map.remap_poly(a.poly_order, a.n); // twiddle indices use flat & (N-1): unaffected
+            // P4: segment of the ring, wave index (scalar) and the distance between two polynomials of the tile
+            const unsigned p4_seg = fst_tile;
+            const unsigned p4_wave = P4 ? static_cast<unsigned>(__builtin_amdgcn_readfirstlane(t >> 6)) : 0u;
+            const unsigned long long p4_stride =
+                P4 ? (static_cast<unsigned long long>(a.mods != nullptr ? a.mod_count : 1) << a.n) : 0ull;
+            (void) p4_seg;
+            (void) p4_wave;
+            (void) p4_stride;
             if constexpr (VQ)
             {
                 unsigned owner;
@@ -502,6 +526,25 @@ namespace gpuntt
                 // block-uniform: no thread bits above the register window; wave-uniform: the 64 lanes
                 // of a wave differ only in tile bits below the window (WL >= 6) -> scalar loads with
                 // the wave's first thread id
+                if constexpr (P4)
+                {
+                    // rounds 0 and 1: every twiddle is uniform over the wave (round 0: over the block) -> scalar loads;
+                    // round 2: the [tile][k][thread] layout, the four 16-lane rows of a wave read the same 16 entries
+                    int o4 = 0;
+                    static_for<STAGES>([&](auto s_) {
+                        constexpr int s = decltype(s_)::value;
+                        constexpr int p = FIRST_POS - s;
+                        constexpr int CNT = 1 << (R - 1 - (p - WL));
+                        const TW* ps = tw_mod + (r == 2 ? p4::tw_lane_index(a.n, p4_seg, static_cast<unsigned>(t), p, 0)
+                                                        : p4::tw_uniform_index(a.n, p4_seg, r == 1 ? p4_wave : 0u, p, 0));
+                        static_for<CNT>([&](auto k_) {
+                            constexpr int kk = decltype(k_)::value;
+                            tws[o4 + kk] = ps[r == 2 ? kk * NT : kk];
+                        });
+                        o4 += CNT;
+                    });
+                    return;
+                }
                 constexpr bool UNIFORM = (WL + R == TL) || (WL >= 6);
                 const int t_uni = (WL + R == TL) ? 0 : __builtin_amdgcn_readfirstlane(t);
                 int off = 0;
@@ -582,7 +625,7 @@ namespace gpuntt
                 constexpr int FIRST_POS = SCH::first_pos(r);
                 constexpr int WL = SCH::wl_of(r);
                 constexpr bool DIRECT_IO = (WL >= 4);
-                constexpr bool UNIFORM_R = (WL + R == TL) || (WL >= 6); // scalar twiddles this round
+                constexpr bool UNIFORM_R = P4 ? (r < 2) : ((WL + R == TL) || (WL >= 6)); // scalar twiddles this round
 
                 // ---- gather -----------------------------------------------------------
                 if constexpr (r == 0)
@@ -713,6 +756,15 @@ namespace gpuntt
                         }
                         relayout_barrier(v); // the exchanges below reuse the buffer in the e + (e >> 4) layout
                     }
+                    else if constexpr (P4)
+                    {
+                        // wave w reads the segment of polynomial w: 512-byte runs straight into registers
+                        const T* srcw = src + (map.base + p4_wave * p4_stride);
+                        const unsigned lane = static_cast<unsigned>(t) & 63u;
+#pragma unroll
+                        for (int j = 0; j < EPT; j++)
+                            v[j] = ld_stream<false>((srcw + (static_cast<unsigned>(j) << WL)) + lane);
+                    }
                     else if constexpr (DIRECT_IO)
                     {
                         if (plain_io)
@@ -814,7 +866,8 @@ namespace gpuntt
                 }
                 else
                 {
-                    const T* lw = lds + lds_pad(elem_of<WL>(t, 0));
+                    const T* lw = lds + (P4 ? static_cast<int>(p4::lds_slot(p4::elem(r, static_cast<unsigned>(t), 0)))
+                                            : lds_pad(elem_of<WL>(t, 0)));
 #pragma unroll
                     for (int j = 0; j < EPT; j++)
                         v[j] = lw[lds_joff<WL>(j)];
@@ -1006,6 +1059,25 @@ namespace gpuntt
                             }
                         }
                     }
+                    else if constexpr (P4)
+                    {
+                        // registers (16 contiguous coefficients per thread) -> LDS -> the wave's store window: its
+                        // 256-coefficient block of the four polynomials, 512 bytes per store instruction
+                        T* lw = lds + p4::lds_slot(p4::elem(r, static_cast<unsigned>(t), 0));
+#pragma unroll
+                        for (int j = 0; j < EPT; j++)
+                            lw[lds_joff<WL>(j)] = v[j];
+                        wave_sync();
+                        const T* lo = lds + p4::lds_slot(p4::elem_out(static_cast<unsigned>(t), 0));
+#pragma unroll
+                        for (int j = 0; j < EPT; j++)
+                            v[j] = lo[p4::lds_slot(p4::elem_out(0, static_cast<unsigned>(j)))];
+                        T* dstw = a.out + (map.base + (p4_wave << 8));
+                        const unsigned lane = static_cast<unsigned>(t) & 63u;
+#pragma unroll
+                        for (int j = 0; j < EPT; j++)
+                            st_stream<true>((dstw + p4::mem_offset(p4::elem_out(0, static_cast<unsigned>(j)), p4_stride)) + lane, v[j]);
+                    }
                     else if constexpr (WIO_OK && !DIRECT_IO && WL <= 6)
                     {
                         // registers (16 contiguous coefficients per thread) -> LDS -> the wave's own
@@ -1133,11 +1205,14 @@ namespace gpuntt
                     // next round's twiddles are requested before the exchange barrier
                     if constexpr (TW_AHEAD)
                         load_twiddles(std::integral_constant<int, r + 1>{}, tw_next);
-                    T* lw = lds + lds_pad(elem_of<WL>(t, 0));
+                    T* lw = lds + (P4 ? static_cast<int>(p4::lds_slot(p4::elem(r, static_cast<unsigned>(t), 0)))
+                                      : lds_pad(elem_of<WL>(t, 0)));
 #pragma unroll
                     for (int j = 0; j < EPT; j++)
                         lw[lds_joff<WL>(j)] = v[j];
-                    if constexpr (WL <= 6 && SCH::wl_of(r + 1 < NR_ ? r + 1 : r) <= 6)
+                    if constexpr (P4 && r == 0)
+                        relayout_barrier(v); // wave = polynomial -> wave = 256-coefficient block of all four: the one block-wide exchange
+                    else if constexpr (WL <= 6 && SCH::wl_of(r + 1 < NR_ ? r + 1 : r) <= 6)
                         wave_sync(); // both windows inside the wave's sub-block
                     else
                         __syncthreads();
@@ -1349,7 +1424,11 @@ namespace gpuntt
                 out[e] = INV ? m.mul(lds[e], ninv) : lds[e];
         }
 
-        template <typename T, int TLOG, bool INV, bool CONTIG, int K, int IN_BOUND, bool LAST, int LIM = 0, int SKIP = 0>
+        // P4 (forward 64-bit, CONTIG, K = 10, 4096-coefficient tile, last pass): the tile is one 1024-coefficient segment
+        // of FOUR polynomials that share a modulus (contig_p4_map.hpp) -- block b -> segment b % 2^(n-10) of modulus
+        // (b >> (n-10)) % mod_count of polynomial group (b >> (n-10)) / mod_count; the host sends whole groups only
+        template <typename T, int TLOG, bool INV, bool CONTIG, int K, int IN_BOUND, bool LAST, int LIM = 0, int SKIP = 0,
+                  bool P4 = false>
         __global__ __launch_bounds__(LTile<TLOG>::NT, (LOcc<TLOG, T>::WAVES)) void merge_pass_lazy(LazyArgsT<T> a)
         {
             using M = lazy::Mod<T, LIM>;
@@ -1359,7 +1438,7 @@ namespace gpuntt
             using SCH = PassSched<TLOG, INV, CONTIG, K, IN_BOUND, M::LIMIT, M::TB, SK>;
             // single-round passes with coalesced register windows never touch LDS
             constexpr bool NEEDS_LDS = (SCH::NR > 1) || (SCH::wl_of(0) < 4);
-            __shared__ T lds[NEEDS_LDS ? LTile<TLOG>::LDS_ELEMS : 1];
+            __shared__ T lds[P4 ? p4::LDS_ELEMS : (NEEDS_LDS ? LTile<TLOG>::LDS_ELEMS : 1)];
 
             // (the inverse row pass of the 4-step rings 2^14 .. 2^16 and the forward last pass of 2^14 .. 2^17 as their own
             // fall-back: phase 2 of the generic algorithm on the block's 4096 words; inverse: a.n = log2 n2, forward: a.n =
@@ -1390,6 +1469,25 @@ namespace gpuntt
             // F_REVERSE: consecutive passes of one transform walk the batch in opposite directions, so a pass
             // starts on the data its predecessor wrote last -- the part still in the 256 MiB Infinity Cache
             const unsigned bx = (a.flags & F_REVERSE) ? (nblk - 1u - bidx) : bidx;
+            if constexpr (P4)
+            {
+                const unsigned mc = (a.mods != nullptr) ? static_cast<unsigned>(a.mod_count) : 1u;
+                const int seg_log = a.n - K;
+                const unsigned seg = uniform32(bx & ((1u << seg_log) - 1u));
+                const unsigned pm = bx >> seg_log; // group * mod_count + modulus
+                mi = static_cast<int>(uniform32(pm % mc));
+                const unsigned long long poly0 = static_cast<unsigned long long>(pm / mc) * (4u * mc) + static_cast<unsigned>(mi);
+                if (a.mods != nullptr)
+                {
+                    const Modulus<T> md = a.mods[mi];
+                    qv = md.value;
+                    qb = md.bit;
+                    qm = md.mu;
+                }
+                pass_body<T, TLOG, INV, CONTIG, K, IN_BOUND, LAST, Fst::none, LIM, Xp::none, SK, false, 0, true>(
+                    a, lds, qv, qb, qm, mi, uniform64((poly0 << a.n) + (static_cast<unsigned long long>(seg) << K)), seg);
+                return;
+            }
             long long blk = static_cast<long long>(bx);
             if (a.batch > 1)
             {

@@ -626,7 +626,7 @@ namespace gpuntt
         // The library reads NO environment variable.  PRODUCT options (GPU_NTT_SetOption / gpuntt_set_option, listed in
         // include/gpuntt/ntt_merge/ntt.cuh): path = default | generic | fast, check_4step_tables, rns_predict.  TEST HOOKS
         // (set_test_hook / gpuntt_test_set_hook -- a symbol the public headers do not declare; csrc/test_hooks.h): path =
-        // fast-strict | generic-capped, no_scratch, rns_force_fallback, u32_e32.  Every public entry point opens a
+        // fast-strict | generic-capped, no_scratch, rns_force_fallback, u32_e32, contig_p4.  Every public entry point opens a
         // WorkspaceScope, and the outermost scope of a thread takes ONE snapshot of all of them: a call sees the same values
         // from its first decision to its last launch, whatever another thread sets meanwhile.
         void baseconv_set_ksplit(int v); // base_conversion.hip
@@ -644,6 +644,7 @@ namespace gpuntt
                 int u32_e32 = 0x1f000;      // test hook: 32-bit Merge rings on the 32-coefficients-per-lane kernels (bit n = ring 2^n; bit 16: the
                                             // full-tile contiguous pass of larger rings)
                 int two_sweep_big = 0;      // test hook (experiment): 64-bit rings 2^23 / 2^24 forward in two sweeps on 16384-coefficient tiles
+                int contig_p4 = 1;          // test hook: forward 64-bit ring 2^16, 10-stage last pass on tiles of four polynomials x one segment
             };
             std::mutex g_opt_mutex;
             std::atomic<int> g_reset_predictions{0};   // test hook reset_predictions: consumed by the next rns_guess
@@ -705,6 +706,8 @@ namespace gpuntt
                     g_opt.u32_e32 = iv; // a mask over the rings 2^12 .. 2^15; bit 16: the contiguous pass of larger rings
                 else if (test_hooks && k == "two_sweep_big" && bit)
                     g_opt.two_sweep_big = iv;
+                else if (test_hooks && k == "contig_p4" && bit)
+                    g_opt.contig_p4 = iv;
                 else if (test_hooks && k == "baseconv_ksplit" && is_num && lv >= 0 && lv <= 16)
                     // base_conversion.hip: workgroups per column tile, 0 = its own choice.  NOT part of the per-call
                     // snapshot below: a measurement knob of tools/bench_baseconv.py, read once per launch from a
@@ -733,6 +736,7 @@ namespace gpuntt
         unsigned lazy_e32_mask() { return static_cast<unsigned>(options().u32_e32); }
         int forced_path() { return options().path; }
         bool lazy_two_sweep_big() { return options().two_sweep_big != 0; }
+        bool lazy_contig_p4() { return options().contig_p4 != 0; }
         static bool rns_predict_enabled() { return options().rns_predict != 0; }
         static bool rns_force_fallback() { return options().rns_force_fallback != 0; }
         bool check_4step_tables() { return options().check_4step != 0; }
@@ -765,6 +769,14 @@ namespace gpuntt
             std::lock_guard<std::mutex> lock(g_log_mutex);
             g_log.push_back(k);
         }
+        // test hook: launches of the four-polynomial tile (kern::merge_pass_lazy<..., P4>) since the library was loaded --
+        // the launch log cannot tell them from the one-polynomial tile, whose name they keep
+        namespace
+        {
+            std::atomic<unsigned long long> g_contig_p4_launches{0};
+        }
+        void note_contig_p4_launch() { g_contig_p4_launches.fetch_add(1, std::memory_order_relaxed); }
+        unsigned long long contig_p4_launches() { return g_contig_p4_launches.load(std::memory_order_relaxed); }
         void launch_log_start()
         {
             std::lock_guard<std::mutex> lock(g_log_mutex);

@@ -8,6 +8,8 @@
  *       rns_force_fallback = 0|1 the preparation kernel's own fall-back serves every drop-in RNS Merge call
  *       u32_e32 = mask           32-bit Merge rings 2^12 .. 2^15 on the 32-coefficients-per-lane kernels (bit n = ring 2^n;
  *                                bit 16: the full-tile contiguous pass of larger rings)
+ *       contig_p4 = 0 | 1        forward 64-bit Merge transforms of the ring 2^16: the 10-stage last pass on tiles of four
+ *                                polynomials x one 1024-coefficient segment (1), or on the one-polynomial tile (0)
  *       two_sweep_big = 0 | 1    experiment: 64-bit rings 2^23 / 2^24 forward in two sweeps on 16384-coefficient tiles
  *       baseconv_ksplit = 0..16  base conversion: workgroups per column tile that share its outputs (0: the library's choice)
  *       keyswitch_split = 0..64  key switching: workgroups per column tile that share the (digit, block) pairs of the ModUp
@@ -21,6 +23,9 @@
  *   gpuntt_test_scratch_stats(out[6])   the twiddle scratch of captured calls, which their graph owns (prep.hip): buffers handed to
  *                                       a graph, of those reported dead by their graph, buffers pooled now, buffers re-used from
  *                                       the pool, chains erased, chains alive
+ *   gpuntt_test_contig_p4_launches()    launches of the four-polynomial tile of the forward 64-bit contiguous pass since the
+ *                                       library was loaded (hook contig_p4): the launch log shows them under the name of the
+ *                                       one-polynomial tile
  *   gpuntt_test_keyswitch_hoist_chunk(word_bytes, digits, n_power)  host only: log2 of the chunk inner_product_galois takes
  *                                       for this word size, D and ring under the hook's current value; -1: bad argument
  *   gpuntt_test_keyswitch_hoist_sum_chunk(word_bytes, digits, n_power)  the same for the destination chunk of
@@ -38,6 +43,7 @@ extern "C"
     int gpuntt_test_launch_log_start(void);
     int gpuntt_test_launch_log_take(char* buf, int capacity);
     int gpuntt_test_scratch_stats(unsigned long long out[6]);
+    unsigned long long gpuntt_test_contig_p4_launches(void);
     int gpuntt_test_keyswitch_hoist_chunk(int word_bytes, int digits, int n_power);
     int gpuntt_test_keyswitch_hoist_sum_chunk(int word_bytes, int digits, int n_power);
 #ifdef __cplusplus
