@@ -115,7 +115,7 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "keyswitch_plan_switch_digits", "keyswitch_plan_apply", "keyswitch_plan_hoisted_scratch_bytes",
               "keyswitch_plan_rotate_hoisted", "keyswitch_plan_hoisted_sum_scratch_bytes",
               "keyswitch_plan_rotate_hoisted_sum", "keyswitch_plan_multiply_relinearize",
-              "keyswitch_plan_owns_workspace",
+              "keyswitch_plan_multiply_relinearize_sum", "keyswitch_plan_owns_workspace",
               "keyswitch_plan_destroy", "keyswitch_constants", "keyswitch_reference_mod_up",
               "keyswitch_reference_mod_down")
     for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option", "gpuntt_galois_element_u32",
@@ -1217,6 +1217,38 @@ class KeySwitchPlan:
         fn = getattr(load_library(), "gpuntt_keyswitch_plan_multiply_relinearize_u%d" % self.bits)
         _check(fn(self._h, _ptr(x), _ptr(y), _ptr(key), _ptr(out), int(count), int(bool(output_ntt)), _ptr(scratch),
                   _stream(stream)))
+
+    def multiply_relinearize_sum(self, xs, ys, key, out, count, output_ntt, scratch, stream=None):
+        """sum_t xs[t] * ys[t] over T = len(xs) pairs of two-component ciphertexts with ONE key switch and ONE ModDown
+        (lazy relinearization): xs, ys two lists of T device tensors, 1 <= T <= 32, each T[2][count][L][N] in NTT form
+        (any words; ys[t] may be xs[t], a tensor may appear in several terms); key, out, count, output_ntt and scratch as
+        for multiply_relinearize; out may be exactly any one of the operands.  With one pair it equals
+        multiply_relinearize word for word; it is NOT word for word the sum of T multiply_relinearize results, which
+        round T times (key_switch.cuh)."""
+        if xs is None or ys is None:
+            raise ValueError("null pointer argument")
+        xs, ys = list(xs), list(ys)
+        if len(xs) != len(ys):
+            raise ValueError("multiply_relinearize_sum takes one y per x")
+        terms = len(xs)
+        if not 1 <= terms <= 32:
+            raise ValueError("Invalid terms!")
+        if key is None or out is None or scratch is None or any(t is None for t in xs + ys):
+            raise ValueError("null pointer argument")
+        cols = self._cols(count)
+        ct = cols * self.q_count * 2
+        self._check_buffers([(t, ct, "x[%d] (2 x count x L x N)" % i) for i, t in enumerate(xs)] +
+                            [(t, ct, "y[%d] (2 x count x L x N)" % i) for i, t in enumerate(ys)] +
+                            [(key, self._key_words(2) if cols else 0, "key (D x 2 x key_mod_count x N)"),
+                             (out, ct, "out (2 x count x L x N)")])
+        _require_gpu(scratch)
+        if int(count) >= 0 and scratch.numel() * scratch.element_size() < self.scratch_bytes(count, 2):
+            raise ValueError("scratch holds fewer than scratch_bytes(count, 2) bytes")
+        x_ptrs = (ctypes.c_void_p * terms)(*[t.data_ptr() for t in xs])
+        y_ptrs = (ctypes.c_void_p * terms)(*[t.data_ptr() for t in ys])
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_multiply_relinearize_sum_u%d" % self.bits)
+        _check(fn(self._h, x_ptrs, y_ptrs, terms, _ptr(key), _ptr(out), int(count), int(bool(output_ntt)),
+                  _ptr(scratch), _stream(stream)))
 
     def close(self):
         if self._h:

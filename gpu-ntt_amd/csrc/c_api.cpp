@@ -1004,6 +1004,18 @@ extern "C"
                 x, y, key, out, count, output_ntt != 0, scratch, static_cast<hipStream_t>(stream));               \
         });                                                                                       \
     }                                                                                             \
+    int gpuntt_keyswitch_plan_multiply_relinearize_sum_##S(const gpuntt_keyswitch_plan* plan,      \
+                                                           const T* const* x_host, const T* const* y_host,        \
+                                                           int terms, const T* key, T* out, int count,            \
+                                                           int output_ntt, void* scratch, void* stream)           \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->multiply_relinearize_sum(            \
+                x_host, y_host, terms, key, out, count, output_ntt != 0, scratch,                 \
+                static_cast<hipStream_t>(stream));                                                \
+        });                                                                                       \
+    }                                                                                             \
     int gpuntt_keyswitch_plan_owns_workspace_##S(const gpuntt_keyswitch_plan* plan)               \
     {                                                                                             \
         GPUNTT_NEED(plan)                                                                         \

@@ -33,6 +33,9 @@
 // multiply_relinearize: tensor_top of relinearize.hip (x1 y1 into the scratch), the plan's own decompose steps on it,
 // inner_product_tensor (the inner product seeded with P (x0 y0) and P (x0 y1 + x1 y0)), then finish over 2 * count stacks
 // (DESIGN.md 3.15).
+//
+// multiply_relinearize_sum: the same sequence with tensor_top_sum and inner_product_tensor_sum of relinearize_sum.hip,
+// which loop over the terms: one key switch and one ModDown for sum_t x_t y_t.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -48,6 +51,7 @@
 #include "hoisted_rotation_internal.hpp"
 #include "launch.hpp"
 #include "relinearize_internal.hpp"
+#include "relinearize_sum_internal.hpp"
 
 namespace gpuntt
 {
@@ -723,6 +727,69 @@ namespace gpuntt
             host::relin_inner_launch<T>(a, key, acc, consts, x, y, args, D, count, L, M, KM, n, true, stream);
             finish(acc, out, 2 * count, output_ntt, stream);
         }
+
+        // xs, ys: host arrays of `terms` pointers to T[2][count][L][N]; everything else as multiply_relinearize
+        void multiply_relinearize_sum(const T* const* xs, const T* const* ys, int terms, const T* key, T* out, int count,
+                                      bool output_ntt, void* scratch, hipStream_t stream) const
+        {
+            need_transforms();
+            const KsScratch s = ks_scratch<T>(L, M, D, n, count, 2); // checks count
+            if (terms < 1 || terms > KEYSWITCH_MAX_TERMS)
+                throw std::invalid_argument("Invalid terms!");
+            if (xs == nullptr || ys == nullptr || key == nullptr || out == nullptr || scratch == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            kern::RelinSumArgs<T> args{};
+            args.terms = terms;
+            for (int t = 0; t < terms; t++)
+            {
+                if (xs[t] == nullptr || ys[t] == nullptr)
+                    throw std::invalid_argument("null pointer argument");
+                args.x[t] = xs[t], args.y[t] = ys[t];
+            }
+            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
+                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            if (count == 0)
+                return;
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T);
+            const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
+            // out may be exactly any x[t] or y[t]: the last read of them (inner_product_tensor_sum) precedes mod_down's
+            // first write on the stream.  Any other overlap is refused
+            if (ks_overlap(scratch, s.total, key, key_bytes) || ks_overlap(out, ct_bytes, key, key_bytes))
+                throw std::invalid_argument("out or the scratch overlaps an operand!");
+            for (int t = 0; t < 2 * terms; t++)
+            {
+                const T* op = t < terms ? xs[t] : ys[t - terms];
+                if (ks_overlap(scratch, s.total, op, ct_bytes) || (ks_overlap(out, ct_bytes, op, ct_bytes) && op != out))
+                    throw std::invalid_argument("out or the scratch overlaps an operand!");
+            }
+            if (ks_overlap(out, ct_bytes, scratch, s.total))
+                throw std::invalid_argument("The scratch overlaps out!");
+            // the batches of the transforms are ints; the grids of mod_up and mod_down: as their own launches check
+            if (static_cast<unsigned long long>(D) * static_cast<unsigned>(count) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
+                throw std::invalid_argument("Invalid count!");
+            if (((cols + kern::KS_NT - 1) / kern::KS_NT) * kern::KS_NT > 0xFFFFFFFFull ||
+                ((2 * cols + kern::BC_NT - 1) / kern::BC_NT) * kern::BC_NT > 0xFFFFFFFFull)
+                throw std::invalid_argument("Invalid count!");
+            for (int m = 0; m < M; m++)
+                args.r.limbs.v[m] = static_cast<unsigned char>(limbs[m]);
+            for (int j = 0; j < L; j++)
+                args.r.p_mod_q[j] = p_mod_q[j], args.r.p_mod_q_shoup[j] = p_mod_q_shoup[j];
+            T* a = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.a);
+            T* d2 = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.c_coeff);
+            T* acc = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.inner_out);
+            const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
+            // the grid limits of both kernels, before the first launch
+            host::relin_sum_top_launch<T>(d2, consts, args, count, L, M, n, false, stream);
+            host::relin_sum_inner_launch<T>(a, key, acc, consts, args, D, count, L, M, KM, n, false, stream);
+
+            host::relin_sum_top_launch<T>(d2, consts, args, count, L, M, n, true, stream);
+            ntt_q_i->execute(d2, d2, count * L, stream);
+            mod_up(d2, a, count, BaseConvMode::centred, stream);
+            ntt_full_f->execute(a, a, D * count * M, stream);
+            host::relin_sum_inner_launch<T>(a, key, acc, consts, args, D, count, L, M, KM, n, true, stream);
+            finish(acc, out, 2 * count, output_ntt, stream);
+        }
     };
 
     template <typename T> int KeySwitchPlan<T>::digits(int q_count, int alpha)
@@ -892,6 +959,15 @@ namespace gpuntt
                                                 int count, bool output_ntt, void* scratch_device, stream_t stream) const
     {
         p_->multiply_relinearize(device_x, device_y, device_key, device_out, count, output_ntt, scratch_device, stream);
+    }
+
+    template <typename T>
+    void KeySwitchPlan<T>::multiply_relinearize_sum(const T* const* device_x_host, const T* const* device_y_host, int terms,
+                                                    const T* device_key, T* device_out, int count, bool output_ntt,
+                                                    void* scratch_device, stream_t stream) const
+    {
+        p_->multiply_relinearize_sum(device_x_host, device_y_host, terms, device_key, device_out, count, output_ntt,
+                                     scratch_device, stream);
     }
     template <typename T>
     void KeySwitchPlan<T>::apply(const T* device_c_in, const T* device_key, T* device_out, int count, int components,

@@ -131,33 +131,6 @@ namespace gpuntt
     {
         namespace
         {
-            // lanes per workgroup and column tiles per polynomial for V columns per lane; throws when `rows` of them
-            // pass what HIP launches in one dimension
-            struct RelinGrid
-            {
-                unsigned nt, tiles, blocks;
-            };
-            RelinGrid relin_grid(int n_power, int V, unsigned long long rows)
-            {
-                const unsigned long long lanes = (1ull << n_power) / V; // per polynomial
-                unsigned nt = 64;
-                while (nt < kern::IP_NT && nt < lanes)
-                    nt *= 2;
-                const unsigned long long tiles = (lanes + nt - 1) / nt;
-                const unsigned long long blocks = tiles * rows;
-                if (blocks * nt > 0xFFFFFFFFull) // HIP caps a launch at 2^32 - 1 work-items per dimension
-                    throw std::invalid_argument("Invalid count!");
-                return RelinGrid{nt, static_cast<unsigned>(tiles), static_cast<unsigned>(blocks)};
-            }
-            // a 16-byte group must stay inside one polynomial and be aligned (every stride is a multiple of N words)
-            template <typename T> bool relin_wide(int n_power, std::initializer_list<const void*> bases)
-            {
-                uintptr_t bits = 0;
-                for (const void* p : bases)
-                    bits |= reinterpret_cast<uintptr_t>(p);
-                return n_power >= (sizeof(T) == 8 ? 1 : 2) && (bits & 15u) == 0;
-            }
-
             template <typename T, int V>
             void relin_top_as(const T* x1, const T* y1, T* d2, const T* consts, int count, int L, int M, int n_power,
                               bool enqueue, hipStream_t stream)

@@ -136,6 +136,48 @@
 //     anything is launched: any other overlap of out or the scratch with an operand or with each other, a null pointer, a
 //     scratch that is not 256-byte aligned, count < 0, a count beyond the grid and batch limits rotate_hoisted checks, a
 //     plan built without transforms
+//   multiply_relinearize_sum(x, y, terms, key, out, count, output_ntt, scratch):  sum_t x_t * y_t over `terms` pairs of
+//     two-component ciphertexts with ONE key switch and ONE ModDown ("lazy relinearization"): an encrypted dot product, a
+//     matrix-vector product, a convolution, the power-basis terms of a polynomial evaluation.  x, y = HOST arrays of
+//     `terms` device pointers (as rotate_hoisted takes its keys), 1 <= terms <= KEYSWITCH_MAX_TERMS = 32; each pointer a
+//     batch T[2][count][L][N] in NTT form over the q-base, every word any value, read modulo q_m.  y[t] may be x[t] (a
+//     square) and the same pointer may appear in several terms.  key, out, count, output_ntt and the scratch are exactly
+//     multiply_relinearize's; the scratch is the existing scratch_bytes(count, 2).
+//     DEFINITION, word for word, through the calls that exist beside it:
+//       1. for every r, m < L and column j the canonical residues
+//            d0 = (sum_t x0_t y0_t) mod q_m,   d1 = (sum_t x0_t y1_t + x1_t y0_t) mod q_m,   d2 = (sum_t x1_t y1_t) mod q_m
+//          -- each what a q-base InnerProductPlan::multiply_accumulate gives (D = terms for d0 and d2, D = 2 * terms for
+//          d1 -- the cap on terms keeps that inside INNERPROD_MAX_DIGITS -- C = 1, the polynomials of y in the key's
+//          place),
+//       2. k = apply(d2, key, count, components = 2, input_ntt = true, output_ntt),
+//       3. out[c] = (k[c] + d_c) mod q_m; with output_ntt false d_c is inverse-transformed over the q-base before the
+//          addition.
+//     With terms = 1 this is multiply_relinearize's definition, and the two calls return the same words.
+//     What runs instead is multiply_relinearize's sequence with the two kernels that loop over t (relinearize_sum.hip):
+//       tensor_top_sum: d2 into the scratch's c_coeff region (one exact mac per term, ONE fold);
+//       the q-base INTT in place, mod_up (centred), the full-base NTT over D * count * M polynomials;
+//       inner_product_tensor_sum: acc[c][r][m][j] = (sum_d a[d][r][m][j] * key[d][c][limb(m)][j]
+//                                 + [m < L] (P mod q_m) * d_c[r][m][j]) mod q_m -- d0 and d1 summed over t on the fly in
+//                                 the exact accumulator (at most one carry per mac, D + 3 * terms <= 160 of them), never
+//                                 written to memory; the K special limbs load nothing of x or y;
+//       finish over 2 * count stacks.
+//     The key switch (INTT, ModUp, NTT over D * M, inner product, INTT over M, ModDown, NTT) does not grow with terms;
+//     6 * terms + 1 passes over count * L * N words remain.
+//     NOT word for word sum_t multiply_relinearize(x_t, y_t): that expression decomposes `terms` top terms and rounds
+//     `terms` times, this one decomposes their sum and rounds once.  ModUp is not additive, so with an arbitrary key the
+//     two are unrelated words and no bound on their difference is promised; only the decrypted values agree, and this
+//     call carries the noise of one key switch and one ModDown instead of `terms`.
+//     Exactness of the fold is multiply_relinearize's argument, unchanged by the sum: P d_c vanishes in the special
+//     limbs, so mod_down's conv_j is what it is for step 2's accumulators alone, and
+//       (c_j + P d - conv_j) P^-1 = d + (c_j - conv_j) P^-1  (mod q_j),
+//     the right side is step 3's sum and both sides are canonical residues: the same word, also after the linear,
+//     canonical forward NTT.
+//     Allocates nothing, never synchronises: one stream, capturable as it is.  count = 0: nothing is launched.  out may
+//     be exactly any one of the x[t] or y[t]: every read of them (the two kernels above) precedes mod_down's first write
+//     on the stream.  std::invalid_argument, before anything is launched: terms outside [1, 32], a null array, a null
+//     entry, a null key / out / scratch, a scratch that is not 256-byte aligned, count < 0, a count beyond the limits
+//     multiply_relinearize checks, any other overlap of out or the scratch with an operand or with each other, a plan
+//     built without transforms
 //
 //   * ranges: 1 <= L, 1 <= K, M = L + K <= 64, alpha >= 1, 1 <= components <= 4, count >= 0 and stacks >= 0 (0: nothing
 //     happens), n_power in [1, 28], M <= key_mod_count <= 256.  A plan is built for ONE level (one L) and one ring; a
@@ -171,6 +213,8 @@
 
 namespace gpuntt
 {
+    constexpr int KEYSWITCH_MAX_TERMS = 32; // multiply_relinearize_sum: pairs of ciphertexts per call
+
     // The plan's constants as the host derived them (KeySwitchPlan::constants, gpuntt_keyswitch_constants_*): every
     // pointer is a caller array of the stated length.  d(i) = i / alpha is the digit of q-limb i.
     template <typename T> struct KeySwitchConstants
@@ -233,6 +277,9 @@ namespace gpuntt
 
         void multiply_relinearize(const T* device_x, const T* device_y, const T* device_key, T* device_out, int count,
                                   bool output_ntt, void* scratch_device, stream_t stream) const;
+        void multiply_relinearize_sum(const T* const* device_x_host, const T* const* device_y_host, int terms,
+                                      const T* device_key, T* device_out, int count, bool output_ntt,
+                                      void* scratch_device, stream_t stream) const;
 
         int q_count() const;
         int p_count() const;

@@ -394,6 +394,13 @@ extern "C"
      *                  exactly x or exactly y); the scratch is gpuntt_keyswitch_plan_scratch_bytes_*(count, 2) bytes,
      *                  256-byte aligned.  out equals the three pointwise products, apply on x1 y1 and the two additions
      *                  word for word (key_switch.cuh)
+     *   multiply_relinearize_sum  sum_t x_t * y_t over `terms` such pairs with ONE key switch and ONE ModDown (lazy
+     *                  relinearization): x_host, y_host HOST arrays of `terms` device pointers, 1 <= terms <= 32, each
+     *                  T[2][count][L][N] in NTT form (any words; y_host[t] may be x_host[t], a pointer may appear in
+     *                  several terms); key, out, count, output_ntt and the scratch as for multiply_relinearize; out may be
+     *                  exactly any one of the operands.  out equals the three summed tensor terms, apply on the top one and
+     *                  the two additions word for word; with terms = 1 it equals multiply_relinearize; it is NOT word for
+     *                  word the sum of `terms` multiply_relinearize results, which round `terms` times (key_switch.cuh)
      * No call allocates or synchronises.
      * host only (no GPU): constants -- arrays_host holds 18 caller arrays in the order of KeySwitchConstants<T>
      * (up_qhat_inv[L], up_qhat_inv_shoup[L], up_matrix[L][M], up_q_mod[D][M], up_recip[L], up_bit_length[L],
@@ -438,6 +445,10 @@ extern "C"
     int gpuntt_keyswitch_plan_multiply_relinearize_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* x, const uint32_t* y,
                                                        const uint32_t* key, uint32_t* out, int count, int output_ntt,
                                                        void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_multiply_relinearize_sum_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* const* x_host,
+                                                           const uint32_t* const* y_host, int terms, const uint32_t* key,
+                                                           uint32_t* out, int count, int output_ntt, void* scratch,
+                                                           void* stream);
     int gpuntt_keyswitch_plan_owns_workspace_u32(const gpuntt_keyswitch_plan* plan); /* 1 / 0, negative on error */
     int gpuntt_keyswitch_plan_destroy_u32(gpuntt_keyswitch_plan* plan);
     int gpuntt_keyswitch_constants_u32(const gpuntt_modulus32* q_moduli_host, int q_count, const gpuntt_modulus32* p_moduli_host, int p_count,
@@ -483,6 +494,10 @@ extern "C"
     int gpuntt_keyswitch_plan_multiply_relinearize_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* x, const uint64_t* y,
                                                        const uint64_t* key, uint64_t* out, int count, int output_ntt,
                                                        void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_multiply_relinearize_sum_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* const* x_host,
+                                                           const uint64_t* const* y_host, int terms, const uint64_t* key,
+                                                           uint64_t* out, int count, int output_ntt, void* scratch,
+                                                           void* stream);
     int gpuntt_keyswitch_plan_owns_workspace_u64(const gpuntt_keyswitch_plan* plan); /* 1 / 0, negative on error */
     int gpuntt_keyswitch_plan_destroy_u64(gpuntt_keyswitch_plan* plan);
     int gpuntt_keyswitch_constants_u64(const gpuntt_modulus64* q_moduli_host, int q_count, const gpuntt_modulus64* p_moduli_host, int p_count,
