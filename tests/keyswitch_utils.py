@@ -1,6 +1,6 @@
 """Shared by the hybrid key switching tests (include/gpuntt/rns/key_switch.cuh): the digit partition, ModUp and ModDown
 restated in Python integers from the formulas of base_conversion.cuh (numpy object arrays: one Python int per word), CRT
-reconstruction and the negacyclic product in Python integers."""
+reconstruction and the negacyclic product in Python integers, and the sequence of public calls that apply stands for."""
 import math
 
 import numpy as np
@@ -99,3 +99,38 @@ def planted_input(rng, bits, qs, shape):
     for i, q in enumerate(qs):  # every limb sees its own extremes
         x[0, i, 0], x[-1, i, -1] = q - 1, top
     return x
+
+
+def tdtype(bits):
+    import torch
+    return torch.int64 if bits == 64 else torch.int32
+
+
+def ones(bits, size, offset=0):
+    import torch
+    return torch.full((size + offset,), -1, dtype=tdtype(bits), device="cuda:0")[offset:]
+
+
+def public_sequence(g, plan, inner, st, c_in, key, count, C, input_ntt, output_ntt, km=None, limbs=None):
+    """the calls apply stands for, through the existing bindings"""
+    import torch
+    bits, n_power, L, M, D = plan.bits, plan.n_power, plan.q_count, plan.mod_count, plan.digits
+    n = 1 << n_power
+    cfg_f = g.ntt_rns_configuration(n_power=n_power, reduction_poly=g.X_N_plus)
+    cfg_i = g.ntt_rns_configuration(n_power=n_power, ntt_type=g.INVERSE, reduction_poly=g.X_N_plus,
+                                    mod_inverse=st["d_ninv"])
+    coeff = c_in.clone()
+    if input_ntt:
+        g.GPU_INTT_Inplace(coeff, st["inv"], st["mods"], cfg_i, count * L, L)
+    a = ones(bits, D * count * M * n)
+    plan.mod_up(coeff, a, count, g.CENTRED)
+    g.GPU_NTT_Inplace(a, st["fwd"], st["mods"], cfg_f, D * count * M, M)
+    acc = ones(bits, C * count * M * n)
+    inner.multiply_accumulate(a, key, acc, n_power, D, C, count, False, km, limbs)
+    g.GPU_INTT_Inplace(acc, st["inv"], st["mods"], cfg_i, C * count * M, M)
+    out = ones(bits, C * count * L * n)
+    plan.mod_down(acc, out, C * count)
+    if output_ntt:
+        g.GPU_NTT_Inplace(out, st["fwd"], st["mods"], cfg_f, C * count * L, L)
+    torch.cuda.synchronize()
+    return out, a

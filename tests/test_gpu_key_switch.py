@@ -15,7 +15,8 @@ import pytest
 
 from gpu_utils import MergeCase, distinct_factors_scaled
 from innerprod_utils import from_words, moduli, random_words, words
-from keyswitch_utils import SHAPES, centre, crt, negacyclic, partition, planted_input, ref_mod_down, ref_mod_up
+from keyswitch_utils import (SHAPES, centre, crt, negacyclic, ones, partition, planted_input, public_sequence, ref_mod_down,
+                             ref_mod_up, tdtype)
 
 pytestmark = pytest.mark.gpu
 
@@ -34,11 +35,6 @@ def bases(bits, L, K):
     return ms[:L], ms[L:L + K]
 
 
-def tdtype(bits):
-    import torch
-    return torch.int64 if bits == 64 else torch.int32
-
-
 def dev(g, x, bits, offset=0):
     """object array -> device tensor; offset: words by which the base pointer is moved off its 16-byte alignment"""
     import torch
@@ -46,11 +42,6 @@ def dev(g, x, bits, offset=0):
     t = torch.zeros(w.size + offset, dtype=tdtype(bits), device="cuda:0")
     t[offset:] = g.to_device(w)
     return t[offset:]
-
-
-def ones(bits, size, offset=0):
-    import torch
-    return torch.full((size + offset,), -1, dtype=tdtype(bits), device="cuda:0")[offset:]
 
 
 def expected_mod_up(g, bits, qs, ps, alpha, x, n_power, count, mode):
@@ -236,31 +227,6 @@ def ring(g, bits, n_power, M=8, wide=False):
 def make_plan(g, st, L, alpha, n_power, bits, **kw):
     return g.KeySwitchPlan(st["moduli"][:L], st["moduli"][L:], alpha, n_power, st["fwd"], st["inv"], st["n_inv"],
                            g.X_N_plus, bits=bits, **kw)
-
-
-def public_sequence(g, plan, inner, st, c_in, key, count, C, input_ntt, output_ntt, km=None, limbs=None):
-    """the calls apply stands for, through the existing bindings"""
-    import torch
-    bits, n_power, L, M, D = plan.bits, plan.n_power, plan.q_count, plan.mod_count, plan.digits
-    n = 1 << n_power
-    cfg_f = g.ntt_rns_configuration(n_power=n_power, reduction_poly=g.X_N_plus)
-    cfg_i = g.ntt_rns_configuration(n_power=n_power, ntt_type=g.INVERSE, reduction_poly=g.X_N_plus,
-                                    mod_inverse=st["d_ninv"])
-    coeff = c_in.clone()
-    if input_ntt:
-        g.GPU_INTT_Inplace(coeff, st["inv"], st["mods"], cfg_i, count * L, L)
-    a = ones(bits, D * count * M * n)
-    plan.mod_up(coeff, a, count, g.CENTRED)
-    g.GPU_NTT_Inplace(a, st["fwd"], st["mods"], cfg_f, D * count * M, M)
-    acc = ones(bits, C * count * M * n)
-    inner.multiply_accumulate(a, key, acc, n_power, D, C, count, False, km, limbs)
-    g.GPU_INTT_Inplace(acc, st["inv"], st["mods"], cfg_i, C * count * M, M)
-    out = ones(bits, C * count * L * n)
-    plan.mod_down(acc, out, C * count)
-    if output_ntt:
-        g.GPU_NTT_Inplace(out, st["fwd"], st["mods"], cfg_f, C * count * L, L)
-    torch.cuda.synchronize()
-    return out, a
 
 
 def scratch_for(plan, count, C, short=0):
