@@ -156,6 +156,14 @@ def contig_p4_launches():
     return int(fn())
 
 
+def alloc_count():
+    """gpuntt_test_alloc_count (csrc/test_hooks.h): hipMalloc / hipHostMalloc / hipFree / hipHostFree calls of the scratch
+    chains and the family prediction's pool since the library was loaded."""
+    fn = load_library().gpuntt_test_alloc_count
+    fn.restype = ctypes.c_ulonglong
+    return int(fn())
+
+
 def scratch_stats():
     """gpuntt_test_scratch_stats (csrc/test_hooks.h): the twiddle scratch of captured calls, which their graph owns."""
     out = (ctypes.c_ulonglong * 6)()
@@ -176,8 +184,13 @@ class launch_log:
     def __exit__(self, *exc):
         lib = load_library()
         buf = ctypes.create_string_buffer(1 << 16)
-        lib.gpuntt_test_launch_log_take(buf, len(buf))
+        need = lib.gpuntt_test_launch_log_take(buf, len(buf))
+        if need > len(buf):  # nothing was copied and the log was kept: take it again with the room it needs
+            buf = ctypes.create_string_buffer(need)
+            need = lib.gpuntt_test_launch_log_take(buf, len(buf))
+        assert 0 < need <= len(buf), "launch log of %d bytes does not fit %d" % (need, len(buf))
         self.kernels = buf.value.decode().split()
+        assert need == len(buf.value) + 1, "launch log cut: %d bytes of %d" % (len(buf.value) + 1, need)
         return False
 
 

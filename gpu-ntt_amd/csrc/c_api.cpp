@@ -26,7 +26,8 @@ namespace gpuntt
         // prep.hip: test hooks (csrc/test_hooks.h)
         bool set_test_hook(const char* name, const char* value);
         void launch_log_start();
-        std::string launch_log_take();
+        size_t launch_log_take(std::string& out, size_t capacity);
+        unsigned long long alloc_count();
         void scratch_stats(unsigned long long out[6]);
         unsigned long long contig_p4_launches();
     } // namespace host
@@ -503,15 +504,19 @@ extern "C"
     }
     int gpuntt_test_launch_log_take(char* buf, int capacity)
     {
-        const std::string s = host::launch_log_take();
+        // never a cut list: a buffer too small for the names and their terminator gets an empty string, and the log is
+        // kept for a second take with the capacity returned here
+        std::string s;
+        const size_t room = (buf != nullptr && capacity > 0) ? static_cast<size_t>(capacity - 1) : 0;
+        const size_t need = host::launch_log_take(s, room);
         if (buf != nullptr && capacity > 0)
         {
-            const size_t n = std::min(s.size(), static_cast<size_t>(capacity - 1));
-            std::memcpy(buf, s.data(), n);
-            buf[n] = '\0';
+            std::memcpy(buf, s.data(), s.size());
+            buf[s.size()] = '\0';
         }
-        return static_cast<int>(s.size()) + 1;
+        return static_cast<int>(need) + 1;
     }
+    unsigned long long gpuntt_test_alloc_count(void) { return host::alloc_count(); }
 
     int gpuntt_test_scratch_stats(unsigned long long out[6])
     {

@@ -158,7 +158,9 @@ namespace gpuntt
         // only after 16 calls in a row that needed less.  A stack the enqueued family cannot serve (first call of a stack
         // with a 61- / 62-bit prime, moduli rewritten in place with wider ones, a captured graph replayed after the moduli
         // changed, moduli outside the documented domain) is transformed by the preparation kernel ITSELF (kern::SlowArgs:
-        // slow, never wrong) -- no generic launch behind any Merge call.  all_families: every lazy family behind the exact
+        // slow, never wrong) -- no generic launch behind any Merge call.  A moduli buffer never seen before starts from what
+        // finished calls of the same SHAPE needed in other buffers (the shape hint; the rules are rns_predict.hpp): on rings
+        // below 2^17 a caller with a fresh buffer per call meets that fall-back once.  all_families: every lazy family behind the exact
         // state (option rns_predict = 0, path = fast-strict, a full prediction table); only the 4-step entry points keep the
         // generic kernels behind their calls (table check).
         struct RnsGuess
@@ -166,7 +168,8 @@ namespace gpuntt
             unsigned state;      // predicted go-flag state (kern::GO_*); meaningful when !all_families
             bool all_families;
             unsigned* state_out; // device pointer of the host-mapped word for the preparation kernel, or nullptr
-            bool unsure = false;         // nothing is known about this stack yet (first call with this moduli buffer), or its last
+            bool unsure = false;         // nothing is known about this stack yet (first call with this moduli buffer, hinted by
+                                         // its shape or not: rings from 2^17 cast the wide net once per buffer), or its last
                                          // call found moduli outside the lazy families' domain
             bool shadow_generic = false; // set by the entry point: the generic kernels are enqueued behind the call, so the
                                          // preparation kernel must not transform the batch itself
@@ -375,7 +378,10 @@ namespace gpuntt
         // rns_force_fallback, u32_e32 -- and everything set_option takes
         bool set_test_hook(const char* name, const char* value);
         void launch_log_start();
-        std::string launch_log_take(); // space-separated kernel names ("merge_pass_lazy:31 prep_twiddles ..."), stops the log
+        // stops the log; space-separated kernel names ("prep_twiddles merge_pass_lazy:31 ...") to `out`, the log cleared --
+        // or, when they are longer than `capacity`, nothing handed out and the log kept.  Returns their length
+        size_t launch_log_take(std::string& out, size_t capacity);
+        unsigned long long alloc_count(); // test hook: hipMalloc / hipHostMalloc / hipFree / hipHostFree calls of prep.hip
         void scratch_stats(unsigned long long out[6]); // test hook: graph-owned scratch of capture chains (prep.hip)
         // 0 size heuristic, 1 generic kernels, 2 fast, 3 fast-strict (a call the fast kernels cannot take throws),
         // 4 generic-capped (4-step RNS overload: generic kernels on the capped shadow grid)

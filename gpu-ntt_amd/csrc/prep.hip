@@ -11,6 +11,7 @@
 // an RNS stack).  Nothing is cached between calls, so a caller that rewrites its table in place
 // is always honoured.
 #include <atomic>
+#include <cctype>
 #include <cstdlib>
 #include <initializer_list>
 #include <string>
@@ -22,6 +23,7 @@
 #include <vector>
 
 #include "lazy_launch.hpp"
+#include "rns_predict.hpp"
 
 namespace gpuntt
 {
@@ -679,10 +681,14 @@ namespace gpuntt
                     return false;
                 const std::string k(name), v(value);
                 // numeric values: the whole string must be a number of the option's documented set -- "abc" or "7" are
-                // refused (false), not silently turned into 0 / the default
+                // refused (false), not silently turned into 0 / the default.  Numbers are DECIMAL ("010" is ten, a leading
+                // zero is no octal prefix); a mask may be written in hexadecimal behind 0x.  No sign, no white space
+                const bool hex = value[0] == '0' && (value[1] == 'x' || value[1] == 'X');
+                const char* digits = hex ? value + 2 : value;
                 char* end = nullptr;
-                const long lv = std::strtol(value, &end, 0);
-                const bool is_num = end != value && *end == '\0';
+                const long lv = std::strtol(digits, &end, hex ? 16 : 10);
+                const bool is_num = (hex ? std::isxdigit(static_cast<unsigned char>(digits[0]))
+                                         : std::isdigit(static_cast<unsigned char>(digits[0]))) != 0 && *end == '\0';
                 const int iv = static_cast<int>(lv);
                 const bool bit = is_num && (lv == 0 || lv == 1);
                 std::lock_guard<std::mutex> lock(g_opt_mutex);
@@ -722,7 +728,7 @@ namespace gpuntt
                     // like keyswitch_split a process-wide knob outside the per-call snapshot that changes no output word.
                     // The same value forces the destination chunk of inner_product_galois_sum, inside its cap of 256 slots
                     keyswitch_set_hoist_chunk(iv);
-                else if (test_hooks && k == "reset_predictions" && bit)
+                else if (test_hooks && k == "reset_predictions" && is_num && lv == 1)
                     g_reset_predictions.store(1, std::memory_order_relaxed); // rns_guess forgets every stack it has seen
                 else
                     return false;
@@ -783,16 +789,35 @@ namespace gpuntt
             g_log.clear();
             g_log_on.store(1, std::memory_order_relaxed);
         }
-        std::string launch_log_take()
+        // stops the log.  The names since start, space-separated, go to `out` and the log is cleared -- unless they are
+        // longer than `capacity`: then nothing is handed out and the log is KEPT for a second take with room for the
+        // returned length.  Returns the length of the names (without a terminator)
+        size_t launch_log_take(std::string& out, size_t capacity)
         {
             std::lock_guard<std::mutex> lock(g_log_mutex);
             g_log_on.store(0, std::memory_order_relaxed);
-            std::string out;
+            size_t need = 0;
+            for (const std::string& e : g_log)
+                need += e.size() + 1;
+            need -= need != 0 ? 1 : 0;
+            out.clear();
+            if (need > capacity)
+                return need;
+            out.reserve(need);
             for (const std::string& e : g_log)
                 out += (out.empty() ? "" : " ") + e;
             g_log.clear();
-            return out;
+            return need;
         }
+
+        // test hook: hipMalloc / hipHostMalloc / hipFree / hipHostFree calls of this file -- the scratch chains and the
+        // prediction pool -- since the library was loaded.  A steady-state call makes none
+        namespace
+        {
+            std::atomic<unsigned long long> g_alloc_calls{0};
+            inline void note_alloc_call() { g_alloc_calls.fetch_add(1, std::memory_order_relaxed); }
+        } // namespace
+        unsigned long long alloc_count() { return g_alloc_calls.load(std::memory_order_relaxed); }
 
         namespace
         {
@@ -1049,7 +1074,10 @@ namespace gpuntt
                 std::this_thread::yield();
             }
             for (void* p : doomed)
+            {
+                note_alloc_call();
                 (void) hipFree(p); // synchronises the device
+            }
         }
 
         void scratch_stats(unsigned long long out[6])
@@ -1065,40 +1093,38 @@ namespace gpuntt
         }
 
         // ---- which lazy family will a drop-in RNS call need?  (RnsGuess, lazy_launch.hpp) ------------------------------
+        // The RULES -- slots, what a slot predicts, widening and narrowing, the unsure flag, recycling of the words, the
+        // shape hint -- are host code without a HIP call: rns_predict.hpp (tests/cpp/rns_predict_check.cpp walks them
+        // without a GPU).  Here: the words themselves.
+        static_assert(predict::GO_GENERIC == kern::GO_GENERIC && predict::GO_LAZY == kern::GO_LAZY &&
+                          predict::GO_LAZY_8Q == kern::GO_LAZY_8Q && predict::GO_LAZY_4Q == kern::GO_LAZY_4Q &&
+                          predict::GO_LAZY_31Q == kern::GO_LAZY_31Q,
+                      "rns_predict.hpp restates the go-flag states of merge_lazy_kernels.hpp");
+        static_assert(predict::family_rank(0u) == kern::family_rank(0u) && predict::family_rank(1u) == kern::family_rank(1u) &&
+                          predict::family_rank(2u) == kern::family_rank(2u) && predict::family_rank(3u) == kern::family_rank(3u) &&
+                          predict::family_rank(4u) == kern::family_rank(4u),
+                      "rns_predict.hpp restates kern::family_rank");
         namespace
         {
-            struct GuessSlot
-            {
-                int word = -1; // index of the slot's word in its device's pool of host-mapped words
-                unsigned predicted = kern::GO_LAZY;
-                bool have_prediction = false;
-                int streak = 0;                          // calls in a row that needed a narrower family than the predicted one
-                unsigned streak_state = kern::GO_LAZY;   // the widest of them
-                unsigned long long last_use = 0;
-                bool generic_seen = false; // the last finished call found a modulus outside the lazy families' domain
-            };
-            // one pinned, device-mapped allocation per device: GUESS_MAX_KEYS words, one cache line apart.  Never freed
+            // one pinned, device-mapped allocation per device: predict::MAX_KEYS words, one cache line apart.  Never freed
             // (captured graphs keep writing their state to the word they were captured with; a word that has been handed to
-            // another stack meanwhile only costs that stack a wrong prediction, which the generic kernels behind it absorb)
+            // another stack meanwhile only costs that stack a wrong prediction, which the preparation kernel's fall-back or
+            // the generic kernels behind the call absorb)
             struct GuessPool
             {
                 unsigned* host = nullptr;
                 unsigned* dev = nullptr;
             };
-            constexpr size_t GUESS_MAX_KEYS = 256;
-            constexpr size_t GUESS_STRIDE = 16; // words
-            constexpr unsigned STATE_UNKNOWN = 0xffffffffu;
             std::mutex g_guess_mutex;
             std::map<int, GuessPool> g_guess_pool;
-            // (device, moduli, mod_order, mod_count, word size | 4-step entry | direction): forward and inverse calls of one
-            // stack may need different families (31 q serves forward transforms only), a *_Modulus_Ordered call uses the
-            // subset its order array names; the Merge entry points otherwise share one slot per stack
-            std::map<std::tuple<int, const void*, const void*, int, int>, GuessSlot> g_guess;
-            // what stacks of the same SHAPE (device, mod_count, word size | entry | direction, ordered or not) needed last,
-            // whatever buffer they lived in: the first prediction for a moduli buffer never seen before -- a caller that
-            // uploads its stack to a fresh buffer per call keeps its family
-            std::map<std::tuple<int, int, int, bool>, unsigned> g_shape_hint;
-            unsigned long long g_guess_clock = 0;
+            // slots per moduli buffer and the SHAPE HINT (rns_predict.hpp).  A slot created for a moduli buffer never seen
+            // before starts from what finished calls of the same shape -- in whatever buffers -- needed: creating it looks at
+            // the words of the last predict::HINT_RECENT slots of that shape, so a caller that uploads its stack to a fresh
+            // buffer per call meets the in-preparation fall-back once, not on every call.  That is what the hint saves, on
+            // rings below 2^17.  A hinted slot stays `unsure` until its own word has spoken, so on rings from 2^17 every
+            // buffer never seen before still casts the wide net (merge_ntt.hip: cast_wide_net), once per buffer: a wrong
+            // hint would have no cheap fall-back there
+            predict::Table g_guess;
         } // namespace
 
         static bool rns_predict_enabled(); // option rns_predict (defined with the options below)
@@ -1114,90 +1140,35 @@ namespace gpuntt
                 return gss;
             std::lock_guard<std::mutex> lock(g_guess_mutex);
             if (g_reset_predictions.exchange(0, std::memory_order_relaxed) != 0)
-            {
-                g_guess.clear(); // (the host-mapped words stay: graphs captured earlier keep writing to theirs)
-                g_shape_hint.clear();
-            }
+                g_guess.reset(); // (the host-mapped words stay: graphs captured earlier keep writing to theirs)
             GuessPool& pool = g_guess_pool[dev];
             if (pool.host == nullptr)
             {
                 void* hp = nullptr;
                 void* dp = nullptr;
-                if (hipHostMalloc(&hp, sizeof(unsigned) * GUESS_STRIDE * GUESS_MAX_KEYS, hipHostMallocMapped) != hipSuccess ||
+                note_alloc_call();
+                if (hipHostMalloc(&hp, sizeof(unsigned) * predict::STRIDE * predict::MAX_KEYS, hipHostMallocMapped) != hipSuccess ||
                     hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess)
                 {
                     (void) hipGetLastError(); // (not during a stream capture, or no pinned memory left): every family
                     if (hp != nullptr)
+                    {
+                        note_alloc_call();
                         (void) hipHostFree(hp);
+                    }
                     return gss;
                 }
                 pool.host = static_cast<unsigned*>(hp);
                 pool.dev = static_cast<unsigned*>(dp);
-                for (size_t i = 0; i < GUESS_MAX_KEYS; i++)
-                    reinterpret_cast<volatile unsigned*>(pool.host)[i * GUESS_STRIDE] = STATE_UNKNOWN;
+                for (size_t i = 0; i < predict::MAX_KEYS; i++)
+                    reinterpret_cast<volatile unsigned*>(pool.host)[i * predict::STRIDE] = predict::STATE_UNKNOWN;
             }
-            const auto key = std::make_tuple(dev, moduli_device, order, mod_count, word_bytes | (inverse ? 0x100 : 0));
-            auto it = g_guess.find(key);
-            if (it == g_guess.end())
-            {
-                GuessSlot slot;
-                size_t on_dev = 0;
-                auto oldest = g_guess.end();
-                for (auto jt = g_guess.begin(); jt != g_guess.end(); ++jt)
-                    if (std::get<0>(jt->first) == dev)
-                    {
-                        on_dev++;
-                        if (oldest == g_guess.end() || jt->second.last_use < oldest->second.last_use)
-                            oldest = jt;
-                    }
-                if (on_dev < GUESS_MAX_KEYS)
-                    slot.word = static_cast<int>(on_dev); // words are handed out in order and only recycled below
-                else
-                {
-                    slot.word = oldest->second.word; // table full: the least recently used stack gives up its word
-                    g_guess.erase(oldest);
-                }
-                reinterpret_cast<volatile unsigned*>(pool.host)[slot.word * GUESS_STRIDE] = STATE_UNKNOWN;
-                const auto hint = g_shape_hint.find(std::make_tuple(dev, mod_count, std::get<4>(key), order != nullptr));
-                if (hint != g_shape_hint.end())
-                    slot.predicted = hint->second;
-                it = g_guess.emplace(key, slot).first;
-            }
-            GuessSlot& s = it->second;
-            s.last_use = ++g_guess_clock;
-            const unsigned seen = reinterpret_cast<volatile unsigned*>(pool.host)[s.word * GUESS_STRIDE];
-            if (seen != STATE_UNKNOWN && seen <= kern::GO_LAZY_31Q && (exact || seen != kern::GO_GENERIC))
-            {
-                // the state some earlier call of this stack found (the last one that has finished).  The enqueued family
-                // serves every narrower stack too, so: widen at once, narrow after 16 calls in a row that needed less
-                const int r_seen = kern::family_rank(seen), r_now = kern::family_rank(s.predicted);
-                if (!s.have_prediction || r_seen > r_now || exact)
-                {
-                    s.predicted = seen;
-                    s.streak = 0;
-                }
-                else if (r_seen == r_now)
-                    s.streak = 0;
-                else
-                {
-                    if (s.streak == 0 || r_seen > kern::family_rank(s.streak_state))
-                        s.streak_state = seen;
-                    if (++s.streak >= 16)
-                    {
-                        s.predicted = s.streak_state;
-                        s.streak = 0;
-                    }
-                }
-                s.have_prediction = true;
-                s.generic_seen = false;
-                g_shape_hint[std::make_tuple(dev, mod_count, std::get<4>(key), order != nullptr)] = s.predicted;
-            }
-            else if (seen == kern::GO_GENERIC)
-                s.generic_seen = true;
-            gss.unsure = !s.have_prediction || s.generic_seen;
-            gss.state_out = pool.dev + s.word * GUESS_STRIDE;
+            const predict::Answer a = g_guess.guess(reinterpret_cast<volatile unsigned*>(pool.host), dev, moduli_device, order,
+                                                    mod_count, word_bytes | (inverse ? 0x100 : 0), exact);
+            gss.unsure = a.unsure;
+            gss.state_out = pool.dev + a.word * predict::STRIDE;
             gss.all_families = false;
-            gss.state = s.predicted;
+            gss.state = a.state;
             return gss;
         }
 
@@ -1303,7 +1274,10 @@ namespace gpuntt
                     }
                 }
                 if (fresh == nullptr)
+                {
+                    note_alloc_call();
                     err = hipMalloc(&fresh, WS_HEADER + want);
+                }
                 if (capturing)
                     (void) hipThreadExchangeStreamCaptureMode(&mode);
                 if (err == hipSuccess && capturing)
@@ -1313,7 +1287,10 @@ namespace gpuntt
                 {
                     err = hipMemsetAsync(fresh, 0xff, WS_HEADER, stream);
                     if (err != hipSuccess)
+                    {
+                        note_alloc_call();
                         (void) hipFree(fresh);
+                    }
                 }
                 if (err != hipSuccess)
                 {

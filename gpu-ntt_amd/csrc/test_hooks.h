@@ -19,7 +19,12 @@
  *       reset_predictions = 1    the family prediction of the RNS overloads forgets every stack it has seen
  *   gpuntt_test_launch_log_start()      start recording the kernel of every launch the library enqueues (all threads)
  *   gpuntt_test_launch_log_take(buf, n) stop; the kernels since start, space-separated ("prep_twiddles merge_pass_lazy:31 ..."),
- *                                       fast kernels with their lazy range behind a colon; returns the length needed
+ *                                       fast kernels with their lazy range behind a colon; returns the capacity needed
+ *                                       (terminator included).  Never a cut list: when n is smaller than that, buf gets an
+ *                                       empty string and the log is KEPT -- take again with the returned capacity
+ *   gpuntt_test_alloc_count()           hipMalloc / hipHostMalloc / hipFree / hipHostFree calls the scratch chains and the
+ *                                       family prediction's pool of host-mapped words (prep.hip) have made since the
+ *                                       library was loaded: a steady-state call makes none
  *   gpuntt_test_scratch_stats(out[6])   the twiddle scratch of captured calls, which their graph owns (prep.hip): buffers handed to
  *                                       a graph, of those reported dead by their graph, buffers pooled now, buffers re-used from
  *                                       the pool, chains erased, chains alive
@@ -44,6 +49,7 @@ extern "C"
     int gpuntt_test_launch_log_take(char* buf, int capacity);
     int gpuntt_test_scratch_stats(unsigned long long out[6]);
     unsigned long long gpuntt_test_contig_p4_launches(void);
+    unsigned long long gpuntt_test_alloc_count(void);
     int gpuntt_test_keyswitch_hoist_chunk(int word_bytes, int digits, int n_power);
     int gpuntt_test_keyswitch_hoist_sum_chunk(int word_bytes, int digits, int n_power);
 #ifdef __cplusplus

@@ -18,6 +18,8 @@ Row fields
   tables    4-step: "ok" | "vetoed" (one W word changed)
   predict   RNS overloads: "unknown" (moduli buffer never seen, no stack of this shape seen either), "right" (third call
             of the same buffer), "wrong" (the buffer held a [60, 60] stack for three calls, then was rewritten in place)
+            "shape seen" (moduli buffer never seen, but a call of the same stack in ANOTHER buffer has finished: the shape
+            hint, csrc/rns_predict.hpp)
   hooks     options / test hooks set for the call, e.g. {"path": "generic"}
   launches  kernels the call enqueues, in order (launch log; fast kernels carry their lazy range: 0 = the word size's
             default, 31 / 8 / 4)
@@ -75,6 +77,11 @@ ROWS = [
          launches=["prep_twiddles", "merge_pass_lazy:4", "merge_pass_lazy:4"], serves="lazy:4"),
     dict(id="rns u64 2^13 [60,61] wrong (rewritten in place)", entry="merge_rns", bits=64, logn=13, batch=4, stack=[60, 61],
          predict="wrong", launches=["prep_twiddles", "merge_pass_lazy:0"], serves="prep"),
+    dict(id="rns u64 2^13 [61,60,60,60,60] fresh buffer, shape seen", entry="merge_rns", bits=64, logn=13, batch=10,
+         stack=[61, 60, 60, 60, 60], predict="shape seen",
+         launches=["prep_twiddles", "merge_pass_lazy:8", "merge_pass_lazy:8"], serves="lazy:8",
+         note="a caller that uploads its stack to a fresh buffer per call meets the in-preparation fall-back once; on rings "
+              "from 2^17 such a buffer stays unsure and casts the wide net"),
     dict(id="rns u64 2^13 [60,tiny] right (out of domain)", entry="merge_rns", bits=64, logn=13, batch=4, stack=[60, "tiny"],
          predict="right", launches=["prep_twiddles", "merge_pass_lazy:0"], serves="prep",
          note="an out-of-domain state is remembered as 'unsure', never as a family: small rings keep the in-preparation "

@@ -138,6 +138,14 @@ def _run_merge_rns(g, row, ordered=False):
         if predict == "right":
             for _ in range(2):
                 call(g.to_device(x), mods)
+        elif predict == "shape seen":
+            # one finished call of the same stack in ANOTHER buffer (kept alive: the row's buffer gets a new address)
+            elsewhere = mods
+            call(g.to_device(x), elsewhere)
+            mods = g.modulus_array_to_device(mods_h, bits)
+            assert mods.data_ptr() != elsewhere.data_ptr()
+        else:
+            assert predict == "unknown", predict
     d = g.to_device(x)
     with g.launch_log() as log:
         call(d, mods)
@@ -236,3 +244,39 @@ def test_dispatch_row(g, row):
     if want is not None:
         assert np.array_equal(got, want), (row["id"], "result differs from the oracle")
     assert kernels == row["launches"], (row["id"], kernels)
+
+
+def test_a_launch_log_longer_than_the_wrapper_s_buffer_comes_back_whole(g):
+    """launch_log.__exit__ hands gpuntt_test_launch_log_take a 64 KiB buffer.  A longer log used to come back cut, without
+    notice; now a take that does not fit copies nothing and KEEPS the log, and the wrapper takes it again with the length
+    it was told.  2200 tiny calls (2^12, batch 1) enqueue more than 64 KiB of names: every one comes back, in order."""
+    import torch
+    per_call = next(r for r in ROWS if r["id"] == "merge u64 2^12 pool fwd (one tile)")["launches"]
+    calls = 2200
+    assert calls * sum(len(k) + 1 for k in per_call) > (1 << 16) + 4096
+    c = MergeCase(g, 64, 12, O.X_N_plus)
+    x = c.P.splitmix(23, 0, c.n, c.q)
+    want = oracle_batch([c], x)
+    cfg = g.ntt_configuration(n_power=12, reduction_poly=O.X_N_plus)
+    d = g.to_device(x)
+    src = d.clone()
+    with g.launch_log() as log:
+        for _ in range(calls):
+            d.copy_(src)  # (torch's copy is no launch of the library)
+            g.GPU_NTT_Inplace(d, c.fwd_dev, c.prm.modulus, cfg, 1)
+    torch.cuda.synchronize()
+    assert len(log.kernels) == calls * len(per_call), (len(log.kernels), log.kernels[:4], log.kernels[-4:])
+    assert log.kernels == per_call * calls
+    assert np.array_equal(g.to_host(d), want)
+    # the C entry point itself: a buffer too small gets an empty string and the log stays; the second take empties it
+    import ctypes
+    lib = g.load_library()
+    lib.gpuntt_test_launch_log_start()
+    g.GPU_NTT_Inplace(d, c.fwd_dev, c.prm.modulus, cfg, 1)
+    small = ctypes.create_string_buffer(b"untouched?", 16)
+    need = lib.gpuntt_test_launch_log_take(small, len(small))
+    assert need == len(" ".join(per_call)) + 1 and small.value == b""
+    exact = ctypes.create_string_buffer(need)
+    assert lib.gpuntt_test_launch_log_take(exact, need) == need and exact.value.decode().split() == per_call
+    assert lib.gpuntt_test_launch_log_take(exact, need) == 1 and exact.value == b""
+    torch.cuda.synchronize()

@@ -520,14 +520,55 @@ def _timed_call(fn):
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) * 1e3
 
+
+def _logged_call(g, fn):
+    """fn() under the launch log, between two synchronisations: (kernels enqueued, host milliseconds).  The milliseconds go
+    into assertion messages for the reader; nothing asserts them (a host clock around one call on a shared machine can
+    stall on a healthy library, and cannot tell which kernels served the call)."""
+    with g.launch_log() as log:
+        ms = _timed_call(fn)
+    return log.kernels, ms
+
+
+def _row(row_id):
+    """launch list of a row of the dispatch table (tests/dispatch_rows.py)"""
+    from dispatch_rows import ROWS
+    return next(r for r in ROWS if r["id"] == row_id)["launches"]
+
+
+def _family_of(wide_net, family):
+    """the launches of a wide-net list a call predicted for ONE family keeps: the preparation kernel and that family"""
+    return [k for k in wide_net if k == "prep_twiddles" or k.endswith(":%d" % family)]
+
+
+def _needed_family(cases, inverse):
+    """lazy range the stack needs, as the preparation kernel classifies it (merge_lazy_kernels.hpp: go-flag states)"""
+    widest = max(int(c.prm.modulus.bit) for c in cases)
+    if widest >= 62:
+        return 4
+    if widest == 61:
+        return 8
+    return 31 if (not inverse and all(31 * c.q < 2**64 for c in cases)) else 0
+
+
 @pytest.mark.parametrize("logn,batch", [(17, 6), (20, 3)])
 def test_first_call_of_a_wide_stack_on_a_large_ring_is_not_the_slow_path(g, logn, batch):
     """61- / 62-bit stacks in moduli buffers the library has never seen, rings of 2^17 and 2^20: the first call (and every
-    call, when the caller uploads its stack to a fresh buffer each time) is exact and takes milliseconds, not the
-    in-preparation fall-back's tens of milliseconds per polynomial; both directions, the *_Ordered entry point too."""
+    call, when the caller uploads its stack to a fresh buffer each time) is exact and casts the WIDE NET -- every lazy family
+    and the generic kernels behind the go-flag, the preparation kernel only classifies -- not one family with the
+    in-preparation fall-back's tens of milliseconds per polynomial behind it; both directions, the *_Ordered entry point
+    too.  By decision a hinted buffer stays on the wide net here (a wrong hint has no cheap fall-back on a large ring):
+    large rings pay it once per buffer, and a third call on the same buffer enqueues the one family the stack needs."""
     import torch
     poly = O.X_N_plus
+    wide_fwd = _row("rns u64 2^17 [60,61] unknown (wide net)")
+    wide_inv = [k for k in wide_fwd if not k.endswith(":31")]  # the inverse twin has no 31 q family
+    assert _family_of(wide_fwd, 8) == _row("rns u64 2^17 [60,61] right")
+    keep = []  # every moduli buffer of the test stays alive: a later one must not get the address (= the slot) of an earlier one
     for widths in ([60, 61, 60], [62, 60], [60, 60]):
+        # "never seen" is a statement about ADDRESSES: a buffer that a test before this one freed may have left its slot
+        # behind, and a buffer allocated at its address would be a known stack
+        g.set_option("reset_predictions", "1")
         mc = len(widths)
         cases, d_fwd, d_inv = rns_stack(g, 64, logn, widths, poly)
         n = 1 << logn
@@ -536,63 +577,152 @@ def test_first_call_of_a_wide_stack_on_a_large_ring_is_not_the_slow_path(g, logn
         ninv = g.to_device(np.array([c.prm.n_inv for c in cases], dtype=np.uint64))
         cfg = g.ntt_rns_configuration(n_power=logn, reduction_poly=poly)
         icfg = g.ntt_rns_configuration(n_power=logn, ntt_type=g.INVERSE, reduction_poly=poly, mod_inverse=ninv)
-        worst, keep = 0.0, []
         for rep in range(3):  # a FRESH moduli buffer per call: the pointer-keyed prediction never settles
             mods = g.modulus_array_to_device([c.prm.modulus for c in cases], 64)
             d = g.to_device(x)
-            worst = max(worst, _timed_call(lambda: g.GPU_NTT_Inplace(d, d_fwd, mods, cfg, batch, mc)))
+            kernels, ms = _logged_call(g, lambda: g.GPU_NTT_Inplace(d, d_fwd, mods, cfg, batch, mc))
             assert np.array_equal(g.to_host(d), want), (widths, rep, "fwd")
-            worst = max(worst, _timed_call(lambda: g.GPU_INTT_Inplace(d, d_inv, mods, icfg, batch, mc)))
+            assert kernels == wide_fwd, (widths, rep, "fwd", kernels, "%.2f ms" % ms)
+            kernels, ms = _logged_call(g, lambda: g.GPU_INTT_Inplace(d, d_inv, mods, icfg, batch, mc))
             assert np.array_equal(g.to_host(d), x), (widths, rep, "inv")
-            keep.append(mods)  # (the next buffer must not reuse this address)
-        # generic kernels on 3 polynomials of 2^20: ~2 ms; the in-preparation fall-back: > 100 ms
-        assert worst < 40.0, (widths, logn, "a first call took %.1f ms" % worst)
+            assert kernels == wide_inv, (widths, rep, "inv", kernels, "%.2f ms" % ms)
+            keep.append(mods)
+        # the same buffer again: its own word has spoken, the third call enqueues the single family the stack needs
+        for direction, fn, table, c, wide, src, res in (("fwd", g.GPU_NTT_Inplace, d_fwd, cfg, wide_fwd, x, want),
+                                                        ("inv", g.GPU_INTT_Inplace, d_inv, icfg, wide_inv, want, x)):
+            for call in (2, 3):
+                d = g.to_device(src)
+                kernels, ms = _logged_call(g, lambda: fn(d, table, mods, c, batch, mc))
+                assert np.array_equal(g.to_host(d), res), (widths, direction, "call", call)
+            assert kernels == _family_of(wide, _needed_family(cases, direction == "inv")), (widths, direction, kernels, "%.2f ms" % ms)
         # ordered entry point on a fresh buffer
         mods = g.modulus_array_to_device([c.prm.modulus for c in cases], 64)
+        keep.append(mods)
         order = torch.tensor(list(range(mc))[::-1], dtype=torch.int32, device="cuda")
         xo = np.concatenate([cases[(mc - 1 - p % mc)].P.splitmix(777 + p, 0, n, cases[(mc - 1 - p % mc)].q) for p in range(batch)])
         wo = np.concatenate([cases[(mc - 1 - p % mc)].P.merge_ntt(xo[p * n:(p + 1) * n], cases[(mc - 1 - p % mc)].oprm)
                              for p in range(batch)])
         d, o = g.to_device(xo), torch.zeros(batch * n, dtype=torch.int64, device="cuda")
-        ms = _timed_call(lambda: g.GPU_NTT_Modulus_Ordered(d, o, d_fwd, mods, cfg, batch, mc, order))
-        assert np.array_equal(g.to_host(o), wo) and ms < 40.0, (widths, "ordered", ms)
+        kernels, ms = _logged_call(g, lambda: g.GPU_NTT_Modulus_Ordered(d, o, d_fwd, mods, cfg, batch, mc, order))
+        assert np.array_equal(g.to_host(o), wo), (widths, "ordered")
+        assert kernels == wide_fwd, (widths, "ordered", kernels, "%.2f ms" % ms)
 
-def test_fresh_buffer_per_call_keeps_the_family_of_its_shape(g):
-    """Small rings keep the in-preparation fall-back for a stack the enqueued family cannot serve (milliseconds there).  A
-    caller that uploads the same 61-bit stack to a fresh buffer per call must meet it ONCE: the prediction for a buffer
-    never seen before starts from what stacks of the same shape needed last (prep.hip: g_shape_hint)."""
-    logn, batch, widths = 13, 64, [61, 60, 60, 60, 60]  # five primes: a shape no other test of this module uses
-    mc = len(widths)
-    cases, d_fwd, _ = rns_stack(g, 64, logn, widths, O.X_N_plus)
+
+@pytest.fixture(scope="module")
+def five_primes(g):
+    """2^13 x 64 under five primes -- a shape no other test of this module uses -- with a 61-bit and with a 62-bit prime
+    on top: (cases, forward tables, inverse tables, inverse configuration's n^-1, x, NTT(x)) per width, computed once"""
+    logn, batch = 13, 64
     n = 1 << logn
-    x = np.concatenate([cases[p % mc].P.splitmix(5 + p, 0, n, cases[p % mc].q) for p in range(batch)])
-    want = oracle_batch(cases, x)
+    out = {}
+    for top in (61, 62):
+        cases, d_fwd, d_inv = rns_stack(g, 64, logn, [top, 60, 60, 60, 60], O.X_N_plus)
+        x = np.concatenate([cases[p % 5].P.splitmix(5 + p, 0, n, cases[p % 5].q) for p in range(batch)])
+        x.setflags(write=False)
+        want = oracle_batch(cases, x)
+        want.setflags(write=False)
+        ninv = g.to_device(np.array([c.prm.n_inv for c in cases], dtype=np.uint64))
+        out[top] = (cases, d_fwd, d_inv, ninv, x, want)
+    return out
+
+
+def test_fresh_buffer_per_call_keeps_the_family_of_its_shape(g, five_primes):
+    """Small rings keep the in-preparation fall-back for a stack the enqueued family cannot serve.  A caller that uploads
+    the same 61-bit stack to a fresh buffer per call must meet it ONCE: a slot created for a buffer never seen before
+    starts from what finished calls of the same shape needed in OTHER buffers (csrc/rns_predict.hpp: the shape hint).
+    Asserted through the launch log: call 1 enqueues the default 16 q family, which cannot serve the stack (the
+    preparation kernel does, the result is exact); calls 2 .. 6 enqueue exactly the 8 q family's list -- so neither the
+    fall-back nor a wide net served them.  A hint must not hide a wider stack: a 62-bit stack in the next fresh buffer
+    gets the 8 q list, an exact result, and the 4 q list from then on.  Steady-state calls allocate nothing: the
+    library's own hipMalloc / hipHostMalloc / hipFree count (gpuntt_test_alloc_count) does not move after call 1.  Both
+    directions."""
+    for inverse in (False, True):
+        _fresh_buffer_per_call(g, five_primes, inverse)
+
+
+def _fresh_buffer_per_call(g, five_primes, inverse):
+    import torch
+    logn, batch, mc = 13, 64, 5
+    first = _row("rns u64 2^13 [60,60] right inv" if inverse else "rns u64 2^13 [60,60] unknown")
+    on_8q, on_4q = _row("rns u64 2^13 [60,61] right"), _row("rns u64 2^13 [62,60] right")
+    assert first == ["prep_twiddles", "merge_pass_lazy:0"]
+    assert on_8q == ["prep_twiddles", "merge_pass_lazy:8", "merge_pass_lazy:8"]
     cfg = g.ntt_rns_configuration(n_power=logn, reduction_poly=O.X_N_plus)
-    times, keep = [], []
-    for rep in range(6):
+    keep, times, allocs = [], [], []
+
+    def call(top):
+        cases, d_fwd, d_inv, ninv, x, want = five_primes[top]
         mods = g.modulus_array_to_device([c.prm.modulus for c in cases], 64)
-        keep.append(mods)
+        keep.append(mods)  # (the next buffer must not reuse this address)
+        src, res = (want, x) if inverse else (x, want)
+        d = g.to_device(src)
+        if inverse:
+            icfg = g.ntt_rns_configuration(n_power=logn, ntt_type=g.INVERSE, reduction_poly=O.X_N_plus, mod_inverse=ninv)
+            kernels, ms = _logged_call(g, lambda: g.GPU_INTT_Inplace(d, d_inv, mods, icfg, batch, mc))
+        else:
+            kernels, ms = _logged_call(g, lambda: g.GPU_NTT_Inplace(d, d_fwd, mods, cfg, batch, mc))
+        # (_logged_call synchronises: the call's state has reached the host-mapped word before the next prediction)
+        times.append(round(ms, 3))
+        allocs.append(g.alloc_count())
+        assert np.array_equal(g.to_host(d), res), (inverse, len(times), top, "result differs from the oracle")
+        return kernels
+
+    g.set_option("reset_predictions", "1")
+    kernels = call(61)
+    assert kernels == first, (inverse, 1, kernels, times)
+    for rep in range(2, 7):
+        kernels = call(61)
+        assert kernels == on_8q, (inverse, rep, kernels, times)
+    assert allocs[1:] == [allocs[0]] * 5, (inverse, "the library allocated or freed during calls 2 .. 6", allocs, times)
+    kernels = call(62)  # predicted from the hint: the 8 q family cannot serve it, the preparation kernel does
+    assert kernels == on_8q, (inverse, "62-bit stack after the 61-bit one", kernels, times)
+    for rep in range(2):
+        kernels = call(62)
+        assert kernels == on_4q, (inverse, "62-bit stack, next fresh buffer", rep, kernels, times)
+    kernels = call(61)  # the 4 q family serves the narrower stack: no narrowing after one call
+    assert kernels == on_4q, (inverse, "61-bit stack after the 62-bit one", kernels, times)
+    assert allocs[1:] == [allocs[0]] * (len(allocs) - 1), (inverse, allocs, times)
+    torch.cuda.synchronize()
+
+
+def test_burst_of_fresh_buffer_calls_without_a_synchronise(g, five_primes):
+    """eight calls, each with its stack in a fresh buffer, enqueued back to back: no call may wait for another's state
+    and the prediction may lag behind (whatever family each call enqueued, the preparation kernel serves what it cannot)
+    -- every result is exact."""
+    import torch
+    logn, batch, mc = 13, 64, 5
+    cfg = g.ntt_rns_configuration(n_power=logn, reduction_poly=O.X_N_plus)
+    g.set_option("reset_predictions", "1")
+    torch.cuda.synchronize()
+    keep, outs = [], []
+    for i in range(8):
+        top = (61, 61, 62, 61, 62, 62, 61, 61)[i]
+        cases, d_fwd, _, _, x, want = five_primes[top]
+        mods = g.modulus_array_to_device([c.prm.modulus for c in cases], 64)
         d = g.to_device(x)
-        if rep == 1:  # the first call's state must have reached the host-mapped word before the second prediction
-            import torch
-            torch.cuda.synchronize()
-        times.append(_timed_call(lambda: g.GPU_NTT_Inplace(d, d_fwd, mods, cfg, batch, mc)))
-        assert np.array_equal(g.to_host(d), want), rep
-    # calls 3 .. 6 run on the predicted 8 q family: as fast as each other and several times faster than a fall-back call
-    assert max(times[2:]) < 2.0, times
+        keep.append(mods)
+        g.GPU_NTT_Inplace(d, d_fwd, mods, cfg, batch, mc)
+        outs.append((d, want))
+    torch.cuda.synchronize()
+    for i, (d, want) in enumerate(outs):
+        assert np.array_equal(g.to_host(d), want), i
+
 
 def test_out_of_domain_stack_on_a_large_ring(g):
     """A stack with a modulus the lazy families cannot take (here: 2, below the domain's minimum of 3 -- the classification
-    is what matters, not the arithmetic) on a ring of 2^17: the generic kernels behind the call serve it, call after call,
-    in milliseconds; their result is whatever the public Barrett operators give, identical to path = generic."""
+    is what matters, not the arithmetic) on a ring of 2^17: call after call casts the wide net (an out-of-domain state is
+    remembered as unsure, never as a family) and the generic kernels behind the go-flag serve it; their result is whatever
+    the public Barrett operators give, identical to path = generic."""
     import torch
     logn, batch = 17, 4
+    wide = _row("rns u64 2^17 [60,tiny] right (out of domain, large ring)")
     cases, d_fwd, _ = rns_stack(g, 64, logn, [60, 60], O.X_N_plus)
     n = 1 << logn
     mods_h = [cases[0].prm.modulus, g.Modulus(value=2, bit=2, mu=16, bits=64)]  # (bit and mu given: no validation)
     x = np.concatenate([cases[0].P.splitmix(31 + p, 0, n, 2) for p in range(batch)])  # residues below every modulus
     cfg = g.ntt_rns_configuration(n_power=logn, reduction_poly=O.X_N_plus)
     mods = g.modulus_array_to_device(mods_h, 64)
+    g.set_option("reset_predictions", "1")  # (whatever stack lived at this address before is forgotten)
     g.set_option("path", "generic")
     try:
         d = g.to_device(x)
@@ -603,8 +733,8 @@ def test_out_of_domain_stack_on_a_large_ring(g):
         g.set_option("path", "default")
     for rep in range(4):
         d = g.to_device(x)
-        ms = _timed_call(lambda: g.GPU_NTT_Inplace(d, d_fwd, mods, cfg, batch, 2))
+        kernels, ms = _logged_call(g, lambda: g.GPU_NTT_Inplace(d, d_fwd, mods, cfg, batch, 2))
         assert np.array_equal(g.to_host(d), ref), rep
-        assert ms < 40.0, (rep, ms)
+        assert kernels == wide, (rep, kernels, "%.2f ms" % ms)
     # polynomial 0 uses the 60-bit prime: the oracle's result
     assert np.array_equal(ref[:n], cases[0].P.merge_ntt(x[:n], cases[0].oprm))
