@@ -117,7 +117,13 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "keyswitch_plan_rotate_hoisted_sum", "keyswitch_plan_multiply_relinearize",
               "keyswitch_plan_multiply_relinearize_sum", "keyswitch_plan_owns_workspace",
               "keyswitch_plan_destroy", "keyswitch_constants", "keyswitch_reference_mod_up",
-              "keyswitch_reference_mod_down")
+              "keyswitch_reference_mod_down",
+              "keyswitch_plan_workspace_bytes_rescale", "keyswitch_plan_create_rescale",
+              "keyswitch_plan_rescale_limbs", "keyswitch_plan_rescale_scratch_bytes",
+              "keyswitch_plan_mod_down_rescale", "keyswitch_plan_rescale",
+              "keyswitch_plan_multiply_relinearize_rescale", "keyswitch_plan_multiply_relinearize_sum_rescale",
+              "keyswitch_plan_rotate_hoisted_sum_rescale", "keyswitch_reference_mod_down_rescale",
+              "keyswitch_reference_rescale")
     for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option", "gpuntt_galois_element_u32",
                                 "gpuntt_automorphism_index_map"]
 
@@ -998,6 +1004,35 @@ def keyswitch_reference_mod_down(q_moduli, p_moduli, x, out, n_power, stacks, bi
     return out
 
 
+def keyswitch_reference_mod_down_rescale(q_moduli, p_moduli, rescale_limbs, x, out, n_power, stacks, bits=64):
+    """Host (no GPU): KeySwitchPlan<T>::reference_mod_down_rescale -- x holds stacks x M x N words, out stacks x (L - R)
+    x N (written and returned), R = rescale_limbs in [1, L - 1] (ValueError otherwise)."""
+    qs, qarr = _keyswitch_moduli(q_moduli, bits)
+    ps, parr = _keyswitch_moduli(p_moduli, bits)
+    L, M, R = len(qs), len(qs) + len(ps), int(rescale_limbs)
+    ok = 1 <= int(n_power) <= 28 and int(stacks) >= 0 and 1 <= R <= L - 1
+    cols = (int(stacks) << int(n_power)) if ok else None
+    px = _keyswitch_host_array(x, bits, cols * M if ok else None, "x (stacks x M x N)")
+    po = _keyswitch_host_array(out, bits, cols * (L - R) if ok else None, "out (stacks x (L - R) x N)")
+    fn = getattr(load_library(), "gpuntt_keyswitch_reference_mod_down_rescale_u%d" % bits)
+    _check(fn(qarr, len(qs), parr, len(ps), R, px, po, int(n_power), int(stacks)))
+    return out
+
+
+def keyswitch_reference_rescale(q_moduli, rescale_limbs, x, out, n_power, stacks, bits=64):
+    """Host (no GPU): KeySwitchPlan<T>::reference_rescale, coefficient form -- x holds stacks x L x N words over the
+    q-base, out stacks x (L - R) x N (written and returned), R = rescale_limbs in [1, L - 1] (ValueError otherwise)."""
+    qs, qarr = _keyswitch_moduli(q_moduli, bits)
+    L, R = len(qs), int(rescale_limbs)
+    ok = 1 <= int(n_power) <= 28 and int(stacks) >= 0 and 1 <= R <= L - 1
+    cols = (int(stacks) << int(n_power)) if ok else None
+    px = _keyswitch_host_array(x, bits, cols * L if ok else None, "x (stacks x L x N)")
+    po = _keyswitch_host_array(out, bits, cols * (L - R) if ok else None, "out (stacks x (L - R) x N)")
+    fn = getattr(load_library(), "gpuntt_keyswitch_reference_rescale_u%d" % bits)
+    _check(fn(qarr, len(qs), R, px, po, int(n_power), int(stacks)))
+    return out
+
+
 class KeySwitchPlan:
     """Extension KeySwitchPlan<T> (include/gpuntt/rns/key_switch.cuh): hybrid key switching for the q-base `q_moduli`
     (L), the special primes `p_moduli` (K) and the digit size `alpha` on a ring of 2^n_power, M = L + K <= 64.
@@ -1007,17 +1042,23 @@ class KeySwitchPlan:
     tensor of workspace_bytes() bytes owned by the caller.  `scratch` of the pipeline calls: a device tensor of at least
     plan.scratch_bytes(count, components) bytes -- the header's static scratch_bytes(L, K, alpha, n_power, count,
     components) with this plan's shape filled in; keyswitch_scratch_bytes() is that static -- 256-byte aligned, owned by
-    the caller; nothing is allocated by any call."""
+    the caller; nothing is allocated by any call.  `rescale_limbs` = R in [0, L - 1]: with R > 0 the plan also holds what
+    mod_down_rescale, rescale and the three *_rescale pipeline calls need (workspace_bytes(..., rescale_limbs=R) bytes);
+    with R = 0 it is the plan without the argument and those calls raise ValueError."""
 
     def __init__(self, q_moduli, p_moduli, alpha, n_power, forward_table=None, inverse_table=None, mod_inverse=None,
                  reduction_poly=X_N_plus, batch_hint=1024, key_mod_count=None, key_limbs=None, bits=64, stream=None,
-                 workspace=None):
+                 workspace=None, rescale_limbs=0, via_rescale_abi=None):
         lib = load_library()
         qs, qarr = _keyswitch_moduli(q_moduli, bits)
         ps, parr = _keyswitch_moduli(p_moduli, bits)
         _require_gpu(workspace, forward_table, inverse_table)
         self.bits, self.q_count, self.p_count, self.mod_count = bits, len(qs), len(ps), len(qs) + len(ps)
         self.alpha, self.n_power = int(alpha), int(n_power)
+        self._rescale_limbs = int(rescale_limbs)
+        self.kept_count = self.q_count - self._rescale_limbs  # L' = L - R
+        # R = 0 goes through gpuntt_keyswitch_plan_create_* unless via_rescale_abi asks for the _rescale_ function
+        rescale_abi = self._rescale_limbs != 0 if via_rescale_abi is None else bool(via_rescale_abi)
         self.digits = keyswitch_digits(len(qs), alpha)
         for t in (forward_table, inverse_table):
             if t is not None and (t.element_size() * 8 != bits or t.numel() < self.mod_count << self.n_power):
@@ -1031,23 +1072,37 @@ class KeySwitchPlan:
         km = self.mod_count if key_mod_count is None else int(key_mod_count)
         limbs = _innerprod_limbs(key_limbs, self.mod_count)
         if workspace is not None:
-            need = self.workspace_bytes(len(qs), len(ps), alpha, n_power, bits)  # raises for counts out of range
+            # raises for counts out of range
+            need = self.workspace_bytes(len(qs), len(ps), alpha, n_power, bits, self._rescale_limbs)
             if workspace.numel() * workspace.element_size() < need:
                 raise ValueError("workspace holds fewer than workspace_bytes() bytes")
         self.key_mod_count = km
         self._keep = (workspace, forward_table, inverse_table)
         self._h = ctypes.c_void_p()
-        fn = getattr(lib, "gpuntt_keyswitch_plan_create_u%d" % bits)
-        _check(fn(ctypes.byref(self._h), qarr, len(qs), parr, len(ps), int(alpha), int(n_power), _ptr(forward_table),
-                  _ptr(inverse_table), ninv, int(reduction_poly), int(batch_hint), km, limbs, _ptr(workspace),
-                  _stream(stream)))
+        head = (ctypes.byref(self._h), qarr, len(qs), parr, len(ps), int(alpha), int(n_power), _ptr(forward_table),
+                _ptr(inverse_table), ninv, int(reduction_poly), int(batch_hint), km, limbs)
+        if rescale_abi:
+            fn = getattr(lib, "gpuntt_keyswitch_plan_create_rescale_u%d" % bits)
+            _check(fn(*head, self._rescale_limbs, _ptr(workspace), _stream(stream)))
+        else:
+            fn = getattr(lib, "gpuntt_keyswitch_plan_create_u%d" % bits)
+            _check(fn(*head, _ptr(workspace), _stream(stream)))
 
     @staticmethod
-    def workspace_bytes(q_count, p_count, alpha, n_power, bits=64):
+    def workspace_bytes(q_count, p_count, alpha, n_power, bits=64, rescale_limbs=0):
         out = ctypes.c_uint64()
-        _check(getattr(load_library(), "gpuntt_keyswitch_plan_workspace_bytes_u%d" % bits)(
-            int(q_count), int(p_count), int(alpha), int(n_power), ctypes.byref(out)))
+        if int(rescale_limbs) != 0:
+            _check(getattr(load_library(), "gpuntt_keyswitch_plan_workspace_bytes_rescale_u%d" % bits)(
+                int(q_count), int(p_count), int(alpha), int(n_power), int(rescale_limbs), ctypes.byref(out)))
+        else:
+            _check(getattr(load_library(), "gpuntt_keyswitch_plan_workspace_bytes_u%d" % bits)(
+                int(q_count), int(p_count), int(alpha), int(n_power), ctypes.byref(out)))
         return int(out.value)
+
+    @property
+    def rescale_limbs(self):
+        """R: the q-limbs the *_rescale calls drop (0: the plan has none of them)"""
+        return int(getattr(load_library(), "gpuntt_keyswitch_plan_rescale_limbs_u%d" % self.bits)(self._h))
 
     def scratch_bytes(self, count, components=1):
         return keyswitch_scratch_bytes(self.q_count, self.p_count, self.alpha, self.n_power, count, components,
@@ -1175,7 +1230,7 @@ class KeySwitchPlan:
                                                    self.bits)
 
     def rotate_hoisted_sum(self, a, c0, keys, elements, weights, out, count, output_ntt=False, scratch=None,
-                           stream=None):
+                           stream=None, _rescale=False):
         """The weighted sum of G = len(elements) Galois automorphisms of one decomposition, taken before the ModDown:
         a, c0, keys and elements as for rotate_hoisted; weights None (all 1) or a list of G entries, each None (1) or a
         device tensor of at least M x N words -- the plaintext diagonal in NTT form over the plan's full base; out
@@ -1193,7 +1248,7 @@ class KeySwitchPlan:
         if a is None or out is None or scratch is None or any(k is None for k in keys):
             raise ValueError("null pointer argument")
         sized = [(a, cols * self.mod_count * self.digits, "a (D x count x M x N)"),
-                 (out, cols * self.q_count * 2, "out (2 x count x L x N)")]
+                 (out, cols * self._out_limbs(_rescale) * 2, "out (2 x count x L x N)")]
         if c0 is not None:
             sized.append((c0, cols * self.q_count, "c0 (count x L x N)"))
         sized += [(k, self._key_words(2) if cols else 0, "key (D x 2 x key_mod_count x N)") for k in keys]
@@ -1207,11 +1262,11 @@ class KeySwitchPlan:
         weight_ptrs = None if weights is None else \
             (ctypes.c_void_p * G)(*[None if w is None else w.data_ptr() for w in weights])
         elts = (ctypes.c_uint32 * G)(*[k & 0xFFFFFFFF for k in elements])
-        fn = getattr(load_library(), "gpuntt_keyswitch_plan_rotate_hoisted_sum_u%d" % self.bits)
+        fn = self._pipeline_fn("rotate_hoisted_sum", _rescale)
         _check(fn(self._h, _ptr(a), _ptr(c0), key_ptrs, elts, weight_ptrs, G, _ptr(out), int(count),
                   int(bool(output_ntt)), _ptr(scratch), _stream(stream)))
 
-    def multiply_relinearize(self, x, y, key, out, count, output_ntt, scratch, stream=None):
+    def multiply_relinearize(self, x, y, key, out, count, output_ntt, scratch, stream=None, _rescale=False):
         """The product of `count` pairs of two-component ciphertexts, relinearized in ONE key switch: x, y
         T[2][count][L][N] in NTT form (any words; y may be x), key the relinearization key, at least
         D x 2 x key_mod_count x N words, out T[2][count][L][N] (may be exactly x or exactly y); scratch: a device tensor
@@ -1223,15 +1278,15 @@ class KeySwitchPlan:
         self._check_buffers(((x, cols * self.q_count * 2, "x (2 x count x L x N)"),
                              (y, cols * self.q_count * 2, "y (2 x count x L x N)"),
                              (key, self._key_words(2) if cols else 0, "key (D x 2 x key_mod_count x N)"),
-                             (out, cols * self.q_count * 2, "out (2 x count x L x N)")))
+                             (out, cols * self._out_limbs(_rescale) * 2, "out (2 x count x L x N)")))
         _require_gpu(scratch)
         if int(count) >= 0 and scratch.numel() * scratch.element_size() < self.scratch_bytes(count, 2):
             raise ValueError("scratch holds fewer than scratch_bytes(count, 2) bytes")
-        fn = getattr(load_library(), "gpuntt_keyswitch_plan_multiply_relinearize_u%d" % self.bits)
+        fn = self._pipeline_fn("multiply_relinearize", _rescale)
         _check(fn(self._h, _ptr(x), _ptr(y), _ptr(key), _ptr(out), int(count), int(bool(output_ntt)), _ptr(scratch),
                   _stream(stream)))
 
-    def multiply_relinearize_sum(self, xs, ys, key, out, count, output_ntt, scratch, stream=None):
+    def multiply_relinearize_sum(self, xs, ys, key, out, count, output_ntt, scratch, stream=None, _rescale=False):
         """sum_t xs[t] * ys[t] over T = len(xs) pairs of two-component ciphertexts with ONE key switch and ONE ModDown
         (lazy relinearization): xs, ys two lists of T device tensors, 1 <= T <= 32, each T[2][count][L][N] in NTT form
         (any words; ys[t] may be xs[t], a tensor may appear in several terms); key, out, count, output_ntt and scratch as
@@ -1253,15 +1308,78 @@ class KeySwitchPlan:
         self._check_buffers([(t, ct, "x[%d] (2 x count x L x N)" % i) for i, t in enumerate(xs)] +
                             [(t, ct, "y[%d] (2 x count x L x N)" % i) for i, t in enumerate(ys)] +
                             [(key, self._key_words(2) if cols else 0, "key (D x 2 x key_mod_count x N)"),
-                             (out, ct, "out (2 x count x L x N)")])
+                             (out, cols * self._out_limbs(_rescale) * 2, "out (2 x count x L x N)")])
         _require_gpu(scratch)
         if int(count) >= 0 and scratch.numel() * scratch.element_size() < self.scratch_bytes(count, 2):
             raise ValueError("scratch holds fewer than scratch_bytes(count, 2) bytes")
         x_ptrs = (ctypes.c_void_p * terms)(*[t.data_ptr() for t in xs])
         y_ptrs = (ctypes.c_void_p * terms)(*[t.data_ptr() for t in ys])
-        fn = getattr(load_library(), "gpuntt_keyswitch_plan_multiply_relinearize_sum_u%d" % self.bits)
+        fn = self._pipeline_fn("multiply_relinearize_sum", _rescale)
         _check(fn(self._h, x_ptrs, y_ptrs, terms, _ptr(key), _ptr(out), int(count), int(bool(output_ntt)),
                   _ptr(scratch), _stream(stream)))
+
+    # ---- rescaling: a plan built with rescale_limbs = R > 0 (key_switch.cuh, "Rescaling"); L' = L - R = kept_count ----
+    def _out_limbs(self, rescale):
+        """limbs per stack of a pipeline call's out; a *_rescale call on a plan with R = 0 is refused here as the library
+        refuses it"""
+        if rescale and self._rescale_limbs == 0:
+            raise ValueError("The plan was built without rescale_limbs!")
+        return self.kept_count if rescale else self.q_count
+
+    def _pipeline_fn(self, name, rescale):
+        return getattr(load_library(), "gpuntt_keyswitch_plan_%s%s_u%d" % (name, "_rescale" if rescale else "", self.bits))
+
+    def mod_down_rescale(self, device_x, device_out, stacks, stream=None):
+        """device_x T[stacks][M][N] -> device_out T[stacks][L'][N]: divided by P and the R dropped primes with ONE
+        rounding; one kernel launch"""
+        if device_x is None or device_out is None:
+            raise ValueError("null pointer argument")
+        cols = self._cols(stacks)
+        self._check_buffers(((device_x, cols * self.mod_count, "x (stacks x M x N)"),
+                             (device_out, cols * self._out_limbs(True), "out (stacks x L' x N)")))
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_mod_down_rescale_u%d" % self.bits)
+        _check(fn(self._h, _ptr(device_x), _ptr(device_out), int(stacks), _stream(stream)))
+
+    def rescale_scratch_bytes(self, stacks):
+        """the scratch of rescale(ntt_form=True): T[stacks][R][N], rounded up to 256"""
+        out = ctypes.c_uint64()
+        _check(getattr(load_library(), "gpuntt_keyswitch_plan_rescale_scratch_bytes_u%d" % self.bits)(
+            self._h, int(stacks), ctypes.byref(out)))
+        return int(out.value)
+
+    def rescale(self, device_x, device_out, stacks, ntt_form=False, scratch=None, stream=None):
+        """device_x T[stacks][L][N] over the q-base (any words) -> device_out T[stacks][L'][N], divided by the R dropped
+        primes.  ntt_form False: coefficient form, one kernel launch, no scratch.  ntt_form True: both in NTT form; scratch
+        a device tensor of at least rescale_scratch_bytes(stacks) bytes, 256-byte aligned; only the dropped limbs are
+        inverse-transformed."""
+        if device_x is None or device_out is None:
+            raise ValueError("null pointer argument")
+        cols = self._cols(stacks)
+        self._check_buffers(((device_x, cols * self.q_count, "x (stacks x L x N)"),
+                             (device_out, cols * self._out_limbs(True), "out (stacks x L' x N)")))
+        if ntt_form:
+            _require_gpu(scratch)
+            if scratch is None:
+                raise ValueError("null pointer argument")
+            if int(stacks) >= 0 and scratch.numel() * scratch.element_size() < self.rescale_scratch_bytes(stacks):
+                raise ValueError("scratch holds fewer than rescale_scratch_bytes(stacks) bytes")
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_rescale_u%d" % self.bits)
+        _check(fn(self._h, _ptr(device_x), _ptr(device_out), int(stacks), int(bool(ntt_form)), _ptr(scratch),
+                  _stream(stream)))
+
+    def multiply_relinearize_rescale(self, x, y, key, out, count, output_ntt, scratch, stream=None):
+        """multiply_relinearize with the rescale in its ModDown: out T[2][count][L'][N], rounded once (within 1 per
+        coefficient of multiply_relinearize followed by rescale, not word for word equal to it)"""
+        self.multiply_relinearize(x, y, key, out, count, output_ntt, scratch, stream, _rescale=True)
+
+    def multiply_relinearize_sum_rescale(self, xs, ys, key, out, count, output_ntt, scratch, stream=None):
+        """multiply_relinearize_sum with the rescale in its ModDown: out T[2][count][L'][N]"""
+        self.multiply_relinearize_sum(xs, ys, key, out, count, output_ntt, scratch, stream, _rescale=True)
+
+    def rotate_hoisted_sum_rescale(self, a, c0, keys, elements, weights, out, count, output_ntt=False, scratch=None,
+                                   stream=None):
+        """rotate_hoisted_sum with the rescale in its ModDown: out T[2][count][L'][N]"""
+        self.rotate_hoisted_sum(a, c0, keys, elements, weights, out, count, output_ntt, scratch, stream, _rescale=True)
 
     def close(self):
         if self._h:

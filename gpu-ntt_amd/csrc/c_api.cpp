@@ -1066,6 +1066,116 @@ extern "C"
                                                  n_power, stacks);                                \
         });                                                                                       \
     }                                                                                             \
+    int gpuntt_keyswitch_plan_workspace_bytes_rescale_##S(int q_count, int p_count, int alpha, int n_power,       \
+                                                          int rescale_limbs, uint64_t* bytes_host) \
+    {                                                                                             \
+        GPUNTT_NEED(bytes_host)                                                                   \
+        return guarded([&] {                                                                      \
+            *bytes_host = KeySwitchPlan<T>::workspace_bytes(q_count, p_count, alpha, n_power, rescale_limbs);     \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_create_rescale_##S(                                                 \
+        gpuntt_keyswitch_plan** plan_host, const CM* q_moduli_host, int q_count, const CM* p_moduli_host,         \
+        int p_count, int alpha, int n_power, const T* forward_table, const T* inverse_table,      \
+        const T* mod_inverse_host, int reduction_poly, int batch_hint, int key_mod_count,         \
+        const int* key_limbs_host, int rescale_limbs, void* workspace_device, void* stream)       \
+    {                                                                                             \
+        GPUNTT_NEED(plan_host)                                                                    \
+        return guarded([&] {                                                                      \
+            const auto qs = to_mods<T>(q_moduli_host, q_count, "Invalid q_count!");                \
+            const auto ps = to_mods<T>(p_moduli_host, p_count, "Invalid p_count!");                \
+            if (reduction_poly != GPUNTT_X_N_PLUS && reduction_poly != GPUNTT_X_N_MINUS)          \
+                throw std::invalid_argument("Invalid reduction_poly!");                           \
+            *plan_host = reinterpret_cast<gpuntt_keyswitch_plan*>(new KeySwitchPlan<T>(           \
+                qs.data(), q_count, ps.data(), p_count, alpha, n_power, forward_table, inverse_table,             \
+                mod_inverse_host, static_cast<ReductionPolynomial>(reduction_poly), batch_hint, key_mod_count,    \
+                key_limbs_host, static_cast<hipStream_t>(stream), workspace_device, rescale_limbs));              \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_rescale_limbs_##S(const gpuntt_keyswitch_plan* plan)                \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return reinterpret_cast<const KeySwitchPlan<T>*>(plan)->rescale_limbs();                  \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_rescale_scratch_bytes_##S(const gpuntt_keyswitch_plan* plan, int stacks,            \
+                                                        uint64_t* bytes_host)                     \
+    {                                                                                             \
+        GPUNTT_NEED(plan, bytes_host)                                                             \
+        return guarded([&] {                                                                      \
+            *bytes_host = reinterpret_cast<const KeySwitchPlan<T>*>(plan)->rescale_scratch_bytes(stacks);         \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_mod_down_rescale_##S(const gpuntt_keyswitch_plan* plan, const T* x, T* out,          \
+                                                   int stacks, void* stream)                      \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->mod_down_rescale(x, out, stacks,      \
+                                                                              static_cast<hipStream_t>(stream));  \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_rescale_##S(const gpuntt_keyswitch_plan* plan, const T* x, T* out, int stacks,       \
+                                          int ntt_form, void* scratch, void* stream)              \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->rescale(x, out, stacks, ntt_form != 0, scratch,      \
+                                                                     static_cast<hipStream_t>(stream));           \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_multiply_relinearize_rescale_##S(const gpuntt_keyswitch_plan* plan, const T* x,      \
+                                                               const T* y, const T* key, T* out, int count,       \
+                                                               int output_ntt, void* scratch, void* stream)       \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->multiply_relinearize_rescale(        \
+                x, y, key, out, count, output_ntt != 0, scratch, static_cast<hipStream_t>(stream));               \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_multiply_relinearize_sum_rescale_##S(                               \
+        const gpuntt_keyswitch_plan* plan, const T* const* x_host, const T* const* y_host, int terms,             \
+        const T* key, T* out, int count, int output_ntt, void* scratch, void* stream)             \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->multiply_relinearize_sum_rescale(    \
+                x_host, y_host, terms, key, out, count, output_ntt != 0, scratch,                 \
+                static_cast<hipStream_t>(stream));                                                \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_rotate_hoisted_sum_rescale_##S(                                     \
+        const gpuntt_keyswitch_plan* plan, const T* a, const T* c0, const T* const* keys_host,    \
+        const uint32_t* galois_elements_host, const T* const* weights_host, int elements, T* out, int count,      \
+        int output_ntt, void* scratch, void* stream)                                              \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->rotate_hoisted_sum_rescale(          \
+                a, c0, keys_host, galois_elements_host, weights_host, elements, out, count, output_ntt != 0,      \
+                scratch, static_cast<hipStream_t>(stream));                                       \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_reference_mod_down_rescale_##S(const CM* q_moduli_host, int q_count,     \
+                                                        const CM* p_moduli_host, int p_count, int rescale_limbs,  \
+                                                        const T* x_host, T* out_host, int n_power, int stacks)    \
+    {                                                                                             \
+        return guarded([&] {                                                                      \
+            const auto qs = to_mods<T>(q_moduli_host, q_count, "Invalid q_count!");                \
+            const auto ps = to_mods<T>(p_moduli_host, p_count, "Invalid p_count!");                \
+            KeySwitchPlan<T>::reference_mod_down_rescale(qs.data(), q_count, ps.data(), p_count, rescale_limbs,   \
+                                                         x_host, out_host, n_power, stacks);      \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_reference_rescale_##S(const CM* q_moduli_host, int q_count, int rescale_limbs,           \
+                                               const T* x_host, T* out_host, int n_power, int stacks)             \
+    {                                                                                             \
+        return guarded([&] {                                                                      \
+            const auto qs = to_mods<T>(q_moduli_host, q_count, "Invalid q_count!");                \
+            KeySwitchPlan<T>::reference_rescale(qs.data(), q_count, rescale_limbs, x_host, out_host, n_power,     \
+                                                stacks);                                          \
+        });                                                                                       \
+    }                                                                                             \
     int gpuntt_4step_plan_workspace_bytes_##S(int n_power, uint64_t* bytes_host)                  \
     {                                                                                             \
         GPUNTT_NEED(bytes_host)                                                                   \

@@ -36,6 +36,14 @@
 //
 // multiply_relinearize_sum: the same sequence with tensor_top_sum and inner_product_tensor_sum of relinearize_sum.hip,
 // which loop over the terms: one key switch and one ModDown for sum_t x_t y_t.
+//
+// Rescaling (a plan built with rescale_limbs = R > 0).  mod_down_rescale is mod_down's launch with a second
+// constants image, {q_{L-R} .. q_{L-1}, p_0 .. p_{K-1}} -> {q_0 .. q_{L-R-1}}: the R dropped q-limbs and the K special
+// limbs are one contiguous run of the full-base stack, (L - R) N words behind its start, so the strided kernel reads them
+// in place and divides by P q_{L-R} ... q_{L-1} with ONE rounding.  Impl::finish takes a flag and ends the three
+// *_rescale pipeline calls with it.  rescale divides a q-base stack by the dropped primes alone (a third image): in
+// coefficient form the same single launch; in NTT form rescale_gather, the inverse transform of the R dropped limbs only,
+// the dense centred conversion, the forward transform over the kept moduli and rescale_sub_scale (rescale.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -52,6 +60,7 @@
 #include "launch.hpp"
 #include "relinearize_internal.hpp"
 #include "relinearize_sum_internal.hpp"
+#include "rescale_internal.hpp"
 
 namespace gpuntt
 {
@@ -387,7 +396,7 @@ namespace gpuntt
                 throw std::invalid_argument("ModUp input and output overlap!");
         }
         template <typename T>
-        void ks_check_mod_down(int L, int M, const T* x, const T* out, int n_power, int stacks)
+        void ks_check_mod_down(int L, int M, const T* x, const T* out, int n_power, int stacks) // L out of M limbs
         {
             ks_check_n_power(n_power);
             if (stacks < 0)
@@ -401,12 +410,20 @@ namespace gpuntt
 
         struct KsLayout // the workspace, in bytes
         {
-            size_t up, down, inner, ntt_full_f, ntt_full_i, ntt_q_i, ntt_q_f, total;
+            size_t up, down, inner, ntt_full_f, ntt_full_i, ntt_q_i, ntt_q_f;
+            size_t down_rs, rs, ntt_keep_f, ntt_drop_i; // R > 0 only: they follow the rest, so R = 0 is the old layout
+            size_t total;
         };
-        template <typename T> KsLayout ks_layout(int L, int K, int alpha, int n_power)
+        void ks_check_rescale_limbs(int L, int R, int least)
+        {
+            if (R < least || R > L - 1)
+                throw std::invalid_argument("Invalid rescale_limbs!");
+        }
+        template <typename T> KsLayout ks_layout(int L, int K, int alpha, int n_power, int R)
         {
             ks_check_counts(L, K, alpha);
             ks_check_n_power(n_power);
+            ks_check_rescale_limbs(L, R, 0);
             const int M = L + K, D = ks_digits(L, alpha > L ? L : alpha);
             KsLayout w{};
             size_t at = 0;
@@ -422,6 +439,13 @@ namespace gpuntt
             w.ntt_full_i = take(NTTPlan<T>::workspace_bytes(n_power, M));
             w.ntt_q_i = take(NTTPlan<T>::workspace_bytes(n_power, L));
             w.ntt_q_f = take(NTTPlan<T>::workspace_bytes(n_power, L));
+            if (R > 0)
+            {
+                w.down_rs = take(host::bc_image_words(K + R, L - R) * sizeof(T));
+                w.rs = take(host::bc_image_words(R, L - R) * sizeof(T));
+                w.ntt_keep_f = take(NTTPlan<T>::workspace_bytes(n_power, L - R));
+                w.ntt_drop_i = take(NTTPlan<T>::workspace_bytes(n_power, R));
+            }
             w.total = at;
             return w;
         }
@@ -475,6 +499,12 @@ namespace gpuntt
         kern::BcOffsets down_off{};
         std::unique_ptr<InnerProductPlan<T>> inner;
         std::unique_ptr<NTTPlan<T>> ntt_full_f, ntt_full_i, ntt_q_i, ntt_q_f;
+        // rescaling, R > 0 only: Lk = L - R kept limbs; the images {dropped q, p} -> {kept q} and {dropped q} -> {kept q};
+        // the forward transform over the kept moduli and the inverse transform over the dropped ones
+        int R = 0, Lk = 0;
+        kern::BcOffsets down_rs_off{}, rs_off{};
+        kern::RsDropped<T> dropped_mods{}; // the dropped moduli and their companions of 1: rescale_gather reduces with them
+        std::unique_ptr<NTTPlan<T>> ntt_keep_f, ntt_drop_i;
 
         void mod_up(const T* in, T* a, int count, BaseConvMode mode, hipStream_t stream) const
         {
@@ -507,19 +537,102 @@ namespace gpuntt
             ks_check_mod_down<T>(L, M, x, out, n, stacks);
             if (stacks == 0)
                 return;
-            const unsigned long long poly = 1ull << n, full = static_cast<unsigned long long>(M) << n;
+            // the input base is {p_k} (K limbs, parked in LDS), the output base {q_j} (L limbs)
+            divide_in_stack(x, out, stacks, M, K, L, lay.down, down_off, stream);
+        }
+
+        // ONE launch of the strided base_convert (centred, divide): stacks of `limbs` limbs at x, the last `in_count` of the
+        // first out_count + in_count are the input base, read in place, the first out_count are c; out is dense,
+        // T[stacks][out_count][N].  The constants image lies `image` bytes into the workspace
+        void divide_in_stack(const T* x, T* out, int stacks, int limbs, int in_count, int out_count, size_t image,
+                             const kern::BcOffsets& off, hipStream_t stream) const
+        {
+            const unsigned long long poly = 1ull << n, full = static_cast<unsigned long long>(limbs) << n;
             const unsigned long long total = static_cast<unsigned long long>(stacks) << n;
             const unsigned long long tiles = (total + kern::BC_NT - 1) / kern::BC_NT;
             if (tiles * kern::BC_NT > 0xFFFFFFFFull) // HIP caps a launch at 2^32 - 1 work-items per dimension
                 throw std::invalid_argument("Invalid stacks!");
-            // the input base is {p_k} (K limbs, parked in LDS), the output base {q_j} (L limbs)
-            const int KP = (L + kern::BC_KB - 1) / kern::BC_KB * kern::BC_KB;
-            const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(host::bc_ksplit(tiles, L)));
-            const size_t lds = static_cast<size_t>(K) * kern::BC_NT * sizeof(T);
-            GPUNTT_LAUNCH((kern::base_convert<T, true, true, true>), grid, dim3(kern::BC_NT), lds, stream, x + L * poly, x,
-                          out, reinterpret_cast<const T*>(ws + lay.down), down_off, K, L, KP, n, total,
-                          kern::BcStrides<true>{full, full, static_cast<unsigned long long>(L) << n});
+            const int KP = (out_count + kern::BC_KB - 1) / kern::BC_KB * kern::BC_KB;
+            const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(host::bc_ksplit(tiles, out_count)));
+            const size_t lds = static_cast<size_t>(in_count) * kern::BC_NT * sizeof(T);
+            GPUNTT_LAUNCH((kern::base_convert<T, true, true, true>), grid, dim3(kern::BC_NT), lds, stream,
+                          x + out_count * poly, x, out, reinterpret_cast<const T*>(ws + image), off, in_count, out_count, KP,
+                          n, total, kern::BcStrides<true>{full, full, static_cast<unsigned long long>(out_count) << n});
             GPUNTT_HIP_CHECK(hipGetLastError());
+        }
+
+        void need_rescale() const
+        {
+            if (R == 0)
+                throw std::invalid_argument("The plan was built without rescale_limbs!");
+        }
+
+        // x: T[stacks][M][N], out: T[stacks][Lk][N]: the R dropped q-limbs and the K special limbs are the input base
+        void mod_down_rescale(const T* x, T* out, int stacks, hipStream_t stream) const
+        {
+            need_rescale();
+            ks_check_mod_down<T>(Lk, M, x, out, n, stacks);
+            if (stacks == 0)
+                return;
+            divide_in_stack(x, out, stacks, M, K + R, Lk, lay.down_rs, down_rs_off, stream);
+        }
+
+        size_t rescale_scratch(int stacks) const
+        {
+            need_rescale();
+            if (stacks < 0)
+                throw std::invalid_argument("Invalid stacks!");
+            return ks_align((static_cast<size_t>(stacks) << n) * R * sizeof(T));
+        }
+
+        // x: T[stacks][L][N], out: T[stacks][Lk][N]; the scratch (ntt_form only): T[stacks][R][N]
+        void rescale(const T* x, T* out, int stacks, bool ntt_form, void* scratch, hipStream_t stream) const
+        {
+            need_rescale();
+            if (ntt_form)
+                need_transforms();
+            ks_check_mod_down<T>(Lk, L, x, out, n, stacks);
+            if (!ntt_form)
+            {
+                if (stacks > 0)
+                    divide_in_stack(x, out, stacks, L, R, Lk, lay.rs, rs_off, stream);
+                return;
+            }
+            const size_t scratch_bytes = rescale_scratch(stacks);
+            if (scratch == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
+                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            if (stacks == 0)
+                return;
+            const std::uint64_t cols = static_cast<std::uint64_t>(stacks) << n;
+            if (ks_overlap(scratch, scratch_bytes, x, cols * L * sizeof(T)))
+                throw std::invalid_argument("The scratch overlaps an operand!");
+            if (ks_overlap(scratch, scratch_bytes, out, cols * Lk * sizeof(T)))
+                throw std::invalid_argument("The scratch overlaps out!");
+            // every limit before the first launch: the batches of the transforms are ints, the grids as their launches check
+            if (static_cast<unsigned long long>(stacks) * static_cast<unsigned>(L) > 0x7FFFFFFFull)
+                throw std::invalid_argument("Invalid stacks!");
+            const unsigned long long tiles = (cols + kern::BC_NT - 1) / kern::BC_NT;
+            if (tiles * kern::BC_NT > 0xFFFFFFFFull)
+                throw std::invalid_argument("Invalid stacks!");
+            T* dropped = static_cast<T*>(scratch);
+            const T* image = reinterpret_cast<const T*>(ws + lay.rs);
+            const kern::RsOffsets sub{rs_off.p, rs_off.onep, rs_off.qinv, rs_off.qinvp};
+            host::rescale_gather_launch<T>(x, dropped, dropped_mods, stacks, L, R, n, false, stream);
+            host::rescale_sub_scale_launch<T>(x, out, image, sub, stacks, L, Lk, n, false, stream);
+
+            host::rescale_gather_launch<T>(x, dropped, dropped_mods, stacks, L, R, n, true, stream);
+            ntt_drop_i->execute(dropped, dropped, stacks * R, stream);
+            // the dense centred conversion {dropped q} -> {kept q}, no division: conv_j in coefficient form
+            const int KP = (Lk + kern::BC_KB - 1) / kern::BC_KB * kern::BC_KB;
+            const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(host::bc_ksplit(tiles, Lk)));
+            GPUNTT_LAUNCH((kern::base_convert<T, true, false, false>), grid, dim3(kern::BC_NT),
+                          static_cast<size_t>(R) * kern::BC_NT * sizeof(T), stream, dropped, out, out, image, rs_off, R, Lk,
+                          KP, n, cols, kern::BcStrides<false>{});
+            GPUNTT_HIP_CHECK(hipGetLastError());
+            ntt_keep_f->execute(out, out, stacks * Lk, stream);
+            host::rescale_sub_scale_launch<T>(x, out, image, sub, stacks, L, Lk, n, true, stream);
         }
 
         void need_transforms() const
@@ -570,27 +683,33 @@ namespace gpuntt
             // a or key overlapping the accumulators in the scratch: refused by the inner product's own check of its
             // output against its inputs, before its launch -- the first of this call
             inner->multiply_accumulate(a, key, acc, n, D, C, count, false, KM, limbs.data(), stream);
-            finish(acc, out, C * count, output_ntt, stream);
+            finish(acc, out, C * count, output_ntt, false, stream);
         }
 
         // the tail of every switch: acc T[stacks][M][N] in the NTT domain -> out T[stacks][L][N]
-        void finish(T* acc, T* out, int stacks, bool output_ntt, hipStream_t stream) const
+        // rescale: -> out T[stacks][Lk][N], divided by P q_{L-R} ... q_{L-1} in the one ModDown
+        void finish(T* acc, T* out, int stacks, bool output_ntt, bool rescale, hipStream_t stream) const
         {
             ntt_full_i->execute(acc, acc, stacks * M, stream);
-            mod_down(acc, out, stacks, stream);
+            if (rescale)
+                mod_down_rescale(acc, out, stacks, stream);
+            else
+                mod_down(acc, out, stacks, stream);
             if (output_ntt)
-                ntt_q_f->execute(out, out, stacks * L, stream);
+                (rescale ? ntt_keep_f : ntt_q_f)->execute(out, out, stacks * (rescale ? Lk : L), stream);
         }
 
         // What rotate_hoisted (groups = G, no weights) and rotate_hoisted_sum (groups = 1) share up to the launch: every
         // refusal of the call, in one order, and the kernel arguments.  out: T[groups][2][count][L][N], the scratch:
         // T[groups][2][count][M][N]; weights: G device pointers (each may be null) or null.  Returns the stacks the tail
-        // runs over, 2 * groups * count; 0: count is 0 and nothing is to be launched
+        // runs over, 2 * groups * count; 0: count is 0 and nothing is to be launched.  rescale: out has Lk limbs per stack
         int hoist_prepare(const T* a, const T* c0, const T* const* keys, const std::uint32_t* elts,
                           const T* const* weights, int G, int groups, const T* out, int count, const void* scratch,
-                          kern::HoistArgs<T>& args) const
+                          kern::HoistArgs<T>& args, bool rescale = false) const
         {
             need_transforms();
+            if (rescale)
+                need_rescale();
             const size_t acc_bytes = ks_hoisted_scratch<T>(M, n, count, groups); // checks count (and G = groups)
             if (G < 1 || G > GALOIS_MAX_COUNT)
                 throw std::invalid_argument("Invalid galois_count!");
@@ -617,7 +736,7 @@ namespace gpuntt
                 return 0;
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
             const std::uint64_t a_bytes = cols * M * D * sizeof(T), c0_bytes = cols * L * sizeof(T);
-            const std::uint64_t out_bytes = cols * L * 2 * groups * sizeof(T);
+            const std::uint64_t out_bytes = cols * (rescale ? Lk : L) * 2 * groups * sizeof(T);
             const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
             const std::uint64_t weight_bytes = (static_cast<std::uint64_t>(M) << n) * sizeof(T);
             for (const auto& w : {std::pair<const void*, std::uint64_t>{out, out_bytes}, {scratch, acc_bytes}})
@@ -653,15 +772,15 @@ namespace gpuntt
             // the first launch of the call: its own grid check throws before it
             host::hoist_launch<T>(a, c0, acc, reinterpret_cast<const T*>(ws + lay.inner), args, D, count, L, M, KM, n,
                                   negacyclic, stream);
-            finish(acc, out, stacks, output_ntt, stream);
+            finish(acc, out, stacks, output_ntt, false, stream);
         }
 
         void rotate_hoisted_sum(const T* a, const T* c0, const T* const* keys, const std::uint32_t* elts,
-                                const T* const* weights, int G, T* out, int count, bool output_ntt, void* scratch,
-                                hipStream_t stream) const
+                                const T* const* weights, int G, T* out, int count, bool output_ntt, bool rescale,
+                                void* scratch, hipStream_t stream) const
         {
             kern::HoistSumArgs<T> args{};
-            const int stacks = hoist_prepare(a, c0, keys, elts, weights, G, 1, out, count, scratch, args.h);
+            const int stacks = hoist_prepare(a, c0, keys, elts, weights, G, 1, out, count, scratch, args.h, rescale);
             if (stacks == 0)
                 return;
             for (int g = 0; g < G && weights != nullptr; g++)
@@ -670,14 +789,17 @@ namespace gpuntt
             // the first launch of the call: its own grid check throws before it
             host::hoist_sum_launch<T>(a, c0, acc, reinterpret_cast<const T*>(ws + lay.inner), args, D, count, L, M, KM, n,
                                       negacyclic, stream);
-            finish(acc, out, stacks, output_ntt, stream);
+            finish(acc, out, stacks, output_ntt, rescale, stream);
         }
 
-        // x, y, out: T[2][count][L][N]; key: T[D_key][2][KM][N]; the scratch: ks_scratch(count, 2)
-        void multiply_relinearize(const T* x, const T* y, const T* key, T* out, int count, bool output_ntt, void* scratch,
-                                  hipStream_t stream) const
+        // x, y: T[2][count][L][N]; out: T[2][count][L][N], rescale: T[2][count][Lk][N]; key: T[D_key][2][KM][N]; the
+        // scratch: ks_scratch(count, 2)
+        void multiply_relinearize(const T* x, const T* y, const T* key, T* out, int count, bool output_ntt, bool rescale,
+                                  void* scratch, hipStream_t stream) const
         {
             need_transforms();
+            if (rescale)
+                need_rescale();
             const KsScratch s = ks_scratch<T>(L, M, D, n, count, 2); // checks count
             if (x == nullptr || y == nullptr || key == nullptr || out == nullptr || scratch == nullptr)
                 throw std::invalid_argument("null pointer argument");
@@ -687,6 +809,7 @@ namespace gpuntt
                 return;
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
             const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T);
+            const std::uint64_t out_bytes = cols * (rescale ? Lk : L) * 2 * sizeof(T);
             const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
             for (const auto& op : {std::pair<const void*, std::uint64_t>{x, ct_bytes}, {y, ct_bytes}, {key, key_bytes}})
             {
@@ -694,10 +817,10 @@ namespace gpuntt
                     throw std::invalid_argument("out or the scratch overlaps an operand!");
                 // out may be exactly x or exactly y: the last read of both (inner_product_tensor) precedes mod_down's
                 // first write on the stream.  Any other overlap is refused
-                if (ks_overlap(out, ct_bytes, op.first, op.second) && (op.first == key || op.first != out))
+                if (ks_overlap(out, out_bytes, op.first, op.second) && (op.first == key || op.first != out))
                     throw std::invalid_argument("out or the scratch overlaps an operand!");
             }
-            if (ks_overlap(out, ct_bytes, scratch, s.total))
+            if (ks_overlap(out, out_bytes, scratch, s.total))
                 throw std::invalid_argument("The scratch overlaps out!");
             // the batches of the transforms are ints; the grids of mod_up and mod_down: as their own launches check
             if (static_cast<unsigned long long>(D) * static_cast<unsigned>(count) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
@@ -725,14 +848,16 @@ namespace gpuntt
             mod_up(d2, a, count, BaseConvMode::centred, stream);
             ntt_full_f->execute(a, a, D * count * M, stream);
             host::relin_inner_launch<T>(a, key, acc, consts, x, y, args, D, count, L, M, KM, n, true, stream);
-            finish(acc, out, 2 * count, output_ntt, stream);
+            finish(acc, out, 2 * count, output_ntt, rescale, stream);
         }
 
         // xs, ys: host arrays of `terms` pointers to T[2][count][L][N]; everything else as multiply_relinearize
         void multiply_relinearize_sum(const T* const* xs, const T* const* ys, int terms, const T* key, T* out, int count,
-                                      bool output_ntt, void* scratch, hipStream_t stream) const
+                                      bool output_ntt, bool rescale, void* scratch, hipStream_t stream) const
         {
             need_transforms();
+            if (rescale)
+                need_rescale();
             const KsScratch s = ks_scratch<T>(L, M, D, n, count, 2); // checks count
             if (terms < 1 || terms > KEYSWITCH_MAX_TERMS)
                 throw std::invalid_argument("Invalid terms!");
@@ -752,18 +877,19 @@ namespace gpuntt
                 return;
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
             const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T);
+            const std::uint64_t out_bytes = cols * (rescale ? Lk : L) * 2 * sizeof(T);
             const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
             // out may be exactly any x[t] or y[t]: the last read of them (inner_product_tensor_sum) precedes mod_down's
             // first write on the stream.  Any other overlap is refused
-            if (ks_overlap(scratch, s.total, key, key_bytes) || ks_overlap(out, ct_bytes, key, key_bytes))
+            if (ks_overlap(scratch, s.total, key, key_bytes) || ks_overlap(out, out_bytes, key, key_bytes))
                 throw std::invalid_argument("out or the scratch overlaps an operand!");
             for (int t = 0; t < 2 * terms; t++)
             {
                 const T* op = t < terms ? xs[t] : ys[t - terms];
-                if (ks_overlap(scratch, s.total, op, ct_bytes) || (ks_overlap(out, ct_bytes, op, ct_bytes) && op != out))
+                if (ks_overlap(scratch, s.total, op, ct_bytes) || (ks_overlap(out, out_bytes, op, ct_bytes) && op != out))
                     throw std::invalid_argument("out or the scratch overlaps an operand!");
             }
-            if (ks_overlap(out, ct_bytes, scratch, s.total))
+            if (ks_overlap(out, out_bytes, scratch, s.total))
                 throw std::invalid_argument("The scratch overlaps out!");
             // the batches of the transforms are ints; the grids of mod_up and mod_down: as their own launches check
             if (static_cast<unsigned long long>(D) * static_cast<unsigned>(count) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
@@ -788,7 +914,7 @@ namespace gpuntt
             mod_up(d2, a, count, BaseConvMode::centred, stream);
             ntt_full_f->execute(a, a, D * count * M, stream);
             host::relin_sum_inner_launch<T>(a, key, acc, consts, args, D, count, L, M, KM, n, true, stream);
-            finish(acc, out, 2 * count, output_ntt, stream);
+            finish(acc, out, 2 * count, output_ntt, rescale, stream);
         }
     };
 
@@ -799,9 +925,10 @@ namespace gpuntt
         return ks_digits(q_count, alpha);
     }
 
-    template <typename T> size_t KeySwitchPlan<T>::workspace_bytes(int q_count, int p_count, int alpha, int n_power)
+    template <typename T>
+    size_t KeySwitchPlan<T>::workspace_bytes(int q_count, int p_count, int alpha, int n_power, int rescale_limbs)
     {
-        return ks_layout<T>(q_count, p_count, alpha, n_power).total;
+        return ks_layout<T>(q_count, p_count, alpha, n_power, rescale_limbs).total;
     }
 
     template <typename T>
@@ -834,11 +961,13 @@ namespace gpuntt
                                     int p_count, int alpha, int n_power, const Root<T>* forward_table_device,
                                     const Root<T>* inverse_table_device, const Ninverse<T>* mod_inverse_host,
                                     ReductionPolynomial reduction_poly, int batch_hint, int key_mod_count,
-                                    const int* key_limbs_host, stream_t stream, void* workspace_device)
+                                    const int* key_limbs_host, stream_t stream, void* workspace_device,
+                                    int rescale_limbs)
         : p_(nullptr)
     {
         const KsHost h = ks_derive<T>(q_moduli_host, q_count, p_moduli_host, p_count, alpha);
-        const KsLayout lay = ks_layout<T>(h.L, h.K, h.alpha, n_power);
+        const KsLayout lay = ks_layout<T>(h.L, h.K, h.alpha, n_power, rescale_limbs);
+        const int R = rescale_limbs, Lk = h.L - R;
         const bool transforms = forward_table_device != nullptr || inverse_table_device != nullptr;
         if (transforms && (forward_table_device == nullptr || inverse_table_device == nullptr || mod_inverse_host == nullptr))
             throw std::invalid_argument("null pointer argument");
@@ -866,6 +995,19 @@ namespace gpuntt
         const std::vector<T> down_img = host::bc_image<T>(h.down, p->down_off);
         std::vector<Modulus<T>> full(q_moduli_host, q_moduli_host + h.L);
         full.insert(full.end(), p_moduli_host, p_moduli_host + h.K);
+        p->R = R, p->Lk = Lk;
+        std::vector<T> down_rs_img, rs_img;
+        if (R > 0)
+        {
+            // limbs Lk .. M - 1 of the full base -> the kept q-limbs, and the dropped q-limbs alone -> the kept ones
+            down_rs_img = host::bc_image<T>(host::bc_derive<T>(full.data() + Lk, R + h.K, full.data(), Lk), p->down_rs_off);
+            rs_img = host::bc_image<T>(host::bc_derive<T>(full.data() + Lk, R, full.data(), Lk), p->rs_off);
+            for (int i = 0; i < R; i++)
+            {
+                p->dropped_mods.q[i] = static_cast<T>(h.mod[Lk + i]);
+                p->dropped_mods.onep[i] = static_cast<T>(h.onep[Lk + i]);
+            }
+        }
 
         void* raw = workspace_device;
         if (raw == nullptr)
@@ -880,6 +1022,13 @@ namespace gpuntt
                                             stream));
             GPUNTT_HIP_CHECK(hipMemcpyAsync(p->ws + lay.down, down_img.data(), down_img.size() * sizeof(T),
                                             hipMemcpyHostToDevice, stream));
+            if (R > 0)
+            {
+                GPUNTT_HIP_CHECK(hipMemcpyAsync(p->ws + lay.down_rs, down_rs_img.data(), down_rs_img.size() * sizeof(T),
+                                                hipMemcpyHostToDevice, stream));
+                GPUNTT_HIP_CHECK(hipMemcpyAsync(p->ws + lay.rs, rs_img.data(), rs_img.size() * sizeof(T),
+                                                hipMemcpyHostToDevice, stream));
+            }
             GPUNTT_HIP_CHECK(hipStreamSynchronize(stream)); // the images die with this scope
             p->inner.reset(new InnerProductPlan<T>(full.data(), h.M, stream, p->ws + lay.inner));
             if (transforms)
@@ -893,10 +1042,22 @@ namespace gpuntt
                                                 mod_inverse_host, batch_hint, stream, p->ws + lay.ntt_q_i));
                 p->ntt_q_f.reset(new NTTPlan<T>(forward_table_device, full.data(), h.L, n_power, reduction_poly, FORWARD,
                                                 nullptr, batch_hint, stream, p->ws + lay.ntt_q_f));
+                if (R > 0)
+                {
+                    // forward over the first Lk moduli: the same table pointer; inverse over the R dropped moduli: the
+                    // table, the moduli and the n^-1 values Lk slots on
+                    p->ntt_keep_f.reset(new NTTPlan<T>(forward_table_device, full.data(), Lk, n_power, reduction_poly,
+                                                       FORWARD, nullptr, batch_hint, stream, p->ws + lay.ntt_keep_f));
+                    p->ntt_drop_i.reset(new NTTPlan<T>(inverse_table_device + (static_cast<size_t>(Lk) << n_power),
+                                                       full.data() + Lk, R, n_power, reduction_poly, INVERSE,
+                                                       mod_inverse_host + Lk, batch_hint, stream,
+                                                       p->ws + lay.ntt_drop_i));
+                }
             }
         }
         catch (...)
         {
+            p->ntt_keep_f.reset(), p->ntt_drop_i.reset();
             p->inner.reset(), p->ntt_full_f.reset(), p->ntt_full_i.reset(), p->ntt_q_i.reset(), p->ntt_q_f.reset();
             if (p->owns)
                 (void) hipFree(p->ws);
@@ -909,6 +1070,7 @@ namespace gpuntt
     {
         if (p_ == nullptr)
             return;
+        p_->ntt_keep_f.reset(), p_->ntt_drop_i.reset();
         p_->inner.reset(), p_->ntt_full_f.reset(), p_->ntt_full_i.reset(), p_->ntt_q_i.reset(), p_->ntt_q_f.reset();
         if (p_->owns)
             (void) hipFree(p_->ws);
@@ -952,21 +1114,65 @@ namespace gpuntt
                                               bool output_ntt, void* scratch_device, stream_t stream) const
     {
         p_->rotate_hoisted_sum(device_a, device_c0, device_keys_host, galois_elements_host, device_weights_host, elements,
-                               device_out, count, output_ntt, scratch_device, stream);
+                               device_out, count, output_ntt, false, scratch_device, stream);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::rotate_hoisted_sum_rescale(const T* device_a, const T* device_c0,
+                                                      const T* const* device_keys_host,
+                                                      const std::uint32_t* galois_elements_host,
+                                                      const T* const* device_weights_host, int elements, T* device_out,
+                                                      int count, bool output_ntt, void* scratch_device,
+                                                      stream_t stream) const
+    {
+        p_->rotate_hoisted_sum(device_a, device_c0, device_keys_host, galois_elements_host, device_weights_host, elements,
+                               device_out, count, output_ntt, true, scratch_device, stream);
     }
     template <typename T>
     void KeySwitchPlan<T>::multiply_relinearize(const T* device_x, const T* device_y, const T* device_key, T* device_out,
                                                 int count, bool output_ntt, void* scratch_device, stream_t stream) const
     {
-        p_->multiply_relinearize(device_x, device_y, device_key, device_out, count, output_ntt, scratch_device, stream);
+        p_->multiply_relinearize(device_x, device_y, device_key, device_out, count, output_ntt, false, scratch_device,
+                                 stream);
     }
+    template <typename T>
+    void KeySwitchPlan<T>::multiply_relinearize_rescale(const T* device_x, const T* device_y, const T* device_key,
+                                                        T* device_out, int count, bool output_ntt, void* scratch_device,
+                                                        stream_t stream) const
+    {
+        p_->multiply_relinearize(device_x, device_y, device_key, device_out, count, output_ntt, true, scratch_device,
+                                 stream);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::multiply_relinearize_sum_rescale(const T* const* device_x_host, const T* const* device_y_host,
+                                                            int terms, const T* device_key, T* device_out, int count,
+                                                            bool output_ntt, void* scratch_device, stream_t stream) const
+    {
+        p_->multiply_relinearize_sum(device_x_host, device_y_host, terms, device_key, device_out, count, output_ntt, true,
+                                     scratch_device, stream);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::mod_down_rescale(const T* device_x, T* device_out, int stacks, stream_t stream) const
+    {
+        p_->mod_down_rescale(device_x, device_out, stacks, stream);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::rescale(const T* device_x, T* device_out, int stacks, bool ntt_form, void* scratch_device,
+                                   stream_t stream) const
+    {
+        p_->rescale(device_x, device_out, stacks, ntt_form, scratch_device, stream);
+    }
+    template <typename T> size_t KeySwitchPlan<T>::rescale_scratch_bytes(int stacks) const
+    {
+        return p_->rescale_scratch(stacks);
+    }
+    template <typename T> int KeySwitchPlan<T>::rescale_limbs() const { return p_->R; }
 
     template <typename T>
     void KeySwitchPlan<T>::multiply_relinearize_sum(const T* const* device_x_host, const T* const* device_y_host, int terms,
                                                     const T* device_key, T* device_out, int count, bool output_ntt,
                                                     void* scratch_device, stream_t stream) const
     {
-        p_->multiply_relinearize_sum(device_x_host, device_y_host, terms, device_key, device_out, count, output_ntt,
+        p_->multiply_relinearize_sum(device_x_host, device_y_host, terms, device_key, device_out, count, output_ntt, false,
                                      scratch_device, stream);
     }
     template <typename T>
@@ -1077,6 +1283,31 @@ namespace gpuntt
                 conv[j] = static_cast<std::uint64_t>(s);
             }
         }
+
+        // convert_and_divide (centred) inside stacks of `limbs` limbs: the input base of `c` is limbs c.K .. c.K + c.L - 1
+        // of every stack, its output base limbs 0 .. c.K - 1; out: T[stacks][c.K][N]
+        template <typename T>
+        void ks_ref_divide(const host::BcHostConsts& c, const T* x_host, T* out_host, int n_power, int stacks, int limbs)
+        {
+            const size_t n = size_t(1) << n_power;
+            std::uint64_t x[BASECONV_MAX_COUNT], conv[BASECONV_MAX_COUNT];
+            for (int s = 0; s < stacks; s++)
+                for (size_t j = 0; j < n; j++)
+                {
+                    const T* src = x_host + static_cast<size_t>(s) * limbs * n + j;
+                    for (int k = 0; k < c.L; k++)
+                        x[k] = src[(c.K + k) * n];
+                    ks_ref_convert<T>(c, x, true, conv);
+                    for (int i = 0; i < c.K; i++)
+                    {
+                        const std::uint64_t q = c.p[i];
+                        const std::uint64_t w = src[i * n] % q;
+                        const std::uint64_t diff = w >= conv[i] ? w - conv[i] : w + (q - conv[i]);
+                        out_host[(static_cast<size_t>(s) * c.K + i) * n + j] =
+                            static_cast<T>(static_cast<U128>(diff) * c.qinv[i] % q);
+                    }
+                }
+        }
     } // namespace
 
     template <typename T>
@@ -1111,25 +1342,42 @@ namespace gpuntt
     {
         const KsHost h = ks_derive<T>(q_moduli_host, q_count, p_moduli_host, p_count, 1, false); // {p} -> {q} only
         ks_check_mod_down<T>(h.L, h.M, x_host, out_host, n_power, stacks);
-        const size_t n = size_t(1) << n_power;
-        const int L = h.L, K = h.K, M = h.M;
-        std::uint64_t x[BASECONV_MAX_COUNT], conv[BASECONV_MAX_COUNT];
-        for (int s = 0; s < stacks; s++)
-            for (size_t j = 0; j < n; j++)
-            {
-                const T* src = x_host + static_cast<size_t>(s) * M * n + j;
-                for (int k = 0; k < K; k++)
-                    x[k] = src[(L + k) * n];
-                ks_ref_convert<T>(h.down, x, true, conv);
-                for (int i = 0; i < L; i++)
-                {
-                    const std::uint64_t q = h.mod[i];
-                    const std::uint64_t c = src[i * n] % q;
-                    const std::uint64_t diff = c >= conv[i] ? c - conv[i] : c + (q - conv[i]);
-                    out_host[(static_cast<size_t>(s) * L + i) * n + j] =
-                        static_cast<T>(static_cast<U128>(diff) * h.down.qinv[i] % q);
-                }
-            }
+        ks_ref_divide<T>(h.down, x_host, out_host, n_power, stacks, h.M);
+    }
+
+    template <typename T>
+    void KeySwitchPlan<T>::reference_mod_down_rescale(const Modulus<T>* q_moduli_host, int q_count,
+                                                      const Modulus<T>* p_moduli_host, int p_count, int rescale_limbs,
+                                                      const T* x_host, T* out_host, int n_power, int stacks)
+    {
+        const KsHost h = ks_derive<T>(q_moduli_host, q_count, p_moduli_host, p_count, 1, false); // every pair is checked
+        ks_check_rescale_limbs(h.L, rescale_limbs, 1);
+        const int Lk = h.L - rescale_limbs;
+        ks_check_mod_down<T>(Lk, h.M, x_host, out_host, n_power, stacks);
+        std::vector<Modulus<T>> full(q_moduli_host, q_moduli_host + h.L);
+        full.insert(full.end(), p_moduli_host, p_moduli_host + h.K);
+        const host::BcHostConsts c = host::bc_derive<T>(full.data() + Lk, rescale_limbs + h.K, full.data(), Lk);
+        ks_ref_divide<T>(c, x_host, out_host, n_power, stacks, h.M);
+    }
+
+    template <typename T>
+    void KeySwitchPlan<T>::reference_rescale(const Modulus<T>* q_moduli_host, int q_count, int rescale_limbs,
+                                             const T* x_host, T* out_host, int n_power, int stacks)
+    {
+        if (q_count < 1 || q_count > INNERPROD_MAX_MODULI)
+            throw std::invalid_argument("Invalid q_count!");
+        if (q_moduli_host == nullptr)
+            throw std::invalid_argument("null pointer argument");
+        ks_check_rescale_limbs(q_count, rescale_limbs, 1);
+        const int Lk = q_count - rescale_limbs;
+        // {dropped} -> {kept} checks the dropped pairwise and against every kept modulus; the kept among themselves here
+        const host::BcHostConsts c = host::bc_derive<T>(q_moduli_host + Lk, rescale_limbs, q_moduli_host, Lk);
+        for (int i = 0; i < Lk; i++)
+            for (int o = i + 1; o < Lk; o++)
+                if (std::__gcd(c.p[i], c.p[o]) != 1)
+                    throw std::invalid_argument("Input base moduli are not pairwise coprime!");
+        ks_check_mod_down<T>(Lk, q_count, x_host, out_host, n_power, stacks);
+        ks_ref_divide<T>(c, x_host, out_host, n_power, stacks, q_count);
     }
 
     template class KeySwitchPlan<Data32>;

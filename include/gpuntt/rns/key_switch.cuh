@@ -179,6 +179,60 @@
 //     multiply_relinearize checks, any other overlap of out or the scratch with an operand or with each other, a plan
 //     built without transforms
 //
+// Rescaling.  A plan built with rescale_limbs = R, 1 <= R <= L - 1, also divides by the last R q-primes -- the rescale that
+// follows every CKKS product (R = 1; R = 2 on 32-bit rings).  L' = L - R limbs are kept, Q_R = q_{L-R} ... q_{L-1},
+// D_R = P Q_R.  Every call below throws std::invalid_argument on a plan with R = 0.
+//   mod_down_rescale(x, out, stacks):  x = T[stacks][M][N] (coefficient form, full base), out = T[stacks][L'][N]:
+//       out[s][j] = what BaseConvPlan({q_{L-R} .. q_{L-1}, p_0 .. p_{K-1}} -> {q_0 .. q_{L'-1}})::convert_and_divide gives
+//                   in centred mode with in = limbs L' .. M-1 of stack s and c = limbs 0 .. L'-1 of stack s:
+//                   round(x / D_R) in the kept base outside that header's rounding band
+//     ONE launch of the strided kernel mod_down launches, with a second constants image: the R dropped q-limbs and the K
+//     special limbs are one contiguous run of the stack, L' N words behind its start, and are read in place (in = x + L' N,
+//     strides {M N, M N, L' N}; K + R <= 63 inputs, so the LDS stays below 64 KiB).  Checks and overlap rule: mod_down's,
+//     with the new sizes
+//   rescale(x, out, stacks, ntt_form, scratch):  x = T[stacks][L][N] over the q-base, every word any value, read modulo its
+//     q; out = T[stacks][L'][N].  For a ciphertext that has not passed a key switch: a ct x pt product, a sum.
+//     ntt_form = false, DEFINITION, word for word: convert_and_divide of BaseConvPlan({q_{L-R} .. q_{L-1}} ->
+//       {q_0 .. q_{L'-1}}), centred, with in = the dropped limbs of stack s and c = the kept limbs.  ONE launch of the
+//       strided kernel with a third image; no scratch (nullptr)
+//     ntt_form = true, DEFINITION: the q-base inverse transform of x, then that conversion, then the forward transform over
+//       the L' kept moduli.  What runs instead, no step's launch count growing with stacks:
+//         1. rescale_gather: the dropped limbs, each word reduced modulo its q, into the scratch T[stacks][R][N];
+//         2. the inverse transform over R * stacks polynomials in the scratch (the R dropped moduli only);
+//         3. the dense centred conversion (no division) from the scratch into out: conv_j in coefficient form;
+//         4. the forward transform over L' * stacks polynomials in place on out;
+//         5. rescale_sub_scale: out[s][j] = ((x[s][j] mod q_j) - out[s][j]) * Q_R^-1 mod q_j, canonical.
+//       R + L' transforms per stack instead of L + L'.  This equals the definition word for word: with c the coefficient
+//       form of x, the definition is NTT_j((c_j - conv_j) Q_R^-1 mod q_j); the forward transform is linear modulo q_j, so
+//       that is (NTT_j(c_j) - NTT_j(conv_j)) Q_R^-1 mod q_j, NTT_j(c_j) is x_j as a residue and NTT_j(conv_j) is what step 4
+//       leaves in out; both sides are canonical residues, hence the same word
+//     The scratch is rescale_scratch_bytes(stacks) bytes, 256-byte aligned; out must not overlap x or the scratch, nor the
+//     scratch x.  Allocates nothing, never synchronises, capturable as it is; stacks = 0 launches nothing.  A plan without
+//     transforms supports ntt_form = false only
+//   multiply_relinearize_rescale, multiply_relinearize_sum_rescale, rotate_hoisted_sum_rescale:  arguments, refusals,
+//     scratch sizes and the rule "out may be exactly an operand" are those of the call without the suffix; out =
+//     T[2][count][L'][N].  DEFINITION, through the existing calls: the accumulators of the call without the suffix as its
+//     own description gives them -- for the two products, the full-base multiply_accumulate of decompose(d2) with the key;
+//     for the rotations, acc of rotate_hoisted_sum without its c0 term -- taken to coefficient form by the full-base
+//     inverse transform; P d_c (P c0, rotated and weighted) in coefficient form added to their q-limbs modulo q_m; then
+//     mod_down_rescale over 2 * count stacks and, with output_ntt, the forward transform over the L' kept moduli.  What
+//     runs is the existing sequence up to the accumulators in the scratch (the P d fold in the NTT domain, equal by
+//     linearity), then finish with the rescale flag: the full-base INTT, mod_down_rescale, [the NTT over L' * stacks].
+//     NOT word for word "the call without the suffix, then rescale": that expression rounds twice, this one once.  With X
+//     the integer in the full-base stack, the two steps return round(round(X / P) / Q_R), this call round(X / (P Q_R)).
+//     The two differ by at most 1 per coefficient outside the rounding bands: round(X / P) = X / P + e with |e| <= 1/2
+//     moves the argument of the outer round by at most 1 / (2 Q_R), so the two-step value lies within 1/2 + 1 / (2 Q_R)
+//     of X / (P Q_R) and the fused one within 1/2 -- two integers less than 2 apart.
+//     The P d fold stays exact: P d vanishes modulo the p_k, and modulo the dropped q-limbs it is simply part of X -- the
+//     conversion now reads those limbs, and they hold c_j + P d as the definition says.
+//     switch_digits, apply and rotate_hoisted get no rescale variant: a key switch or a rotation alone does not change the
+//     scale
+//   workspace and waits with R > 0: two more constants images (bc_image of {q_{L-R} .., p} -> {q_0 ..} and of {q_{L-R} ..}
+//     -> {q_0 ..}) and, when the plan has transforms, two more NTTPlans -- forward over the first L' moduli (the same table
+//     pointer), inverse over the R dropped moduli (table pointer, moduli and n^-1 values L' slots on) -- which wait for the
+//     stream once each: up to eight host waits per plan, none afterwards.  With R = 0 workspace_bytes, the waits and every
+//     launch are those of a plan built without the argument
+//
 //   * ranges: 1 <= L, 1 <= K, M = L + K <= 64, alpha >= 1, 1 <= components <= 4, count >= 0 and stacks >= 0 (0: nothing
 //     happens), n_power in [1, 28], M <= key_mod_count <= 256.  A plan is built for ONE level (one L) and one ring; a
 //     caller at a lower level builds another plan and points it at the full-level key through key_mod_count /
@@ -192,7 +246,8 @@
 //   * workspace: every constant and every NTTPlan lives in workspace_bytes(L, K, alpha, n_power) bytes of device memory
 //     (nullptr = the plan allocates and owns it; owns_workspace()).  The constructor waits for `stream`: once for its own
 //     constants and once in each plan it builds (the inner product's and the four NTTPlans) -- up to six host waits per
-//     plan, none afterwards
+//     plan, none afterwards.  rescale_limbs = R > 0: workspace_bytes(L, K, alpha, n_power, R) bytes and two more waits
+//     ("Rescaling" above); R outside [0, L - 1]: std::invalid_argument ("Invalid rescale_limbs!")
 //   * scratch: scratch_bytes(L, K, alpha, n_power, count, components) bytes owned by the CALLER, 256-byte aligned; the
 //     pipeline methods allocate nothing and never synchronise, so apply can be captured on one stream as it is.
 //     mod_up and mod_down allocate nothing, never synchronise and launch exactly one kernel
@@ -245,7 +300,7 @@ namespace gpuntt
     template <typename T> class KeySwitchPlan
     {
       public:
-        static size_t workspace_bytes(int q_count, int p_count, int alpha, int n_power);
+        static size_t workspace_bytes(int q_count, int p_count, int alpha, int n_power, int rescale_limbs = 0);
         static size_t scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count, int components);
         static size_t hoisted_scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count, int elements);
         static size_t hoisted_sum_scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count);
@@ -254,7 +309,8 @@ namespace gpuntt
         KeySwitchPlan(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* p_moduli_host, int p_count,
                       int alpha, int n_power, const Root<T>* forward_table_device, const Root<T>* inverse_table_device,
                       const Ninverse<T>* mod_inverse_host, ReductionPolynomial reduction_poly, int batch_hint,
-                      int key_mod_count, const int* key_limbs_host, stream_t stream, void* workspace_device = nullptr);
+                      int key_mod_count, const int* key_limbs_host, stream_t stream, void* workspace_device = nullptr,
+                      int rescale_limbs = 0);
         ~KeySwitchPlan();
         KeySwitchPlan(const KeySwitchPlan&) = delete;
         KeySwitchPlan& operator=(const KeySwitchPlan&) = delete;
@@ -281,7 +337,23 @@ namespace gpuntt
                                       const T* device_key, T* device_out, int count, bool output_ntt,
                                       void* scratch_device, stream_t stream) const;
 
+        // rescaling: a plan built with rescale_limbs = R > 0; every one of them throws on a plan with R = 0
+        void mod_down_rescale(const T* device_x, T* device_out, int stacks, stream_t stream) const;
+        void rescale(const T* device_x, T* device_out, int stacks, bool ntt_form, void* scratch_device,
+                     stream_t stream) const;
+        size_t rescale_scratch_bytes(int stacks) const; // the scratch of rescale(ntt_form = true): T[stacks][R][N]
+        void multiply_relinearize_rescale(const T* device_x, const T* device_y, const T* device_key, T* device_out,
+                                          int count, bool output_ntt, void* scratch_device, stream_t stream) const;
+        void multiply_relinearize_sum_rescale(const T* const* device_x_host, const T* const* device_y_host, int terms,
+                                              const T* device_key, T* device_out, int count, bool output_ntt,
+                                              void* scratch_device, stream_t stream) const;
+        void rotate_hoisted_sum_rescale(const T* device_a, const T* device_c0, const T* const* device_keys_host,
+                                        const std::uint32_t* galois_elements_host, const T* const* device_weights_host,
+                                        int elements, T* device_out, int count, bool output_ntt, void* scratch_device,
+                                        stream_t stream) const;
+
         int q_count() const;
+        int rescale_limbs() const; // R
         int p_count() const;
         int alpha() const;
         int digits() const;
@@ -302,6 +374,13 @@ namespace gpuntt
                                      BaseConvMode mode);
         static void reference_mod_down(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* p_moduli_host,
                                        int p_count, const T* x_host, T* out_host, int n_power, int stacks);
+        // host only (no GPU): mod_down_rescale and rescale(ntt_form = false) on HOST arrays, in the same manner.
+        // rescale_limbs outside [1, q_count - 1] throws ("Invalid rescale_limbs!")
+        static void reference_mod_down_rescale(const Modulus<T>* q_moduli_host, int q_count,
+                                               const Modulus<T>* p_moduli_host, int p_count, int rescale_limbs,
+                                               const T* x_host, T* out_host, int n_power, int stacks);
+        static void reference_rescale(const Modulus<T>* q_moduli_host, int q_count, int rescale_limbs, const T* x_host,
+                                      T* out_host, int n_power, int stacks);
 
       private:
         struct Impl;

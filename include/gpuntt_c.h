@@ -508,6 +508,90 @@ extern "C"
     int gpuntt_keyswitch_reference_mod_down_u64(const gpuntt_modulus64* q_moduli_host, int q_count, const gpuntt_modulus64* p_moduli_host,
                                                 int p_count, const uint64_t* x_host, uint64_t* out_host, int n_power, int stacks);
 
+    /* ---- extension: rescaling inside the key switching plan (include/gpuntt/rns/key_switch.cuh, "Rescaling") --------
+     * create_rescale / workspace_bytes_rescale: gpuntt_keyswitch_plan_create_* / _workspace_bytes_* with
+     * rescale_limbs = R, 0 <= R <= L - 1 (R = 0: exactly the plan and the bytes of the functions above; R > 0: two more
+     * constants images and, with transforms, two more transform plans -- two more host waits at creation).  Every call
+     * below returns an error on a plan with R = 0.  L' = L - R.
+     *   mod_down_rescale  x T[stacks][M][N] -> out T[stacks][L'][N]: centred, divided by P q_{L-R} ... q_{L-1} with one
+     *                  rounding; one launch; out must not overlap x
+     *   rescale        x T[stacks][L][N] (q-base, any words) -> out T[stacks][L'][N], divided by q_{L-R} ... q_{L-1}.
+     *                  ntt_form 0: coefficient form, one launch, scratch unused (NULL).  ntt_form 1: x and out in NTT
+     *                  form; scratch gpuntt_keyswitch_plan_rescale_scratch_bytes_*() bytes, 256-byte aligned; only the R
+     *                  dropped limbs are inverse-transformed.  out must not overlap x or the scratch
+     *   multiply_relinearize_rescale, multiply_relinearize_sum_rescale, rotate_hoisted_sum_rescale  the calls without the
+     *                  suffix with mod_down_rescale as their ModDown: out T[2][count][L'][N], rounded ONCE -- within 1 per
+     *                  coefficient of the call followed by rescale, not word for word equal to it (key_switch.cuh)
+     * host only (no GPU): reference_mod_down_rescale / reference_rescale (coefficient form), R in [1, L - 1] */
+    int gpuntt_keyswitch_plan_workspace_bytes_rescale_u32(int q_count, int p_count, int alpha, int n_power, int rescale_limbs,
+                                                          uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_create_rescale_u32(gpuntt_keyswitch_plan** plan_host, const gpuntt_modulus32* q_moduli_host,
+                                                 int q_count, const gpuntt_modulus32* p_moduli_host, int p_count, int alpha,
+                                                 int n_power, const uint32_t* forward_table, const uint32_t* inverse_table,
+                                                 const uint32_t* mod_inverse_host, int reduction_poly, int batch_hint,
+                                                 int key_mod_count, const int* key_limbs_host, int rescale_limbs,
+                                                 void* workspace_device, void* stream);
+    int gpuntt_keyswitch_plan_rescale_limbs_u32(const gpuntt_keyswitch_plan* plan); /* R, negative on error */
+    int gpuntt_keyswitch_plan_rescale_scratch_bytes_u32(const gpuntt_keyswitch_plan* plan, int stacks, uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_mod_down_rescale_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* x, uint32_t* out,
+                                                   int stacks, void* stream);
+    int gpuntt_keyswitch_plan_rescale_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* x, uint32_t* out, int stacks,
+                                          int ntt_form, void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_multiply_relinearize_rescale_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* x,
+                                                               const uint32_t* y, const uint32_t* key, uint32_t* out,
+                                                               int count, int output_ntt, void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_multiply_relinearize_sum_rescale_u32(const gpuntt_keyswitch_plan* plan,
+                                                                   const uint32_t* const* x_host,
+                                                                   const uint32_t* const* y_host, int terms,
+                                                                   const uint32_t* key, uint32_t* out, int count,
+                                                                   int output_ntt, void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_rotate_hoisted_sum_rescale_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* a,
+                                                             const uint32_t* c0, const uint32_t* const* keys_host,
+                                                             const uint32_t* galois_elements_host,
+                                                             const uint32_t* const* weights_host, int elements,
+                                                             uint32_t* out, int count, int output_ntt, void* scratch,
+                                                             void* stream);
+    int gpuntt_keyswitch_reference_mod_down_rescale_u32(const gpuntt_modulus32* q_moduli_host, int q_count,
+                                                        const gpuntt_modulus32* p_moduli_host, int p_count,
+                                                        int rescale_limbs, const uint32_t* x_host, uint32_t* out_host,
+                                                        int n_power, int stacks);
+    int gpuntt_keyswitch_reference_rescale_u32(const gpuntt_modulus32* q_moduli_host, int q_count, int rescale_limbs,
+                                               const uint32_t* x_host, uint32_t* out_host, int n_power, int stacks);
+    int gpuntt_keyswitch_plan_workspace_bytes_rescale_u64(int q_count, int p_count, int alpha, int n_power, int rescale_limbs,
+                                                          uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_create_rescale_u64(gpuntt_keyswitch_plan** plan_host, const gpuntt_modulus64* q_moduli_host,
+                                                 int q_count, const gpuntt_modulus64* p_moduli_host, int p_count, int alpha,
+                                                 int n_power, const uint64_t* forward_table, const uint64_t* inverse_table,
+                                                 const uint64_t* mod_inverse_host, int reduction_poly, int batch_hint,
+                                                 int key_mod_count, const int* key_limbs_host, int rescale_limbs,
+                                                 void* workspace_device, void* stream);
+    int gpuntt_keyswitch_plan_rescale_limbs_u64(const gpuntt_keyswitch_plan* plan); /* R, negative on error */
+    int gpuntt_keyswitch_plan_rescale_scratch_bytes_u64(const gpuntt_keyswitch_plan* plan, int stacks, uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_mod_down_rescale_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* x, uint64_t* out,
+                                                   int stacks, void* stream);
+    int gpuntt_keyswitch_plan_rescale_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* x, uint64_t* out, int stacks,
+                                          int ntt_form, void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_multiply_relinearize_rescale_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* x,
+                                                               const uint64_t* y, const uint64_t* key, uint64_t* out,
+                                                               int count, int output_ntt, void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_multiply_relinearize_sum_rescale_u64(const gpuntt_keyswitch_plan* plan,
+                                                                   const uint64_t* const* x_host,
+                                                                   const uint64_t* const* y_host, int terms,
+                                                                   const uint64_t* key, uint64_t* out, int count,
+                                                                   int output_ntt, void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_rotate_hoisted_sum_rescale_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* a,
+                                                             const uint64_t* c0, const uint64_t* const* keys_host,
+                                                             const uint32_t* galois_elements_host,
+                                                             const uint64_t* const* weights_host, int elements,
+                                                             uint64_t* out, int count, int output_ntt, void* scratch,
+                                                             void* stream);
+    int gpuntt_keyswitch_reference_mod_down_rescale_u64(const gpuntt_modulus64* q_moduli_host, int q_count,
+                                                        const gpuntt_modulus64* p_moduli_host, int p_count,
+                                                        int rescale_limbs, const uint64_t* x_host, uint64_t* out_host,
+                                                        int n_power, int stacks);
+    int gpuntt_keyswitch_reference_rescale_u64(const gpuntt_modulus64* q_moduli_host, int q_count, int rescale_limbs,
+                                               const uint64_t* x_host, uint64_t* out_host, int n_power, int stacks);
+
     /* ---- extension: prepared 4-step transforms (FourStepPlan<T>, include/gpuntt/ntt_4step/ntt_4step.cuh) ----
      * The Shoup pairs of the n1 / n2 / W tables are derived once, at creation, into workspace_device
      * (gpuntt_4step_plan_workspace_bytes_*() bytes owned by the caller) or a buffer the plan allocates (NULL).
