@@ -10,8 +10,15 @@
 //     instructions, no shifts, no compare;
 //   * qh drops the low partial products (error <= 3), so the product lands in [0, 4q);
 //   * values are kept in [0, B*q) with B tracked at COMPILE TIME per register (PassSched);
-//     a conditional subtraction is emitted only where U + 4q could overflow LIMIT*q < 2^64.
-//     For q < 2^60 (LIMIT = 16) that is one correction per two stages on the U input.
+//     a range correction is emitted only where U + 4q could overflow LIMIT*q < 2^64.
+//     Inverse passes and the 8 q / 4 q ranges correct butterfly by butterfly with conditional subtractions of a
+//     power-of-two multiple (ct_plan / gs_plan).  Forward 64-bit passes of the 16 q / 31 q ranges are planned as a
+//     WHOLE (ct_sched): per stage nothing, csub<K> for any integer K (4 instructions, halves the bound) or the
+//     quotient estimate reduce_2q (5, any value below 32 q -> [0, 2q)), cheapest plan under a hand-off cap; the
+//     two-pass plans of the rings 2^14 and 2^16 cap the hand-off of the strided pass (which has VALU time to spare)
+//     at the bound from which the VALU-bound last pass needs its fewest correction stages (ct_handoff_cap: 19 q in
+//     the 31 q range -- ONE estimate in ten stages --, 12 q in the 16 q range: three).  The host computes the
+//     bounds it dispatches by with the same constexpr functions (lazy_launch.hpp: FwdBounds, evaluated at compile time).
 //   * 32-bit moduli (q < 2^30): exact one-instruction quotient, products in [0, 2q), LIMIT 4,
 //     corrections are a subtract + unsigned min.
 //
@@ -148,12 +155,21 @@ namespace gpuntt
             }
             // x < 32 q  ->  [0, 2q): quotient estimate from the top bits, one 32 x 64 multiply-subtract.
             // HI: the modulus has >= 48 bits (nc.hi), the top bits are the high word as it stands
+            // 5 instructions with HI (v_mul_hi_u32, v_lshrrev_b32, v_mad_u64_u32, v_mul_lo_u32, v_add_u32), 6 with the
+            // 64-bit shift: k * hi32(-q) is added to the HIGH WORD alone -- as a shifted 64-bit addend it cost
+            // v_mul_lo_u32 + v_mov_b32 + v_lshl_add_u64.  (A second v_mad_u64_u32 on a pair accumulator, the Mod32
+            // form, is no gain here: its low result word is the high word of the value, register pairs are even-
+            // aligned, and the two words meet only through two v_mov_b32.)  The add is asm so that the sum is not
+            // re-canonicalised into the 64-bit form.
             template <bool HI = false> __device__ __forceinline__ uint64_t reduce_2q(uint64_t x) const
             {
                 const uint32_t xt = HI ? hi32(x) : static_cast<uint32_t>(x >> nc.sh);
                 const uint32_t k = __umulhi(xt, nc.M) >> nc.c;
                 const uint64_t r = static_cast<uint64_t>(k) * lo32(qneg) + x; // v_mad_u64_u32
-                return r + (static_cast<uint64_t>(k * hi32(qneg)) << 32);
+                const uint32_t kh = k * hi32(qneg);
+                uint32_t h;
+                asm("v_add_u32 %0, %1, %2" : "=v"(h) : "v"(hi32(r)), "v"(kh));
+                return (static_cast<uint64_t>(h) << 32) | lo32(r);
             }
             __device__ __forceinline__ uint64_t kq(int k) const { return q * static_cast<uint64_t>(k); }
             __device__ __forceinline__ bool hi_norm() const { return nc.hi != 0u; } // wave-uniform
@@ -257,7 +273,7 @@ namespace gpuntt
         {
         };
         // 31 q < 2^64 (every prime of the reference's 64-bit pools: 2^59 + small): twice the headroom, forward
-        // transforms correct the range every fourth stage instead of every second (host-side switch, lim = 31)
+        // transforms only (host-side switch, lim = 31) -- one quotient estimate carries seven stages (ct_sched below)
         template <> struct Mod<uint64_t, 31, false> : Mod64<31>
         {
         };
@@ -426,6 +442,124 @@ namespace gpuntt
             }
             p.out = bu + tb;
             return p;
+        }
+
+        // Cooley-Tukey PASS plan (64-bit forward kernels of the 16 q / 31 q families): every register of a forward pass
+        // carries the same bound, so a pass of k stages is planned as a whole.  The U inputs of a stage get ONE of
+        //   nothing                      (b + tb <= limit)
+        //   csub<K>, K = ceil(b / 2)      (any integer K: k q is a scalar multiple)            -> K,  CT_COST_CSUB
+        //   the quotient estimate        (Mod64::reduce_2q: any value below 32 q -> [0, 2 q)) -> 2,  CT_COST_EST
+        // and the stage hands over b' + tb.  ct_sched() finds the cheapest plan (VALU instructions per U value) whose
+        // hand-off bound is at most `cap`; where none is cheaper than ct_plan() at every stage, it IS that plan.
+        // The host reads values of the same function, evaluated at compile time (host::FwdBounds), so the bound it reports
+        // for a pass is the one the kernel was compiled for.
+        constexpr int CT_MAX_STAGES = 16;
+        constexpr int CT_MAX_BOUND = 32; // bounds are <= LIMIT <= 31
+        constexpr int CT_COST_CSUB = 4;
+        constexpr int CT_COST_EST = 5; // 4 where the high word gives the estimate; planned for the shifted form
+        constexpr int CT_EST = -1;     // `ku` code of the quotient estimate (as in merge_e32_kernels.hpp)
+        struct CtSched
+        {
+            int ku[CT_MAX_STAGES]; // per stage: 0, K > 0 (csub<K>) or CT_EST
+            int bu[CT_MAX_STAGES]; // bound of the stage's inputs, before the correction
+            int out;               // hand-off bound
+            int cost;              // per U value
+            bool ok;               // a plan exists
+        };
+        // today's rule: ct_plan at every stage
+        constexpr CtSched ct_sched_plain(int bound, int k, int limit, int tb)
+        {
+            CtSched s{};
+            for (int i = 0; i < k; i++)
+            {
+                const CtPlan p = ct_plan(bound, limit, tb);
+                s.ku[i] = p.ku;
+                s.bu[i] = bound;
+                s.cost += p.ku != 0 ? CT_COST_CSUB : 0;
+                bound = p.out;
+            }
+            s.out = bound;
+            s.ok = bound <= limit;
+            return s;
+        }
+        // the search itself, with the prices as arguments (1 / 1 counts correction stages: ct_handoff_cap)
+        constexpr CtSched ct_search(int bound, int k, int limit, int tb, int cap, int price_csub, int price_est)
+        {
+            constexpr int INF = 1 << 20;
+            CtSched s{};
+            if (k > CT_MAX_STAGES || limit >= CT_MAX_BOUND || bound > limit || bound < 1)
+                return s;
+            int cost[CT_MAX_STAGES + 1][CT_MAX_BOUND] = {};
+            int from[CT_MAX_STAGES + 1][CT_MAX_BOUND] = {};
+            int how[CT_MAX_STAGES + 1][CT_MAX_BOUND] = {};
+            for (int i = 0; i <= k; i++)
+                for (int b = 0; b < CT_MAX_BOUND; b++)
+                    cost[i][b] = INF;
+            cost[0][bound] = 0;
+            for (int i = 0; i < k; i++)
+                for (int b = 1; b <= limit; b++)
+                {
+                    if (cost[i][b] >= INF)
+                        continue;
+                    // candidates: (corrected bound, ku, price)
+                    const int kh = (b + 1) / 2;
+                    const int nb[3] = {b, kh, 2};
+                    const int ku[3] = {0, kh, CT_EST};
+                    const int pr[3] = {0, price_csub, price_est};
+                    for (int c = 0; c < 3; c++)
+                    {
+                        if (c == 1 && kh >= b)
+                            continue; // nothing to gain below 2 q
+                        if (c == 2 && b <= 2)
+                            continue;
+                        const int o = nb[c] + tb;
+                        if (o > limit)
+                            continue;
+                        const int t = cost[i][b] + pr[c];
+                        if (t < cost[i + 1][o])
+                        {
+                            cost[i + 1][o] = t;
+                            from[i + 1][o] = b;
+                            how[i + 1][o] = ku[c];
+                        }
+                    }
+                }
+            int best = -1;
+            for (int b = 1; b <= limit && b <= cap; b++)
+                if (cost[k][b] < INF && (best < 0 || cost[k][b] < cost[k][best]))
+                    best = b; // ties: the smallest hand-off
+            if (best < 0)
+                return s;
+            s.out = best;
+            s.cost = cost[k][best];
+            s.ok = true;
+            for (int i = k, b = best; i > 0; i--)
+            {
+                s.ku[i - 1] = how[i][b];
+                s.bu[i - 1] = from[i][b];
+                b = from[i][b];
+            }
+            return s;
+        }
+        constexpr CtSched ct_sched(int bound, int k, int limit, int tb, int cap)
+        {
+            const CtSched plain = ct_sched_plain(bound, k, limit, tb);
+            const CtSched best = ct_search(bound, k, limit, tb, cap, CT_COST_CSUB, CT_COST_EST);
+            if (plain.ok && plain.out <= cap && (!best.ok || plain.cost <= best.cost))
+                return plain;
+            return best;
+        }
+        // Hand-off cap for the pass IN FRONT of a last pass of k_next stages: the largest input bound from which that
+        // pass needs no more correction STAGES than from the smallest bound a pass can hand over at all (2 + tb, behind
+        // an estimate).  31 q range, 10 stages: 19 -- one estimate at stage 3, then 2 + 4 * 7 = 30.
+        constexpr int ct_handoff_cap(int k_next, int limit, int tb)
+        {
+            const int base = ct_search(2 + tb, k_next, limit, tb, limit, 1, 1).cost;
+            int cap = 2 + tb;
+            for (int b = 2 + tb; b <= limit; b++)
+                if (ct_search(b, k_next, limit, tb, limit, 1, 1).cost == base)
+                    cap = b;
+            return cap;
         }
 
         // Gentleman-Sande (inverse) butterfly plan:

@@ -533,14 +533,107 @@ namespace gpuntt
         inline bool lazy_lim31_modulus(uint64_t q) { return q >= 3 && q <= 0xffffffffffffffffull / 31; }
         extern template void launch_pass_lazy_lim<true, 4>(const Pass&, bool, bool, const kern::LazyArgsT<uint64_t>&, hipStream_t);
 
-        // Range bound (units of q) a forward pass of k stages hands over when it reads values below `bound` -- the
-        // run-time twin of kern::PassSched for Cooley-Tukey passes (every register carries the same bound there).
-        // The last contiguous pass of a two-pass plan is instantiated for the bound it really receives (25 q behind
-        // six strided stages, not the range limit): one round of range corrections less.
-        inline int fwd_bound_after(int bound, int k, int limit, int tb)
+        // Two-pass forward plans of the rings 2^14 and 2^16 (strided K = 4 / 6 + contiguous K = 10 on the 4096-coefficient
+        // tile) are planned ACROSS the passes: the strided pass, which has VALU time to spare under its memory time,
+        // hands over at most the bound from which the VALU-bound contiguous pass needs its fewest correction stages
+        // (lazy::ct_handoff_cap: 19 q in the 31 q range, 12 q in the 16 q range), and the contiguous pass is compiled
+        // for that bound.  Everything else keeps the contract "a pass hands over at most LIMIT".  (2^15 runs 7 + 8
+        // stages, lazy_contig_k_merge: no plan has a strided pass of 5 stages in front of a 10-stage one, so there is
+        // no capped K = 5 kernel.)
+        constexpr int FWD_CAP_CONTIG_K = 10;
+        constexpr bool fwd_cap_strided_k(int k) { return k == 4 || k == 6; }
+        // Everything the host needs of the planner at run time, evaluated at COMPILE time (a call pays table look-ups,
+        // not the search): the cap, and per stage count the hand-off bound of the pass shapes dispatch_tl instantiates
+        // -- compiled for 1 (canonical input), for the cap or for the range limit, uncapped, and for 1 with the cap.
+        struct FwdOutRow
         {
-            for (int s = 0; s < k; s++)
-                bound = lazy::ct_plan(bound, limit, tb).out;
+            int out[lazy::CT_MAX_STAGES + 1]; // by stage count; 0: no plan
+        };
+        constexpr FwdOutRow fwd_out_row(int bound, int limit, int cap)
+        {
+            FwdOutRow r{};
+            for (int k = 1; k <= lazy::CT_MAX_STAGES; k++)
+            {
+                const lazy::CtSched s = lazy::ct_sched(bound, k, limit, 4, cap);
+                r.out[k] = s.ok ? s.out : 0;
+            }
+            return r;
+        }
+        template <int LIMIT> struct FwdBounds
+        {
+            static constexpr int CAP10 = lazy::ct_handoff_cap(FWD_CAP_CONTIG_K, LIMIT, 4);
+            static constexpr FwdOutRow from_1 = fwd_out_row(1, LIMIT, LIMIT);
+            static constexpr FwdOutRow from_1_capped = fwd_out_row(1, LIMIT, CAP10);
+            static constexpr FwdOutRow from_cap = fwd_out_row(CAP10, LIMIT, LIMIT);
+            static constexpr FwdOutRow from_limit = fwd_out_row(LIMIT, LIMIT, LIMIT);
+            static int after(int bound, int k, int cap)
+            {
+                if (k < 1 || k > lazy::CT_MAX_STAGES)
+                    return 0;
+                if (cap == CAP10 && bound == 1)
+                    return from_1_capped.out[k];
+                if (cap != 0)
+                    return 0;
+                return bound == 1 ? from_1.out[k] : bound == CAP10 ? from_cap.out[k] : bound == LIMIT ? from_limit.out[k] : 0;
+            }
+        };
+        // 16 q / 31 q ranges only
+        inline int fwd_handoff_cap10(int limit) { return limit == 31 ? FwdBounds<31>::CAP10 : FwdBounds<16>::CAP10; }
+        // Range bound (units of q) a forward 64-bit pass of k stages hands over when it was compiled for values below
+        // `bound` and a hand-off cap `cap` (0: the range limit) -- the run-time twin of kern::PassSched for the passes it
+        // plans as a whole (16 q / 31 q ranges, product bound 4 q): values of the SAME constexpr function, so the two
+        // cannot disagree (tests/test_range_schedule_host.py compares them shape by shape).
+        inline int fwd_bound_after(int bound, int k, int limit, int cap = 0)
+        {
+            const int out = limit == 31 ? FwdBounds<31>::after(bound, k, cap) : limit == 16 ? FwdBounds<16>::after(bound, k, cap) : 0;
+            if (out == 0)
+                throw std::invalid_argument("internal: no range plan for a forward pass");
+            return out;
+        }
+        // hand-off cap of pass i of a forward 64-bit plan (0: none)
+        inline int fwd_pass_cap(const Plan& pl, int i, int tile_log, bool first, int limit)
+        {
+            if (pl.count != 2 || i != 0 || !first || tile_log != 12)
+                return 0;
+            const Pass& p = pl.pass[0];
+            const Pass& nx = pl.pass[1];
+            if (p.contig || !fwd_cap_strided_k(p.k) || !nx.contig || nx.k != FWD_CAP_CONTIG_K)
+                return 0;
+            return fwd_handoff_cap10(limit);
+        }
+        // IN_BOUND the kernel of a forward 64-bit pass is instantiated for (dispatch_tl chooses by the same function):
+        // 1 on canonical input, the cap behind a capped hand-off (10-stage last pass on the 4096-coefficient tile), else
+        // the range limit
+        inline int fwd_inst_bound(const Pass& p, int tile_log, bool in_first, bool last, int limit)
+        {
+            if (in_first)
+                return 1;
+            if (p.contig && last && tile_log == 12 && p.k == FWD_CAP_CONTIG_K && p.in_b > 0)
+            {
+                const int cap = fwd_handoff_cap10(limit);
+                if (p.in_b <= cap)
+                    return cap;
+            }
+            return limit;
+        }
+
+        // tile a pass of a 64-bit plan on tile size `tl` runs on: only the contiguous pass runs on a big tile
+        inline int fwd_pass_tile64(const Pass& p, int tl) { return (!p.contig && p.k <= 8) ? 12 : tl; }
+        // Range bookkeeping of a forward 64-bit plan (16 q / 31 q ranges): per pass the bound it reads (in_b) and its
+        // hand-off cap; returns the bound the LAST pass hands to the normalisation.  first_bound: 1 on canonical input
+        // (partial = false), else the bound of the pass in front of the plan
+        inline int fwd_plan_bounds(Plan& pl, int tl, bool partial, int limit)
+        {
+            int bound = partial ? 16 : 1;
+            for (int i = 0; i < pl.count; i++)
+            {
+                Pass& p = pl.pass[i];
+                const int tlp = fwd_pass_tile64(p, tl);
+                const bool first = i == 0 && !partial;
+                p.in_b = bound;
+                p.cap = fwd_pass_cap(pl, i, tlp, first, limit);
+                bound = fwd_bound_after(fwd_inst_bound(p, tlp, first, i == pl.count - 1, limit), p.k, limit, p.cap);
+            }
             return bound;
         }
 
@@ -581,18 +674,18 @@ namespace gpuntt
             }
             // (64-bit rings 2^23 / 2^24 on 16384-coefficient tiles, experiment: ONE strided pass of 9 / 10 stages)
             const bool big2 = sizeof(T) == 8 && tl == 14 && pn >= 23 && !partial;
-            const Plan pl = make_plan_tl(pn, tl, tl == 12 ? (partial ? lazy_contig_k(pn) : lazy_contig_k_merge<T>(pn, INV)) : tl,
+            Plan pl = make_plan_tl(pn, tl, tl == 12 ? (partial ? lazy_contig_k(pn) : lazy_contig_k_merge<T>(pn, INV)) : tl,
                                          big2 ? 10 : (sizeof(T) == 4 && tl == 15) ? 9 : 8);
             const void* src = base.in;
-            int fwd_bound = partial ? 16 : 1; // range bound of the values in flight (forward, 31 q range: see fwd_bound_after)
+            // range bounds of the values in flight and hand-off caps (forward 64-bit, 16 q / 31 q ranges)
+            if (!INV && sizeof(T) == 8 && (base.lim == 31 || base.lim == 0))
+                fwd_plan_bounds(pl, tl, partial, base.lim == 31 ? 31 : 16);
             for (int i = 0; i < pl.count; i++)
             {
                 Pass p = INV ? pl.pass[pl.count - 1 - i] : pl.pass[i];
-                if (!INV && sizeof(T) == 8 && base.lim == 31)
-                {
-                    p.in_b = fwd_bound;
-                    fwd_bound = fwd_bound_after(fwd_bound, p.k, 31, 4);
-                }
+                // 64-bit: only the contiguous pass runs on a big tile
+                // (32-bit plans on the 32768-coefficient tile: their strided pass runs on 16384-coefficient tiles)
+                const int tlp = sizeof(T) == 8 ? fwd_pass_tile64(p, tl) : (tl == 15 && !p.contig) ? 14 : tl;
                 kern::LazyArgsT<T> a = base;
                 a.in = src;
                 a.p_lo = p.p_lo;
@@ -606,9 +699,6 @@ namespace gpuntt
                 // of the hand-off; GPUNTT_NO_REVERSE=1 switches it off for A/B timing)
                 if (((pl.count - 1 - i) & 1) != 0 && lazy_reverse_passes())
                     a.flags |= kern::F_REVERSE;
-                // 64-bit: only the contiguous pass runs on a big tile
-                // (32-bit plans on the 32768-coefficient tile: their strided pass runs on 16384-coefficient tiles)
-                const int tlp = (sizeof(T) == 8 && !p.contig && p.k <= 8) ? 12 : (sizeof(T) == 4 && tl == 15 && !p.contig) ? 14 : tl;
                 // rings from 2^20: the per-lane twiddles of a contiguous pass are tens of MiB per
                 // polynomial -- poly-minor block order lets a batch share them through L2
                 const unsigned long long polys = base.total >> base.n;

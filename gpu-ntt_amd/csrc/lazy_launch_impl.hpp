@@ -7,12 +7,13 @@ namespace gpuntt
 {
     namespace host
     {
-        template <typename T, int TLOG, bool INV, bool CONTIG, int K, int IN_BOUND, bool LAST, int LIMSEL = 0, bool P4 = false>
+        template <typename T, int TLOG, bool INV, bool CONTIG, int K, int IN_BOUND, bool LAST, int LIMSEL = 0, bool P4 = false,
+                  int CAP = 0>
         inline void launch_lazy_one(const kern::LazyArgsT<T>& a, unsigned grid, hipStream_t stream)
         {
             if constexpr (P4)
                 note_contig_p4_launch();
-            GPUNTT_LAUNCH_FAMILY(LIMSEL, (kern::merge_pass_lazy<T, TLOG, INV, CONTIG, K, IN_BOUND, LAST, LIMSEL, 0, P4>), dim3(grid),
+            GPUNTT_LAUNCH_FAMILY(LIMSEL, (kern::merge_pass_lazy<T, TLOG, INV, CONTIG, K, IN_BOUND, LAST, LIMSEL, 0, P4, CAP>), dim3(grid),
                                dim3(kern::LTile<TLOG>::NT), 0, stream, a);
             GPUNTT_HIP_CHECK(hipGetLastError());
         }
@@ -20,6 +21,7 @@ namespace gpuntt
         // Instantiated pass shapes (everything run_transform_lazy can ask for):
         //   single pass       CONTIG K = n <= TLOG              (IN 1, last)   [TLOG 14: K = 13, 14 only]
         //   forward, n > TLOG STRIDED K 1..8 (IN 1 | LIMIT, not last) + CONTIG K (IN LIMIT, last)
+        //                     64-bit, 16 q / 31 q ranges, 2^14 / 2^16: STRIDED K 4 / 6 (IN 1, hand-off cap) + CONTIG 10 (IN cap)
         //   inverse, n > TLOG CONTIG K (IN 1, not last) + STRIDED K 1..8 (IN LIMIT / 2, last | not last)
         //   with CONTIG K in 8..12 for 4096-coefficient tiles and K = 14 for 16384-coefficient tiles
         template <typename T, int TLOG, bool INV, int LIMSEL = 0>
@@ -34,6 +36,11 @@ namespace gpuntt
             if (tiles > 0x7fffffffull)
                 throw std::invalid_argument("batch_size * N too large for one launch");
             const unsigned grid = lazy_grid_cap<T, LIMSEL>(tiles, a.go_flag);
+            // forward 64-bit, 16 q / 31 q ranges: two-pass plans of 2^14 / 2^16 are planned across their passes (lazy_launch.hpp)
+            constexpr bool CAPPED = sizeof(T) == 8 && !INV && TLOG == 12 && (LIM == 16 || LIM == 31);
+            constexpr int CAP10 = CAPPED ? FwdBounds<CAPPED ? LIM : 16>::CAP10 : LIM;
+            if (!CAPPED && p.cap != 0)
+                throw std::invalid_argument("internal: no capped hand-off in this kernel family");
 #define GPUNTT_ONE(CONTIG_, K_, IN_, LAST_)                                                      \
     return launch_lazy_one<T, TLOG, INV, CONTIG_, K_, IN_, LAST_, LIMSEL>(a, grid, stream)
             if constexpr (sizeof(T) == 8 && TLOG >= 13)
@@ -117,19 +124,19 @@ namespace gpuntt
                                 case 10:
                                     // four-polynomial tile (Pass::p4, run_transform_lazy: whole groups of
                                     // 4 * mod_count polynomials): same grid, same bounds
+                                    // behind a hand-off of at most CAP10 (two-pass plans of 2^14 .. 2^16; the low stages
+                                    // of a 4-step ring): the kernel compiled for that bound -- fewest correction stages
                                     if constexpr (sizeof(T) == 8)
                                         if (p.p4)
                                         {
-                                            if constexpr (LIM == 31)
-                                                if (p.in_b > 0 && p.in_b <= 27)
-                                                    return launch_lazy_one<T, TLOG, INV, true, 10, 27, true, LIMSEL, true>(a, grid, stream);
+                                            if constexpr (CAPPED)
+                                                if (fwd_inst_bound(p, TLOG, in_first, last, LIM) == CAP10)
+                                                    return launch_lazy_one<T, TLOG, INV, true, 10, CAP10, true, LIMSEL, true>(a, grid, stream);
                                             return launch_lazy_one<T, TLOG, INV, true, 10, LIM, true, LIMSEL, true>(a, grid, stream);
                                         }
-                                    // 31 q range behind a strided pass that hands over <= 27 q (two-pass plans
-                                    // of 2^14 .. 2^16: 17 / 21 / 25 q): three rounds of range corrections, not four
-                                    if constexpr (LIM == 31)
-                                        if (p.in_b > 0 && p.in_b <= 27)
-                                            GPUNTT_ONE(true, 10, 27, true);
+                                    if constexpr (CAPPED)
+                                        if (fwd_inst_bound(p, TLOG, in_first, last, LIM) == CAP10)
+                                            GPUNTT_ONE(true, 10, CAP10, true);
                                     GPUNTT_ONE(true, 10, LIM, true);
                                 case 11: GPUNTT_ONE(true, 11, LIM, true);
                                 case 12: GPUNTT_ONE(true, 12, LIM, true);
@@ -171,6 +178,19 @@ namespace gpuntt
             {
                 if constexpr (!INV)
                 {
+                    // first pass of a plan that is planned across its passes: hands over at most CAP10
+                    if constexpr (CAPPED)
+                        if (p.cap != 0)
+                        {
+                            if (!last && in_first && p.cap == CAP10)
+                                switch (p.k)
+                                {
+                                    case 4: return launch_lazy_one<T, TLOG, INV, false, 4, 1, false, LIMSEL, false, CAP10>(a, grid, stream);
+                                    case 6: return launch_lazy_one<T, TLOG, INV, false, 6, 1, false, LIMSEL, false, CAP10>(a, grid, stream);
+                                    default: break;
+                                }
+                            throw std::invalid_argument("internal: unsupported capped strided pass in the fast path");
+                        }
                     if (!last)
                         switch (p.k * 2 + (in_first ? 1 : 0))
                         {

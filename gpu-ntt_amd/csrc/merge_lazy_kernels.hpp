@@ -145,10 +145,18 @@ namespace gpuntt
         // ---- compile-time schedule of range corrections for one pass --------------------
         // SKIP (inverse contiguous passes only): the pass runs the stages on tile bits [SKIP, K) -- the low SKIP stages of
         // the K-bit rows were done by the pass before it (inverse 4-step of the rings 2^15 / 2^16 in Merge form)
-        template <int TLOG, bool INV, bool CONTIG, int K, int IN_BOUND, int LIMIT, int TB, int SKIP = 0> struct PassSched
+        // EST (forward 64-bit passes of the 16 q / 31 q ranges): the pass is planned as a whole by lazy::ct_sched -- a
+        // stage's correction may be csub<K> for any K or the quotient estimate (ku = lazy::CT_EST), and the hand-off
+        // bound is at most CAP (0: LIMIT, the contract of every pass that is not planned together with its successor)
+        template <int TLOG, bool INV, bool CONTIG, int K, int IN_BOUND, int LIMIT, int TB, int SKIP = 0, int CAP = 0,
+                  bool EST = false>
+        struct PassSched
         {
             using G = LGeo<TLOG, CONTIG, K>;
             static_assert(SKIP == 0 || (INV && CONTIG && SKIP < K), "partial passes: inverse, contiguous");
+            static_assert(!EST || (!INV && SKIP == 0 && K <= lazy::CT_MAX_STAGES), "whole-pass plans: forward passes");
+            static_assert(CAP == 0 || EST, "a hand-off cap needs the whole-pass plan");
+            static constexpr int HANDOFF_CAP = CAP == 0 ? LIMIT : CAP;
             static constexpr int TL = TLOG;
             static constexpr int NR = (K - SKIP + R - 1) / R;
             struct Data
@@ -190,6 +198,8 @@ namespace gpuntt
             {
                 Data d{};
                 int bound_in = IN_BOUND;
+                const lazy::CtSched whole = EST ? lazy::ct_sched(IN_BOUND, K, LIMIT, TB, HANDOFF_CAP) : lazy::CtSched{};
+                int g = 0; // stage of the pass
                 for (int r = 0; r < NR; r++)
                 {
                     int b[EPT] = {};
@@ -204,7 +214,13 @@ namespace gpuntt
                         {
                             const int j0 = (h & ((1 << jb) - 1)) | ((h >> jb) << (jb + 1));
                             const int j1 = j0 | (1 << jb);
-                            if (!INV)
+                            if (!INV && EST)
+                            {
+                                const int ku = whole.ku[g];
+                                d.ku[r][s][h] = ku;
+                                b[j0] = b[j1] = (ku == lazy::CT_EST ? 2 : (ku > 0 ? ku : b[j0])) + TB;
+                            }
+                            else if (!INV)
                             {
                                 const lazy::CtPlan pl = lazy::ct_plan(b[j0], LIMIT, TB);
                                 d.ku[r][s][h] = pl.ku;
@@ -221,6 +237,7 @@ namespace gpuntt
                                 b[j1] = TB;
                             }
                         }
+                        g++;
                     }
                     int mx = 0;
                     for (int j = 0; j < EPT; j++)
@@ -230,14 +247,23 @@ namespace gpuntt
                     }
                     bound_in = mx;
                 }
-                d.final_bound = bound_in;
+                d.final_bound = (EST && (!whole.ok || whole.out != bound_in)) ? LIMIT + 1 : bound_in; // (no plan: fails below)
                 return d;
             }
             static constexpr Data d = make();
             static_assert(d.final_bound <= LIMIT, "lazy bound exceeds the headroom");
+            static_assert(d.final_bound <= HANDOFF_CAP, "the pass hands over more than its successor was compiled for");
             // inverse passes are instantiated with IN_BOUND = LIMIT / 2 behind another inverse pass (lazy_launch_impl.hpp)
             static_assert(!INV || d.final_bound <= LIMIT / 2, "an inverse pass must hand over values below LIMIT / 2");
         };
+
+        // Which passes are planned as a whole (PassSched EST): the plain forward 64-bit passes of the 16 q / 31 q ranges
+        // with wave-uniform moduli.  PLAIN: no 4-step gather / transposition fused in.  The host tracks the hand-off bounds
+        // of exactly these passes with the same planner (host::fwd_bound_after).
+        template <typename T, bool INV, bool VQ, bool PLAIN> constexpr bool plans_whole_pass(int limit)
+        {
+            return !INV && sizeof(T) == 8 && !VQ && PLAIN && (limit == 16 || limit == 31);
+        }
 
         // waves per SIMD requested from the register allocator: four 256-thread tiles per CU
         // (128 VGPRs) or two 1024-thread tiles per CU (64 VGPRs; the 32-bit kernels fit once the
@@ -408,7 +434,7 @@ namespace gpuntt
         // and only the operand classes change: q, -q, twiddles and n^-1 in vector registers (lazy::Mod<T, LIM, true>).
         template <typename T, int TLOG, bool INV, bool CONTIG, int K, int IN_BOUND, bool LAST,
                   Fst FST = Fst::none, int LIM = 0, Xp XP = Xp::none, int SKIP = 0, bool VQ = false, int ROWLEN = 0,
-                  bool P4 = false>
+                  bool P4 = false, int CAP = 0>
         __device__ __forceinline__ void pass_body(const LazyArgsT<T>& a, T* lds, T q_value, T q_bit, T q_mu,
                                                   int mi, unsigned long long fst_poly = 0,
                                                   unsigned fst_tile = 0, long long blk_override = -1,
@@ -416,7 +442,9 @@ namespace gpuntt
         {
             using G = LGeo<TLOG, CONTIG, K>;
             using M = lazy::Mod<T, LIM, VQ>;
-            using SCH = PassSched<TLOG, INV, CONTIG, K, IN_BOUND, M::LIMIT, M::TB, SKIP>;
+            constexpr bool EST = plans_whole_pass<T, INV, VQ, (FST == Fst::none && XP == Xp::none)>(M::LIMIT);
+            static_assert(CAP == 0 || EST, "hand-off caps: plain forward 64-bit passes");
+            using SCH = PassSched<TLOG, INV, CONTIG, K, IN_BOUND, M::LIMIT, M::TB, SKIP, CAP, EST>;
             using TW = lazy::Tw<T>;
             static_assert(!VQ || (FST == Fst::none && XP == Xp::none && SKIP == 0), "per-lane moduli: plain passes");
             static_assert(!(VQ && CONTIG) || (K >= R && K < TLOG && IN_BOUND == 1 && LAST),
@@ -891,6 +919,23 @@ namespace gpuntt
                     constexpr int s = decltype(s_)::value;
                     constexpr int p = INV ? (FIRST_POS + s) : (FIRST_POS - s);
                     constexpr int jb = p - WL;
+                    // quotient estimate on the U inputs of the stage (whole-pass plans: the same correction for every
+                    // butterfly of a stage): ONE branch on the wave-uniform form of the estimate, both sides straight-line
+                    if constexpr (!INV && SCH::d.ku[r][s][0] == lazy::CT_EST)
+                    {
+                        if (m.hi_norm())
+                            static_for<EPT / 2>([&](auto h_) {
+                                constexpr int h = decltype(h_)::value;
+                                constexpr int j0 = (h & ((1 << jb) - 1)) | ((h >> jb) << (jb + 1));
+                                v[j0] = m.template reduce_2q<true>(v[j0]);
+                            });
+                        else
+                            static_for<EPT / 2>([&](auto h_) {
+                                constexpr int h = decltype(h_)::value;
+                                constexpr int j0 = (h & ((1 << jb) - 1)) | ((h >> jb) << (jb + 1));
+                                v[j0] = m.template reduce_2q<false>(v[j0]);
+                            });
+                    }
                     static_for<EPT / 2>([&](auto h_) {
                         constexpr int h = decltype(h_)::value;
                         constexpr int j0 = (h & ((1 << jb) - 1)) | ((h >> jb) << (jb + 1));
@@ -902,7 +947,7 @@ namespace gpuntt
                         {
                             constexpr int ku = SCH::d.ku[r][s][h];
                             T U = v[j0];
-                            if constexpr (ku != 0)
+                            if constexpr (ku > 0)
                                 U = m.template csub<ku>(U);
                             // first stage of a cyclic transform: table[0] = omega^0 = 1 for every
                             // butterfly (block-uniform scalar test, so tables that differ still work);
@@ -1428,7 +1473,7 @@ namespace gpuntt
         // of FOUR polynomials that share a modulus (contig_p4_map.hpp) -- block b -> segment b % 2^(n-10) of modulus
         // (b >> (n-10)) % mod_count of polynomial group (b >> (n-10)) / mod_count; the host sends whole groups only
         template <typename T, int TLOG, bool INV, bool CONTIG, int K, int IN_BOUND, bool LAST, int LIM = 0, int SKIP = 0,
-                  bool P4 = false>
+                  bool P4 = false, int CAP = 0>
         __global__ __launch_bounds__(LTile<TLOG>::NT, (LOcc<TLOG, T>::WAVES)) void merge_pass_lazy(LazyArgsT<T> a)
         {
             using M = lazy::Mod<T, LIM>;
@@ -1484,7 +1529,7 @@ namespace gpuntt
                     qb = md.bit;
                     qm = md.mu;
                 }
-                pass_body<T, TLOG, INV, CONTIG, K, IN_BOUND, LAST, Fst::none, LIM, Xp::none, SK, false, 0, true>(
+                pass_body<T, TLOG, INV, CONTIG, K, IN_BOUND, LAST, Fst::none, LIM, Xp::none, SK, false, 0, true, CAP>(
                     a, lds, qv, qb, qm, mi, uniform64((poly0 << a.n) + (static_cast<unsigned long long>(seg) << K)), seg);
                 return;
             }
@@ -1511,7 +1556,8 @@ namespace gpuntt
                 qb = md.bit;
                 qm = md.mu;
             }
-            pass_body<T, TLOG, INV, CONTIG, K, IN_BOUND, LAST, Fst::none, LIM, Xp::none, SK>(a, lds, qv, qb, qm, mi, 0, 0, blk);
+            pass_body<T, TLOG, INV, CONTIG, K, IN_BOUND, LAST, Fst::none, LIM, Xp::none, SK, false, 0, false, CAP>(a, lds, qv, qb,
+                                                                                                                   qm, mi, 0, 0, blk);
                 });
         }
 

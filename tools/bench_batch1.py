@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Latency of single-polynomial transforms (the reference's own benchmark axis: batch = 1,
 logN 12..24, benchmark/bench_merge_ntt.cu:57-75).  Run once per kernel family:
-    GPUNTT_PATH=generic python tools/bench_batch1.py ; GPUNTT_PATH=fast python tools/bench_batch1.py"""
+    GPUNTT_PATH=generic python tools/bench_batch1.py ; GPUNTT_PATH=fast python tools/bench_batch1.py
+LOGN_MIN / LOGN_MAX (default 12 / 24) and BITS (default "64,32") narrow the sweep; GPUNTT_LIB picks another build."""
 import json
 import os
 import sys
@@ -17,8 +18,9 @@ g = _load_pkg()
 g.load_library()
 import torch  # noqa: E402
 
-for bits in (() if os.environ.get('SKIP_MERGE') else (64, 32)):
-    for logn in range(int(os.environ.get('LOGN_MIN', '12')), 25):
+LOGN_MIN, LOGN_MAX = int(os.environ.get('LOGN_MIN', '12')), int(os.environ.get('LOGN_MAX', '24'))
+for bits in (() if os.environ.get('SKIP_MERGE') else tuple(int(b) for b in os.environ.get('BITS', '64,32').split(','))):
+    for logn in range(LOGN_MIN, LOGN_MAX + 1):
         prm = g.NTTParameters(logn, g.X_N_minus, bits)
         n = 1 << logn
         x = (np.arange(n, dtype=np.uint64) * 2654435761 % prm.modulus.value).astype(g.np_dtype(bits))
@@ -34,7 +36,7 @@ for bits in (() if os.environ.get('SKIP_MERGE') else (64, 32)):
                           "batch": 1, "us": round(ms * 1e3, 2), "plan_us": round(msp * 1e3, 2)}), flush=True)
 
 # 4-step, single polynomial (benchmark/bench_4step_ntt.cu:96-100 sweeps the same axis), pre-transposed input
-for logn in range(12, 25):
+for logn in range(max(LOGN_MIN, 12), LOGN_MAX + 1):
     p4 = g.NTTParameters4Step(logn, 64)
     x = (np.arange(p4.n, dtype=np.uint64) * 2654435761 % p4.modulus.value).astype(np.uint64)
     a = g.to_device(x)
