@@ -123,7 +123,9 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "keyswitch_plan_mod_down_rescale", "keyswitch_plan_rescale",
               "keyswitch_plan_multiply_relinearize_rescale", "keyswitch_plan_multiply_relinearize_sum_rescale",
               "keyswitch_plan_rotate_hoisted_sum_rescale", "keyswitch_reference_mod_down_rescale",
-              "keyswitch_reference_rescale")
+              "keyswitch_reference_rescale",
+              "keyswitch_plan_bsgs_scratch_bytes", "keyswitch_plan_linear_transform_bsgs",
+              "keyswitch_plan_linear_transform_bsgs_rescale")
     for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option", "gpuntt_galois_element_u32",
                                 "gpuntt_automorphism_index_map"]
 
@@ -1380,6 +1382,67 @@ class KeySwitchPlan:
                                    stream=None):
         """rotate_hoisted_sum with the rescale in its ModDown: out T[2][count][L'][N]"""
         self.rotate_hoisted_sum(a, c0, keys, elements, weights, out, count, output_ntt, scratch, stream, _rescale=True)
+
+    # ---- the double-hoisted baby-step/giant-step linear transform (key_switch.cuh, "linear_transform_bsgs") ----
+    def bsgs_scratch_bytes(self, count, n1, n2):
+        """the caller-owned scratch of linear_transform_bsgs, in bytes"""
+        out = ctypes.c_uint64()
+        _check(getattr(load_library(), "gpuntt_keyswitch_plan_bsgs_scratch_bytes_u%d" % self.bits)(
+            self.q_count, self.p_count, self.alpha, self.n_power, int(count), int(n1), int(n2), ctypes.byref(out)))
+        return int(out.value)
+
+    def linear_transform_bsgs(self, a, c0, c1, baby_keys, baby_elements, giant_keys, giant_elements, weights, out, count,
+                              output_ntt=False, scratch=None, stream=None, _rescale=False):
+        """out = sum_g sigma_{k_g}(sum_b pt_{g,b} (.) sigma_{k_b}(ct)) with n1 + n2 keys and ONE ModDown: a
+        T[D][count][M][N] (what decompose writes), c0 / c1 T[count][L][N] in NTT form (c0 may be None; c1 is needed only
+        if a baby key is None), baby_keys / giant_keys lists of n1 / n2 device tensors -- None = no key switch for that
+        step, accepted only where the element is 1 -- baby_elements / giant_elements lists of odd ints, weights a list
+        of n2 lists of n1 entries, each a device tensor of at least M x N words (the diagonal in NTT form over the full
+        base) or None = the term is ABSENT (weight 0; unlike rotate_hoisted_sum, where None means 1); out
+        T[2][count][L][N]; scratch: a device tensor of at least bsgs_scratch_bytes(count, n1, n2) bytes, 256-byte
+        aligned.  The diagonal is applied BEFORE the giant rotation (key_switch.cuh)."""
+        if baby_keys is None or baby_elements is None or giant_keys is None or giant_elements is None or weights is None:
+            raise ValueError("null pointer argument")
+        baby_keys, giant_keys = list(baby_keys), list(giant_keys)
+        baby_elements, giant_elements = [int(k) for k in baby_elements], [int(k) for k in giant_elements]
+        n1, n2, cols = len(baby_elements), len(giant_elements), self._cols(count)
+        if len(baby_keys) != n1 or len(giant_keys) != n2:
+            raise ValueError("linear_transform_bsgs takes one key (or None) per Galois element")
+        if not (1 <= n1 <= 64 and 1 <= n2 <= 64 and n1 * n2 <= 256):
+            raise ValueError("Invalid baby or giant step count!")
+        weights = [None if row is None else list(row) for row in weights]
+        if len(weights) != n2 or any(row is None or len(row) != n1 for row in weights):
+            raise ValueError("linear_transform_bsgs takes n2 lists of n1 weights (or None)")
+        if a is None or out is None or scratch is None:
+            raise ValueError("null pointer argument")
+        sized = [(a, cols * self.mod_count * self.digits, "a (D x count x M x N)"),
+                 (out, cols * self._out_limbs(_rescale) * 2, "out (2 x count x L x N)")]
+        sized += [(c, cols * self.q_count, "c%d (count x L x N)" % i) for i, c in enumerate((c0, c1)) if c is not None]
+        sized += [(k, self._key_words(2) if cols else 0, "key (D x 2 x key_mod_count x N)")
+                  for k in baby_keys + giant_keys if k is not None]
+        flat = [w for row in weights for w in row]
+        sized += [(w, self.mod_count << self.n_power if cols else 0, "weight (M x N)") for w in flat if w is not None]
+        self._check_buffers(sized)
+        _require_gpu(scratch)
+        if int(count) >= 0 and scratch.numel() * scratch.element_size() < self.bsgs_scratch_bytes(count, n1, n2):
+            raise ValueError("scratch holds fewer than bsgs_scratch_bytes(count, n1, n2) bytes")
+
+        def ptrs(ts):
+            return (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+        def elts(ks):
+            return (ctypes.c_uint32 * len(ks))(*[k & 0xFFFFFFFF for k in ks])
+
+        fn = self._pipeline_fn("linear_transform_bsgs", _rescale)
+        _check(fn(self._h, _ptr(a), _ptr(c0), _ptr(c1), ptrs(baby_keys), elts(baby_elements), n1, ptrs(giant_keys),
+                  elts(giant_elements), n2, ptrs(flat), _ptr(out), int(count), int(bool(output_ntt)), _ptr(scratch),
+                  _stream(stream)))
+
+    def linear_transform_bsgs_rescale(self, a, c0, c1, baby_keys, baby_elements, giant_keys, giant_elements, weights, out,
+                                      count, output_ntt=False, scratch=None, stream=None):
+        """linear_transform_bsgs with the rescale in its ModDown: out T[2][count][L'][N]"""
+        self.linear_transform_bsgs(a, c0, c1, baby_keys, baby_elements, giant_keys, giant_elements, weights, out, count,
+                                   output_ntt, scratch, stream, _rescale=True)
 
     def close(self):
         if self._h:

@@ -1156,6 +1156,40 @@ extern "C"
                 scratch, static_cast<hipStream_t>(stream));                                       \
         });                                                                                       \
     }                                                                                             \
+    int gpuntt_keyswitch_plan_bsgs_scratch_bytes_##S(int q_count, int p_count, int alpha, int n_power, int count,  \
+                                                     int n1, int n2, uint64_t* bytes_host)        \
+    {                                                                                             \
+        GPUNTT_NEED(bytes_host)                                                                   \
+        return guarded([&] {                                                                      \
+            *bytes_host = KeySwitchPlan<T>::bsgs_scratch_bytes(q_count, p_count, alpha, n_power, count, n1, n2);  \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_linear_transform_bsgs_##S(                                          \
+        const gpuntt_keyswitch_plan* plan, const T* a, const T* c0, const T* c1, const T* const* baby_keys_host,  \
+        const uint32_t* baby_elements_host, int n1, const T* const* giant_keys_host,              \
+        const uint32_t* giant_elements_host, int n2, const T* const* weights_host, T* out, int count,             \
+        int output_ntt, void* scratch, void* stream)                                              \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->linear_transform_bsgs(               \
+                a, c0, c1, baby_keys_host, baby_elements_host, n1, giant_keys_host, giant_elements_host, n2,      \
+                weights_host, out, count, output_ntt != 0, scratch, static_cast<hipStream_t>(stream));            \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_linear_transform_bsgs_rescale_##S(                                  \
+        const gpuntt_keyswitch_plan* plan, const T* a, const T* c0, const T* c1, const T* const* baby_keys_host,  \
+        const uint32_t* baby_elements_host, int n1, const T* const* giant_keys_host,              \
+        const uint32_t* giant_elements_host, int n2, const T* const* weights_host, T* out, int count,             \
+        int output_ntt, void* scratch, void* stream)                                              \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->linear_transform_bsgs_rescale(       \
+                a, c0, c1, baby_keys_host, baby_elements_host, n1, giant_keys_host, giant_elements_host, n2,      \
+                weights_host, out, count, output_ntt != 0, scratch, static_cast<hipStream_t>(stream));            \
+        });                                                                                       \
+    }                                                                                             \
     int gpuntt_keyswitch_reference_mod_down_rescale_##S(const CM* q_moduli_host, int q_count,     \
                                                         const CM* p_moduli_host, int p_count, int rescale_limbs,  \
                                                         const T* x_host, T* out_host, int n_power, int stacks)    \

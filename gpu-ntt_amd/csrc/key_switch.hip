@@ -30,6 +30,12 @@
 // the G elements in the extended base), then finish over 2 * count stacks whatever G is.  The two share
 // Impl::hoist_prepare: every refusal of the call and the kernel arguments.
 //
+// linear_transform_bsgs: the double-hoisted baby-step/giant-step transform.  Impl::bsgs_axis sorts each
+// axis (the steps with a key first) and refuses what the header lists; then inner_product_galois over the keyed baby
+// steps and bsgs_scale_input over the others, bsgs_weighted_sum, the plan's own INTT, mod_down, mod_up and NTT over the
+// second components of all keyed giant steps at once, inner_product_galois_giant (all of hoisted_rotation.hip) and finish
+// over 2 * count stacks.
+//
 // multiply_relinearize: tensor_top of relinearize.hip (x1 y1 into the scratch), the plan's own decompose steps on it,
 // inner_product_tensor (the inner product seeded with P (x0 y0) and P (x0 y1 + x1 y0)), then finish over 2 * count stacks
 // (DESIGN.md 3.15).
@@ -484,6 +490,31 @@ namespace gpuntt
         {
             return ks_hoisted_scratch<T>(M, n_power, count, 1);
         }
+
+        // the scratch of linear_transform_bsgs, in bytes.  u: T[n1][2][count][M][N], the baby accumulators -- dead after
+        // bsgs_weighted_sum, so acc T[2][count][M][N] lives at its start; v: T[2][n2][count][M][N], the weighted sums,
+        // component-major with the keyed giant steps first; t: T[n2 * count][L][N], the second components after mod_down;
+        // a2: T[D][n2 * count][M][N], their digits.  t and a2 are sized for n2 keyed giant steps
+        struct KsBsgsScratch
+        {
+            size_t u, v, t, a2, total;
+        };
+        template <typename T> KsBsgsScratch ks_bsgs_scratch(int L, int M, int D, int n_power, int count, int n1, int n2)
+        {
+            if (count < 0)
+                throw std::invalid_argument("Invalid count!");
+            if (n1 < 1 || n1 > KEYSWITCH_MAX_STEPS || n2 < 1 || n2 > KEYSWITCH_MAX_STEPS ||
+                n1 * n2 > KEYSWITCH_MAX_DIAGONALS)
+                throw std::invalid_argument("Invalid baby or giant step count!");
+            const size_t poly = (static_cast<size_t>(count) << n_power) * sizeof(T);
+            KsBsgsScratch s{};
+            s.u = 0;
+            s.v = s.u + ks_align(poly * M * 2 * n1);
+            s.t = s.v + ks_align(poly * M * 2 * n2);
+            s.a2 = s.t + ks_align(poly * L * n2);
+            s.total = s.a2 + ks_align(poly * M * D * n2);
+            return s;
+        }
     } // namespace
 
     template <typename T> struct KeySwitchPlan<T>::Impl
@@ -792,6 +823,132 @@ namespace gpuntt
             finish(acc, out, stacks, output_ntt, rescale, stream);
         }
 
+        // One axis of linear_transform_bsgs: the steps with a key first (into `args`, in their order), then the others;
+        // order[i] = the caller's index of step i of the scratch.  Returns the number of keyed steps
+        int bsgs_axis(const T* const* keys, const std::uint32_t* elts, int steps, kern::HoistArgs<T>& args,
+                      int* order) const
+        {
+            const std::uint32_t mask = negacyclic ? (2u << n) - 1u : (1u << n) - 1u; // as GPU_Automorphism_NTT reduces
+            int keyed = 0;
+            for (int i = 0; i < steps; i++)
+            {
+                const std::uint32_t k = elts[i] & mask;
+                if ((k & 1u) == 0u)
+                    throw std::invalid_argument("Invalid Galois element (must be odd)!");
+                if (keys[i] == nullptr && k != 1u)
+                    throw std::invalid_argument("A null key is accepted only where the element is 1!");
+                if (keys[i] != nullptr)
+                {
+                    args.elt[keyed] = k, args.inv[keyed] = galois_inverse(k) & mask, args.key[keyed] = keys[i];
+                    order[keyed++] = i;
+                }
+            }
+            args.count = keyed;
+            for (int i = 0, at = keyed; i < steps; i++)
+                if (keys[i] == nullptr)
+                    order[at++] = i;
+            for (int m = 0; m < M; m++)
+                args.limb[m] = static_cast<unsigned char>(limbs[m]);
+            for (int j = 0; j < L; j++)
+                args.p_mod_q[j] = p_mod_q[j], args.p_mod_q_shoup[j] = p_mod_q_shoup[j];
+            return keyed;
+        }
+
+        void linear_transform_bsgs(const T* a, const T* c0, const T* c1, const T* const* bkeys,
+                                   const std::uint32_t* belts, int n1, const T* const* gkeys,
+                                   const std::uint32_t* gelts, int n2, const T* const* weights, T* out, int count,
+                                   bool output_ntt, bool rescale, void* scratch, hipStream_t stream) const
+        {
+            need_transforms();
+            if (rescale)
+                need_rescale();
+            const KsBsgsScratch s = ks_bsgs_scratch<T>(L, M, D, n, count, n1, n2); // checks count, n1 and n2
+            if (a == nullptr || bkeys == nullptr || belts == nullptr || gkeys == nullptr || gelts == nullptr ||
+                weights == nullptr || out == nullptr || scratch == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
+                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            kern::HoistArgs<T> bargs{}, gargs{};
+            int border[KEYSWITCH_MAX_STEPS], gorder[KEYSWITCH_MAX_STEPS];
+            const int n1k = bsgs_axis(bkeys, belts, n1, bargs, border);
+            const int n2k = bsgs_axis(gkeys, gelts, n2, gargs, gorder);
+            if (n1k < n1 && c1 == nullptr)
+                throw std::invalid_argument("null pointer argument"); // a baby step without a key reads c1
+            kern::BsgsWeights<T> wa{};
+            wa.n1 = n1, wa.n2 = n2;
+            for (int g = 0; g < n2; g++)
+            {
+                bool any = false;
+                for (int b = 0; b < n1; b++)
+                {
+                    wa.w[g * n1 + b] = weights[gorder[g] * n1 + border[b]];
+                    any = any || wa.w[g * n1 + b] != nullptr;
+                }
+                if (!any)
+                    throw std::invalid_argument("A giant step has no present weight!");
+            }
+            if (count == 0)
+                return;
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const std::uint64_t a_bytes = cols * M * D * sizeof(T), c_bytes = cols * L * sizeof(T);
+            const std::uint64_t out_bytes = cols * (rescale ? Lk : L) * 2 * sizeof(T);
+            const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
+            const std::uint64_t weight_bytes = (static_cast<std::uint64_t>(M) << n) * sizeof(T);
+            for (const auto& w : {std::pair<const void*, std::uint64_t>{out, out_bytes}, {scratch, s.total}})
+            {
+                bool hit = ks_overlap(w.first, w.second, a, a_bytes) ||
+                           (c0 != nullptr && ks_overlap(w.first, w.second, c0, c_bytes)) ||
+                           (c1 != nullptr && ks_overlap(w.first, w.second, c1, c_bytes));
+                for (int i = 0; i < n1k; i++)
+                    hit = hit || ks_overlap(w.first, w.second, bargs.key[i], key_bytes);
+                for (int i = 0; i < n2k; i++)
+                    hit = hit || ks_overlap(w.first, w.second, gargs.key[i], key_bytes);
+                for (int i = 0; i < n1 * n2; i++)
+                    hit = hit || (wa.w[i] != nullptr && ks_overlap(w.first, w.second, wa.w[i], weight_bytes));
+                if (hit)
+                    throw std::invalid_argument("out or the scratch overlaps an operand!");
+            }
+            if (ks_overlap(out, out_bytes, scratch, s.total))
+                throw std::invalid_argument("The scratch overlaps out!");
+            // every limit before the first launch, at n2 keyed giant steps whatever their number is: the batches of the
+            // transforms are ints; the grids of mod_up, mod_down and the five kernels of hoisted_rotation.hip launch at
+            // most stacks * max(N, 256) work-items
+            const unsigned long long stacks = static_cast<unsigned long long>(n2 > 2 ? n2 : 2) * static_cast<unsigned>(count);
+            if (stacks * static_cast<unsigned>(D) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
+                throw std::invalid_argument("Invalid count!");
+            if (stacks * ((1ull << n) > 256ull ? (1ull << n) : 256ull) > 0xFFFFFFFFull)
+                throw std::invalid_argument("Invalid count!");
+
+            char* base = static_cast<char*>(scratch);
+            T* u = reinterpret_cast<T*>(base + s.u);
+            T* v = reinterpret_cast<T*>(base + s.v);
+            T* t = reinterpret_cast<T*>(base + s.t);
+            T* a2 = reinterpret_cast<T*>(base + s.a2);
+            T* acc = u; // u is dead once v is formed
+            const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
+            // 1. the baby steps: u[b] for the keyed b < n1k, then the others
+            if (n1k > 0)
+                host::hoist_launch<T>(a, c0, u, consts, bargs, D, count, L, M, KM, n, negacyclic, stream);
+            if (n1k < n1)
+                host::bsgs_scale_launch<T>(c0, c1, u, consts, bargs, n1k, n1, count, L, M, n, stream);
+            // 2. all n2 weighted sums
+            host::bsgs_sum_launch<T>(u, v, consts, wa, count, M, n, stream);
+            // 3. the second components of the keyed giant steps, one contiguous T[n2k * count][M][N]: to coefficient
+            //    form, down to the q-base and into digits again
+            if (n2k > 0)
+            {
+                T* v1 = v + static_cast<size_t>(n2) * cols * M;
+                ntt_full_i->execute(v1, v1, n2k * count * M, stream);
+                mod_down(v1, t, n2k * count, stream);
+                mod_up(t, a2, n2k * count, BaseConvMode::centred, stream);
+                ntt_full_f->execute(a2, a2, D * n2k * count * M, stream);
+            }
+            // 4. the giant steps, summed
+            host::bsgs_giant_launch<T>(a2, v, acc, consts, gargs, n2, D, count, M, KM, n, negacyclic, stream);
+            // 5. ONE ModDown
+            finish(acc, out, 2 * count, output_ntt, rescale, stream);
+        }
+
         // x, y: T[2][count][L][N]; out: T[2][count][L][N], rescale: T[2][count][Lk][N]; key: T[D_key][2][KM][N]; the
         // scratch: ks_scratch(count, 2)
         void multiply_relinearize(const T* x, const T* y, const T* key, T* out, int count, bool output_ntt, bool rescale,
@@ -954,6 +1111,17 @@ namespace gpuntt
         ks_check_counts(q_count, p_count, alpha);
         ks_check_n_power(n_power);
         return ks_hoisted_sum_scratch<T>(q_count + p_count, n_power, count);
+    }
+
+    template <typename T>
+    size_t KeySwitchPlan<T>::bsgs_scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count, int n1,
+                                                int n2)
+    {
+        ks_check_counts(q_count, p_count, alpha);
+        ks_check_n_power(n_power);
+        return ks_bsgs_scratch<T>(q_count, q_count + p_count, ks_digits(q_count, alpha > q_count ? q_count : alpha),
+                                  n_power, count, n1, n2)
+            .total;
     }
 
     template <typename T>
@@ -1126,6 +1294,36 @@ namespace gpuntt
     {
         p_->rotate_hoisted_sum(device_a, device_c0, device_keys_host, galois_elements_host, device_weights_host, elements,
                                device_out, count, output_ntt, true, scratch_device, stream);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::linear_transform_bsgs(const T* device_a, const T* device_c0, const T* device_c1,
+                                                 const T* const* baby_keys_host,
+                                                 const std::uint32_t* baby_elements_host, int n1,
+                                                 const T* const* giant_keys_host,
+                                                 const std::uint32_t* giant_elements_host, int n2,
+                                                 const T* const* weights_host, T* device_out, int count, bool output_ntt,
+                                                 void* scratch_device, stream_t stream) const
+    {
+        p_->linear_transform_bsgs(device_a, device_c0, device_c1, baby_keys_host, baby_elements_host, n1, giant_keys_host,
+                                  giant_elements_host, n2, weights_host, device_out, count, output_ntt, false,
+                                  scratch_device, stream);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::linear_transform_bsgs_rescale(const T* device_a, const T* device_c0, const T* device_c1,
+                                                         const T* const* baby_keys_host,
+                                                         const std::uint32_t* baby_elements_host, int n1,
+                                                         const T* const* giant_keys_host,
+                                                         const std::uint32_t* giant_elements_host, int n2,
+                                                         const T* const* weights_host, T* device_out, int count,
+                                                         bool output_ntt, void* scratch_device, stream_t stream) const
+    {
+        p_->linear_transform_bsgs(device_a, device_c0, device_c1, baby_keys_host, baby_elements_host, n1, giant_keys_host,
+                                  giant_elements_host, n2, weights_host, device_out, count, output_ntt, true,
+                                  scratch_device, stream);
+    }
+    template <typename T> size_t KeySwitchPlan<T>::bsgs_scratch_bytes(int count, int n1, int n2) const
+    {
+        return ks_bsgs_scratch<T>(p_->L, p_->M, p_->D, p_->n, count, n1, n2).total;
     }
     template <typename T>
     void KeySwitchPlan<T>::multiply_relinearize(const T* device_x, const T* device_y, const T* device_key, T* device_out,

@@ -178,6 +178,58 @@
 //     entry, a null key / out / scratch, a scratch that is not 256-byte aligned, count < 0, a count beyond the limits
 //     multiply_relinearize checks, any other overlap of out or the scratch with an operand or with each other, a plan
 //     built without transforms
+//   linear_transform_bsgs(a, c0, c1, baby_keys, baby_elements, n1, giant_keys, giant_elements, n2, weights, out, count,
+//     output_ntt, scratch):  a baby-step/giant-step linear transform, double hoisted (Bossuat et al.): everything stays in
+//     the extended base P Q until ONE final ModDown, with n1 + n2 switching keys for n1 * n2 diagonals.
+//     CONVENTION: out = sum_g sigma_{k_g}( sum_b pt_{g,b} (.) sigma_{k_b}(ct) ).  The diagonal is applied BEFORE the giant
+//     rotation, so a caller pre-rotates its diagonals by the inverse giant step, as every BSGS does.
+//     a = T[D][count][M][N], what decompose writes for the second components.  c0, c1 = T[count][L][N] in NTT form, any
+//     word, read modulo q_m; c0 may be nullptr ("no first component", as in rotate_hoisted); c1 is required only if some
+//     baby key is nullptr.  baby_elements / giant_elements: odd once reduced as GPU_Automorphism_NTT reduces them;
+//     duplicates and the identity are allowed.  Keys = T[D_key][2][key_mod_count][N], read through the plan's
+//     key_mod_count / key_limbs.  **A nullptr key means "no key switch for this step" and is accepted only where the
+//     reduced element is 1**: the usual b = 0 and g = 0 steps need no identity key.
+//     weights = a HOST array of n2 * n1 device pointers, row-major [g][b]; weights[g * n1 + b] = T[M][N], the diagonal
+//     pt_{g,b} in NTT form over the FULL base, any word.  **A nullptr entry means the term is ABSENT (weight 0) -- unlike
+//     rotate_hoisted_sum, where nullptr means 1.**  The array itself must not be nullptr and every giant row g must have
+//     at least one present weight.  Limits: 1 <= n1 <= 64, 1 <= n2 <= 64, n1 * n2 <= KEYSWITCH_MAX_DIAGONALS = 256.
+//     out = T[2][count][L][N].
+//     DEFINITION, word for word, through the calls that exist beside it; every residue canonical, pi = galois_ntt_source:
+//       1. baby accumulators u_b, b < n1.  With a key, rotate_hoisted's acc:
+//            u_b[c][r][m][j] = (sum_d a[d][r][m][pi_b(j)] * key_b[d][c][limb(m)][j]
+//                               + [c = 0, m < L, c0 != nullptr] (P mod q_m) * c0[r][m][pi_b(j)]) mod q_m;
+//          with a nullptr key: u_b[c][r][m][j] = [m < L] (P mod q_m) * (c_c[r][m][j] mod q_m) mod q_m, c_0 = c0 (0 if
+//          nullptr), c_1 = c1.
+//       2. v_g[c][r][m][j] = (sum_{b: present} (w_{g,b}[m][j] mod q_m) * u_b[c][r][m][j]) mod q_m -- a full-base
+//          InnerProductPlan::multiply_accumulate with the n1 stacks as digits, the weights as the key (absent = zero
+//          limbs), C = 1, over 2 * count inputs.
+//       3. giant step g with a key: t_g = mod_down(full-base GPU_INTT(v_g[1]), stacks = count); a'_g = decompose(t_g,
+//          count, input_ntt = false);
+//            s_g[c][r][m][j] = (sum_d a'_g[d][r][m][pi_g(j)] * gkey_g[d][c][limb(m)][j] + [c = 0] v_g[0][r][m][pi_g(j)])
+//                              mod q_m for ALL m < M, with multiplier 1
+//          -- GPU_Automorphism_NTT + multiply_accumulate + GPU_Automorphism_NTT(v_g[0]) added mod q_m.  With a nullptr
+//          key: s_g = v_g.  Multiplier 1 is right because v_g already lives at scale P (step 1 folded c0 in as P c0) and
+//          so do the key-switch accumulators of decompose(mod_down(V1)).
+//       4. acc[c][r][m][j] = (sum_g s_g[c][r][m][j]) mod q_m, then finish over 2 * count stacks: the full-base INTT,
+//          mod_down, [output_ntt: the q-base NTT].
+//     The fused path computes canonical residues of the same exact sums, so every word equals this composition; the
+//     order of summation and the reordering of steps inside the scratch (keyed steps first) cannot change a word.  With
+//     n2 = 1, a nullptr giant key, every baby key and every weight present, the call returns EXACTLY rotate_hoisted_sum's
+//     words for the same operands.
+//     What runs, no step's launch count growing with count, n1 or n2: inner_product_galois over the
+//     keyed baby steps and bsgs_scale_input over the others (each only if there is such a step); bsgs_weighted_sum;
+//     if a giant step has a key, the full-base INTT, mod_down, mod_up (centred) and the full-base NTT over all keyed
+//     giant steps at once; inner_product_galois_giant; finish.
+//     Contract as for rotate_hoisted_sum: allocates nothing, never synchronises, one stream, capturable as it is; count =
+//     0 launches nothing.  The scratch is bsgs_scratch_bytes(count, n1, n2) bytes, 256-byte aligned; out and the scratch
+//     must not overlap a, c0, c1, any key, any present weight or each other.  std::invalid_argument, before anything is
+//     launched: n1, n2 or their product out of range; count < 0 or beyond the grid / int limits of the transforms, mod_up
+//     and mod_down at (n2 * count, D * n2 * count * M) stacks; an even element; a nullptr key at an element != 1; a
+//     nullptr c1 while some baby key is nullptr; a nullptr weights array; a giant row with no present weight; a nullptr
+//     a / out / array / scratch; a misaligned scratch; an overlap; a plan without transforms
+//   linear_transform_bsgs_rescale:  the same on a plan built with rescale_limbs = R > 0: out = T[2][count][L'][N], step 4
+//     ends in mod_down_rescale and the NTT over the L' kept moduli, exactly as rotate_hoisted_sum_rescale relates to
+//     rotate_hoisted_sum; std::invalid_argument on a plan with R = 0
 //
 // Rescaling.  A plan built with rescale_limbs = R, 1 <= R <= L - 1, also divides by the last R q-primes -- the rescale that
 // follows every CKKS product (R = 1; R = 2 on 32-bit rings).  L' = L - R limbs are kept, Q_R = q_{L-R} ... q_{L-1},
@@ -269,6 +321,8 @@
 namespace gpuntt
 {
     constexpr int KEYSWITCH_MAX_TERMS = 32; // multiply_relinearize_sum: pairs of ciphertexts per call
+    constexpr int KEYSWITCH_MAX_DIAGONALS = 256; // linear_transform_bsgs: n1 * n2, the weight pointers of one call
+    constexpr int KEYSWITCH_MAX_STEPS = 64;      // linear_transform_bsgs: n1 and n2 each
 
     // The plan's constants as the host derived them (KeySwitchPlan::constants, gpuntt_keyswitch_constants_*): every
     // pointer is a caller array of the stated length.  d(i) = i / alpha is the digit of q-limb i.
@@ -304,6 +358,7 @@ namespace gpuntt
         static size_t scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count, int components);
         static size_t hoisted_scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count, int elements);
         static size_t hoisted_sum_scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count);
+        static size_t bsgs_scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count, int n1, int n2);
         static int digits(int q_count, int alpha); // D
 
         KeySwitchPlan(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* p_moduli_host, int p_count,
@@ -351,6 +406,19 @@ namespace gpuntt
                                         const std::uint32_t* galois_elements_host, const T* const* device_weights_host,
                                         int elements, T* device_out, int count, bool output_ntt, void* scratch_device,
                                         stream_t stream) const;
+
+        // the double-hoisted baby-step/giant-step linear transform ("linear_transform_bsgs" above); _rescale: R > 0
+        void linear_transform_bsgs(const T* device_a, const T* device_c0, const T* device_c1,
+                                   const T* const* baby_keys_host, const std::uint32_t* baby_elements_host, int n1,
+                                   const T* const* giant_keys_host, const std::uint32_t* giant_elements_host, int n2,
+                                   const T* const* weights_host, T* device_out, int count, bool output_ntt,
+                                   void* scratch_device, stream_t stream) const;
+        void linear_transform_bsgs_rescale(const T* device_a, const T* device_c0, const T* device_c1,
+                                           const T* const* baby_keys_host, const std::uint32_t* baby_elements_host, int n1,
+                                           const T* const* giant_keys_host, const std::uint32_t* giant_elements_host,
+                                           int n2, const T* const* weights_host, T* device_out, int count,
+                                           bool output_ntt, void* scratch_device, stream_t stream) const;
+        size_t bsgs_scratch_bytes(int count, int n1, int n2) const;
 
         int q_count() const;
         int rescale_limbs() const; // R

@@ -592,6 +592,41 @@ extern "C"
     int gpuntt_keyswitch_reference_rescale_u64(const gpuntt_modulus64* q_moduli_host, int q_count, int rescale_limbs,
                                                const uint64_t* x_host, uint64_t* out_host, int n_power, int stacks);
 
+    /* ---- KeySwitchPlan<T>::linear_transform_bsgs: the double-hoisted baby-step/giant-step linear transform ----
+     * out = sum_g sigma_{k_g}( sum_b pt_{g,b} (.) sigma_{k_b}(ct) ): the diagonal is applied BEFORE the giant rotation.
+     *   a T[D][count][M][N] (what decompose writes), c0 / c1 T[count][L][N] in NTT form (c0 may be NULL; c1 is needed
+     *   only if a baby key is NULL); baby_keys_host / giant_keys_host HOST arrays of n1 / n2 device pointers, a NULL key
+     *   = no key switch for that step, accepted only where the reduced element is 1; weights_host a HOST array of
+     *   n2 * n1 device pointers, row-major [g][b], each T[M][N] in NTT form over the full base -- a NULL entry means the
+     *   term is ABSENT (weight 0), unlike rotate_hoisted_sum, where NULL means 1; every giant row needs one present
+     *   weight.  1 <= n1, n2 <= 64, n1 * n2 <= 256.  out T[2][count][L][N] (L' with _rescale, a plan with R > 0).  The
+     *   scratch is gpuntt_keyswitch_plan_bsgs_scratch_bytes_*() bytes, 256-byte aligned.  n1 + n2 keys, ONE final ModDown;
+     *   every word equals the composition of the existing calls that key_switch.cuh defines */
+    int gpuntt_keyswitch_plan_bsgs_scratch_bytes_u32(int q_count, int p_count, int alpha, int n_power, int count, int n1,
+                                                     int n2, uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_bsgs_scratch_bytes_u64(int q_count, int p_count, int alpha, int n_power, int count, int n1,
+                                                     int n2, uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_linear_transform_bsgs_u32(
+        const gpuntt_keyswitch_plan* plan, const uint32_t* a, const uint32_t* c0, const uint32_t* c1,
+        const uint32_t* const* baby_keys_host, const uint32_t* baby_elements_host, int n1,
+        const uint32_t* const* giant_keys_host, const uint32_t* giant_elements_host, int n2,
+        const uint32_t* const* weights_host, uint32_t* out, int count, int output_ntt, void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_linear_transform_bsgs_u64(
+        const gpuntt_keyswitch_plan* plan, const uint64_t* a, const uint64_t* c0, const uint64_t* c1,
+        const uint64_t* const* baby_keys_host, const uint32_t* baby_elements_host, int n1,
+        const uint64_t* const* giant_keys_host, const uint32_t* giant_elements_host, int n2,
+        const uint64_t* const* weights_host, uint64_t* out, int count, int output_ntt, void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_linear_transform_bsgs_rescale_u32(
+        const gpuntt_keyswitch_plan* plan, const uint32_t* a, const uint32_t* c0, const uint32_t* c1,
+        const uint32_t* const* baby_keys_host, const uint32_t* baby_elements_host, int n1,
+        const uint32_t* const* giant_keys_host, const uint32_t* giant_elements_host, int n2,
+        const uint32_t* const* weights_host, uint32_t* out, int count, int output_ntt, void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_linear_transform_bsgs_rescale_u64(
+        const gpuntt_keyswitch_plan* plan, const uint64_t* a, const uint64_t* c0, const uint64_t* c1,
+        const uint64_t* const* baby_keys_host, const uint32_t* baby_elements_host, int n1,
+        const uint64_t* const* giant_keys_host, const uint32_t* giant_elements_host, int n2,
+        const uint64_t* const* weights_host, uint64_t* out, int count, int output_ntt, void* scratch, void* stream);
+
     /* ---- extension: prepared 4-step transforms (FourStepPlan<T>, include/gpuntt/ntt_4step/ntt_4step.cuh) ----
      * The Shoup pairs of the n1 / n2 / W tables are derived once, at creation, into workspace_device
      * (gpuntt_4step_plan_workspace_bytes_*() bytes owned by the caller) or a buffer the plan allocates (NULL).
