@@ -943,6 +943,17 @@ def keyswitch_hoist_sum_chunk(bits, digits, n_power):
     return lc
 
 
+def bsgs_sum_shape(bits, n1, n_power, aligned):
+    """test hook read-back (csrc/test_hooks.h, host only): the launch shape of bsgs_weighted_sum for this word width, n1
+    baby steps and ring -- (V, nt): words per lane (a 16-byte group, or 1) and lanes per workgroup; aligned: every base
+    pointer of the launch is 16-byte aligned"""
+    V, nt = ctypes.c_int(), ctypes.c_uint()
+    if load_library().gpuntt_test_bsgs_sum_shape(int(bits) // 8, int(n1), int(n_power), int(bool(aligned)),
+                                                 ctypes.byref(V), ctypes.byref(nt)) != 0:
+        raise ValueError("Invalid argument!")
+    return int(V.value), int(nt.value)
+
+
 def keyswitch_constants(q_moduli, p_moduli, alpha, bits=64):
     """Host (no GPU): the constants a KeySwitchPlan of these bases uploads (KeySwitchConstants<T>), as a dict of numpy
     arrays -- per digit the ModUp constants up_qhat_inv[L], up_qhat_inv_shoup[L], up_matrix[L][M], up_q_mod[D][M],

@@ -537,6 +537,14 @@ extern "C"
             return -1;
         return host::hoist_chunk_log(static_cast<size_t>(word_bytes), digits, n_power, host::HOIST_SUM_LOG_MAX);
     }
+    int gpuntt_test_bsgs_sum_shape(int word_bytes, int n1, int n_power, int aligned, int* V, unsigned* nt)
+    {
+        if ((word_bytes != 4 && word_bytes != 8) || n1 < 1 || n1 > KEYSWITCH_MAX_STEPS || n_power < 1 || n_power > 28 ||
+            V == nullptr || nt == nullptr)
+            return -1;
+        host::bsgs_sum_shape(static_cast<size_t>(word_bytes), n1, n_power, aligned != 0, *V, *nt);
+        return 0;
+    }
 
     int gpuntt_galois_element_u32(int steps, int n_power, int conjugation, uint32_t* elt_host)
     {

@@ -36,6 +36,10 @@
  *   gpuntt_test_keyswitch_hoist_sum_chunk(word_bytes, digits, n_power)  the same for the destination chunk of
  *                                       inner_product_galois_sum (rotate_hoisted_sum): the same rule capped at one slot per
  *                                       lane, 256 slots, which the hook keyswitch_hoist_chunk forces as well, inside that cap
+ *   gpuntt_test_bsgs_sum_shape(word_bytes, n1, n_power, aligned, V, nt)  host only: the launch shape bsgs_weighted_sum
+ *                                       (linear_transform_bsgs) takes for this word size, n1 baby steps and ring -- V words
+ *                                       per lane (a 16-byte group, or 1) and nt lanes per workgroup; aligned: every base
+ *                                       pointer of the launch is 16-byte aligned; -1: bad argument
  * Options are snapshot once per API call (prep.hip), so a hook set while another thread's call is in flight does not change
  * that call. */
 #ifndef GPUNTT_TEST_HOOKS_H
@@ -52,6 +56,7 @@ extern "C"
     unsigned long long gpuntt_test_alloc_count(void);
     int gpuntt_test_keyswitch_hoist_chunk(int word_bytes, int digits, int n_power);
     int gpuntt_test_keyswitch_hoist_sum_chunk(int word_bytes, int digits, int n_power);
+    int gpuntt_test_bsgs_sum_shape(int word_bytes, int n1, int n_power, int aligned, int* V, unsigned* nt);
 #ifdef __cplusplus
 }
 #endif

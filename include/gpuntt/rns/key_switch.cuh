@@ -187,7 +187,8 @@
 //     word, read modulo q_m; c0 may be nullptr ("no first component", as in rotate_hoisted); c1 is required only if some
 //     baby key is nullptr.  baby_elements / giant_elements: odd once reduced as GPU_Automorphism_NTT reduces them;
 //     duplicates and the identity are allowed.  Keys = T[D_key][2][key_mod_count][N], read through the plan's
-//     key_mod_count / key_limbs.  **A nullptr key means "no key switch for this step" and is accepted only where the
+//     key_mod_count / key_limbs; every key word may hold any value, it is read modulo q_m, as rotate_hoisted reads its
+//     keys.  **A nullptr key means "no key switch for this step" and is accepted only where the
 //     reduced element is 1**: the usual b = 0 and g = 0 steps need no identity key.
 //     weights = a HOST array of n2 * n1 device pointers, row-major [g][b]; weights[g * n1 + b] = T[M][N], the diagonal
 //     pt_{g,b} in NTT form over the FULL base, any word.  **A nullptr entry means the term is ABSENT (weight 0) -- unlike

@@ -69,14 +69,17 @@ class MergeCase:
 
 def oracle_batch(cases, x, inverse=False):
     """NTTCPU::ntt / ::intt of EVERY polynomial of a batch -- polynomial p under cases[p % len(cases)] -- through the
-    oracle's OpenMP batch entry (oracle/ntt_oracle_impl.h: merge_batch) on all host threads; returns a new array."""
+    oracle's OpenMP batch entry (oracle/ntt_oracle_impl.h: merge_batch) on all host threads, though never more than
+    there are polynomials (a team of hundreds for a handful of short polynomials costs more than the transforms);
+    returns a new array."""
     import os
     c0 = cases[0]
     n = c0.n
     size = c0.oprm["root_size"]
     tables = np.concatenate([np.ascontiguousarray(c.oprm["inv" if inverse else "fwd"], dtype=c0.P.T) for c in cases])
     y = np.array(x, dtype=c0.P.T, copy=True, order="C")
-    c0.P.merge_batch(y, c0.logn, c0.poly, inverse, tables, size, [c.q for c in cases], os.cpu_count() or 1)
+    c0.P.merge_batch(y, c0.logn, c0.poly, inverse, tables, size, [c.q for c in cases],
+                     max(1, min(os.cpu_count() or 1, y.size // n)))
     return y
 
 

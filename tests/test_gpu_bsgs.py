@@ -111,6 +111,56 @@ def test_the_limits_run(g, chunk6, bits, n1, n2):
     check_against_the_composition(g, plan, st, np.random.default_rng(n1 + bits), [(n1, n2, 1)])
 
 
+# bsgs_weighted_sum's launch shape by n1: (V words per lane, lanes per workgroup) for u64 and for u32, every base pointer
+# 16-byte aligned, on a ring long enough that N decides nothing.  Written out from host::bsgs_sum_shape with its 32 KiB
+# LDS budget (n1 * lanes * V * word bytes may not pass it; V falls to one word once 64 lanes of n1 groups do): a change of
+# the rule is a conscious edit here
+SUM_SHAPES = {8: ((2, 256), (4, 256)), 9: ((2, 128), (4, 128)), 16: ((2, 128), (4, 128)), 17: ((2, 64), (4, 64)),
+              32: ((2, 64), (4, 64)), 33: ((1, 64), (1, 128)), 64: ((1, 64), (1, 128))}
+SUM_SHAPES_OFF_ALIGNMENT = {17: ((1, 128), (1, 256))}  # a weight one word off 16 bytes: one word per lane
+
+
+def sum_shape_case(g, bits, n1, table, offset):
+    """N = 2^11: the smallest ring at which every shape of the tables has at least two tiles per polynomial (256 lanes
+    x 4 words of u32 = 1024 columns) and the N rule never decides; n2 = 2, count = 1"""
+    n_power, L, K, alpha = 11, 3, 2, 2
+    V, nt = table[n1][0 if bits == 64 else 1]
+    assert g.bsgs_sum_shape(bits, n1, n_power, offset == 0) == (V, nt)
+    assert (1 << n_power) // (V * nt) >= 2 and n1 * nt * V * (bits // 8) <= 32768
+    if n1 == 64:
+        assert n1 * nt * V * (bits // 8) == 32768  # the dynamic LDS at the whole budget
+    st = ring(g, bits, n_power).sub(list(range(L + K)))
+    plan = make_plan(g, st, L, alpha, n_power, bits)
+    check_against_the_composition(g, plan, st, np.random.default_rng(n1 + bits), [(n1, 2, 1)], offset=offset)
+
+
+@pytest.mark.parametrize("bits", [64, 32])
+@pytest.mark.parametrize("n1", sorted(SUM_SHAPES))
+def test_every_launch_shape_of_the_weighted_sum(g, bits, n1):
+    """256, 128 and 64 lanes with a 16-byte group per lane, the 64 lanes the LDS budget forces, one word per lane
+    because n1 > 32, and n1 = 64 with 32 KiB of dynamic LDS: each asserted through the library's own rule, then run with
+    more than one tile per polynomial -- a wrong LDS size or [b][lane] stride only shows on the hardware"""
+    sum_shape_case(g, bits, n1, SUM_SHAPES, 0)
+
+
+@pytest.mark.parametrize("bits", [64, 32])
+def test_the_launch_shape_with_base_pointers_off_alignment(g, bits):
+    """n1 = 17 with a, c0, c1, the keys, the weights and out one word off 16 bytes: one word per lane, and more lanes
+    than the aligned call takes"""
+    sum_shape_case(g, bits, 17, SUM_SHAPES_OFF_ALIGNMENT, 1)
+
+
+def test_the_launch_shape_on_a_ring_shorter_than_a_group(g):
+    """N = 2 is shorter than the four words of a u32 group: one word per lane, 64 lanes (n_power = 1 is run against the
+    composition by test_every_output_word_with_chunks_of_64_slots); u64's group of two still fits"""
+    for n1 in (1, 3, 4, 64):
+        assert g.bsgs_sum_shape(32, n1, 1, True) == (1, 64)
+    assert g.bsgs_sum_shape(64, 3, 1, True) == (2, 64)
+    for bad in ((16, 3, 5), (64, 0, 5), (64, 65, 5), (64, 3, 0), (64, 3, 29)):
+        with pytest.raises(ValueError):
+            g.bsgs_sum_shape(*bad, True)
+
+
 @pytest.mark.parametrize("bits", [64, 32])
 def test_beyond_the_limits_is_refused(g, bits):
     n_power, L, K, alpha = 5, 3, 2, 2

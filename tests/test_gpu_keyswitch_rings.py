@@ -7,8 +7,9 @@ chunk of the library's own LDS rule over many chunks, and the workspace regions 
   1. mod_up / mod_down: every word against the library's host references (pinned to Python integers by
      tests/test_key_switch_host.py) and a fixed column sample against keyswitch_utils' Python integers, which share no
      code with the library.
-  2. apply, decompose + switch_digits, rotate_hoisted, rotate_hoisted_sum, multiply_relinearize and
-     multiply_relinearize_sum: every output word against the composition of public calls that defines each of them.  At
+  2. apply, decompose + switch_digits, rotate_hoisted, rotate_hoisted_sum, multiply_relinearize,
+     multiply_relinearize_sum and (at 2^13 and 2^14) linear_transform_bsgs: every output word against the composition of
+     public calls that defines each of them.  At
      u64 2^16 the library's counter of four-polynomial-tile launches must move exactly for the eligible batches; at u64
      2^14 a plan built with batch_hint = 1 must give the words of the default plan; the launch log of apply must be that
      of the stand-alone NTTPlans plus three kernels, with two sweeps per transform where the README says so.
@@ -25,6 +26,7 @@ import time
 import numpy as np
 import pytest
 
+from bsgs_utils import bsgs_elements, bsgs_operands, bsgs_scratch, composition_bsgs, with_absent
 from hoisted_exact import NARROW, exact_rotate_hoisted, exact_rotate_hoisted_sum, exact_u, finish, host_cases, transform
 from hoisted_sum_utils import composition_sum, make_weights, sum_scratch, with_nones
 from hoisted_utils import (WIDE_WIDTHS, any_words, canonical_key, composition, device_words, elements_for, filled,
@@ -315,6 +317,36 @@ def test_multiply_relinearize_sum_equals_its_composition(g, bits, n_power, kind,
                         lambda p: p.multiply_relinearize_sum(xs, ys, key, out, count, output_ntt, scratch),
                         out, want, (count, output_ntt))
         unmodified(xs + ys + [key], keep)
+
+
+BSGS_CASES = [c for c in RING_CASES if c[1] <= 14]
+
+
+@pytest.mark.parametrize("bits,n_power,kind,shape", BSGS_CASES,
+                         ids=["u%d-2^%d-%s-L%d" % (b, n, k, s[0]) for b, n, k, s in BSGS_CASES])
+def test_linear_transform_bsgs_equals_its_composition(g, bits, n_power, kind, shape):
+    """(n1, n2, count) = (3, 2, 2), one baby step and one giant step without a key, one absent weight per row: step 3 is
+    the only place where the plan's transforms, mod_down and mod_up run over the stacks of all keyed giant steps in one
+    batch, and at 2^14 the u64 inverse transform takes two sweeps.  The exact-integer runs stay on small rings
+    (test_gpu_bsgs_exact.py): the arithmetic does not depend on N, the reference's time does"""
+    s = Setup(g, bits, n_power, kind, shape)
+    n1, n2, count = 3, 2, 2
+    rng = np.random.default_rng(11 * n_power + s.L + bits)
+    a, c0, c1, bkeys, gkeys, weights = bsgs_operands(g, s.plan, s.st, rng, count, n1, n2)
+    be, ge = bsgs_elements(g, n_power, n1, null_at=1), bsgs_elements(g, n_power, n2, null_at=0)
+    bk, gk = [bkeys[0], None, bkeys[2]], [None, gkeys[1]]
+    w = with_absent(weights, 1)
+    assert all(sum(x is None for x in row) == 1 for row in w)
+    flat = [t for row in weights for t in row]
+    keep = [t.clone() for t in (a, c0, c1, *bkeys, *gkeys, *flat)]
+    scratch = bsgs_scratch(s.plan, count, n1, n2)
+    out = filled(bits, 2 * count * s.L * s.n)
+    for output_ntt in (False, True):
+        want = composition_bsgs(g, s.plan, s.st, a, c0, c1, bk, be, gk, ge, w, count, output_ntt)
+        run_checked(s, False, lambda p: p.linear_transform_bsgs(a, c0, c1, bk, be, gk, ge, w, out, count, output_ntt,
+                                                                  scratch),
+                    out, want, ("linear_transform_bsgs", output_ntt))
+    unmodified([a, c0, c1, *bkeys, *gkeys, *flat], keep)
 
 
 @pytest.mark.parametrize("bits,n_power", [(64, 15), (64, 16), (32, 16)])
