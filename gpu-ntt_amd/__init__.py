@@ -136,7 +136,7 @@ ENV_OPTIONS = {"GPUNTT_PATH": ("path", None), "GPUNTT_U32_E32": ("u32_e32", lamb
 
 
 TEST_HOOKS = {"no_scratch", "rns_force_fallback", "u32_e32", "reset_predictions", "two_sweep_big", "baseconv_ksplit",
-              "keyswitch_split", "keyswitch_hoist_chunk", "contig_p4"}
+              "keyswitch_split", "keyswitch_hoist_chunk", "contig_p4", "premul"}
 TEST_PATHS = {"fast-strict", "generic-capped"}
 
 
@@ -160,6 +160,14 @@ def contig_p4_launches():
     """gpuntt_test_contig_p4_launches (csrc/test_hooks.h): launches of the four-polynomial tile of the forward 64-bit
     contiguous pass since the library was loaded."""
     fn = load_library().gpuntt_test_contig_p4_launches
+    fn.restype = ctypes.c_ulonglong
+    return int(fn())
+
+
+def premul_launches():
+    """gpuntt_test_premul_launches (csrc/test_hooks.h): calls since the library was loaded whose strided pass did the
+    last pass's first twiddle product (forward 64-bit ring 2^16, hook premul)."""
+    fn = load_library().gpuntt_test_premul_launches
     fn.restype = ctypes.c_ulonglong
     return int(fn())
 

@@ -30,6 +30,7 @@ namespace gpuntt
         unsigned long long alloc_count();
         void scratch_stats(unsigned long long out[6]);
         unsigned long long contig_p4_launches();
+        unsigned long long premul_launches();
     } // namespace host
 } // namespace gpuntt
 
@@ -523,6 +524,7 @@ extern "C"
         return guarded([&] { host::scratch_stats(out); });
     }
     unsigned long long gpuntt_test_contig_p4_launches(void) { return host::contig_p4_launches(); }
+    unsigned long long gpuntt_test_premul_launches(void) { return host::premul_launches(); }
     int gpuntt_test_keyswitch_hoist_chunk(int word_bytes, int digits, int n_power)
     {
         if ((word_bytes != 4 && word_bytes != 8) || digits < 1 || digits > INNERPROD_MAX_DIGITS || n_power < 1 ||

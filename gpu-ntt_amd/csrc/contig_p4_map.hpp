@@ -87,5 +87,37 @@ namespace gpuntt
                 return (1u << (n - 1 - p)) + (seg >> 2) * ((8u >> p) * NT) + kk * NT + group;
             }
         } // namespace p4
+
+        // The hoisted first twiddle product of the last pass (merge_lazy_kernels.hpp: pass_body<..., PRE>).  The first
+        // stage of the 10-stage last pass -- distance 512 inside a 1024-coefficient segment -- multiplies the elements
+        // with ring bit 9 set by a twiddle that depends on the segment alone.  The strided pass in front of it (K stages
+        // on a 4096-coefficient tile of 2^K rows x 2^(12-K) columns, row = segment) does that product on its way out and
+        // stores T = V w in V's place; the last pass then starts from U' = U + T, V' = 2 U + 4 q - U'.
+        namespace premul
+        {
+            constexpr int BIT = p4::K - 1; // ring bit of the hoisted stage
+            // the hoisted stage's operand V lies at this ring position
+            GPUNTT_P4_HD constexpr bool premultiplied(unsigned ring_pos) { return ((ring_pos >> BIT) & 1u) != 0u; }
+            // prepared-table index the STRIDED pass reads for the element at ring position ring_pos
+            GPUNTT_P4_HD constexpr unsigned tw_index(int n, unsigned ring_pos)
+            {
+                return (1u << (n - 1 - BIT)) + (ring_pos >> (BIT + 1));
+            }
+            // the index the last pass reads today for the same stage of segment seg
+            GPUNTT_P4_HD constexpr unsigned tw_index_contig(int n, unsigned seg) { return p4::tw_uniform_index(n, seg, 0u, BIT, 0u); }
+            // strided pass of k stages, last register round (window at tile bit 12 - k): thread t, register j -> tile element
+            GPUNTT_P4_HD constexpr unsigned strided_elem(int k, unsigned t, unsigned j)
+            {
+                const int w = p4::TLOG - k;
+                return (t & ((1u << w) - 1u)) | (j << w) | ((t >> w) << (w + p4::RB));
+            }
+            // ring position of element e of tile b of a polynomial (kern::LTileMap, STRIDED, p_lo = n - k)
+            GPUNTT_P4_HD constexpr unsigned strided_ring_pos(int n, int k, unsigned b, unsigned e)
+            {
+                const int l = p4::TLOG - k, p_lo = n - k;
+                const unsigned xb = b & ((1u << (p_lo - l)) - 1u), hi = b >> (p_lo - l);
+                return ((hi << (p_lo + k)) | (xb << l)) + (((e >> l) << p_lo) | (e & ((1u << l) - 1u)));
+            }
+        } // namespace premul
     } // namespace kern
 } // namespace gpuntt

@@ -54,6 +54,7 @@ namespace gpuntt
             int in_b = 0; // fast path, forward: range bound (units of q) of the values this pass reads, 0 = not tracked
             int cap = 0;  // fast path, forward 64-bit: hand-off cap this pass is compiled for (host::fwd_pass_cap), 0 = the range limit
             bool p4 = false; // fast path, forward 64-bit 10-stage last pass: tiles of four polynomials x one segment
+            bool premul = false; // fast path, forward 64-bit ring 2^16: the strided pass does the last pass's first twiddle product (both passes carry the flag)
         };
 
         struct Plan

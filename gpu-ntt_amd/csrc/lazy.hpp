@@ -247,6 +247,14 @@ namespace gpuntt
                     asm("v_lshl_add_u64 %0, %1, 1, %2" : "=v"(d) : "v"(x), "s"(k));
                 return d;
             }
+            // x + y: one v_lshl_add_u64 (a butterfly whose product is already there; opaque like shl1_add, so that the
+            // butterfly's three instructions are not re-associated)
+            __device__ __forceinline__ uint64_t add(uint64_t x, uint64_t y) const
+            {
+                uint64_t d;
+                asm("v_lshl_add_u64 %0, %1, 0, %2" : "=v"(d) : "v"(x), "v"(y));
+                return d;
+            }
             // x * w  (mod q), any x < 2^64, result in [0, 4q)
             template <bool UNI = false> __device__ __forceinline__ uint64_t mul(uint64_t x, const Tw64& t) const
             {
@@ -365,6 +373,7 @@ namespace gpuntt
                 const uint64_t a = ZERO ? mad32z<UNI>(x, t.w) : mad32<UNI>(x, t.w, pair_lo(acc));
                 return lo32(mad32<!VQ>(qh, qneg, a));
             }
+            __device__ __forceinline__ uint32_t add(uint32_t x, uint32_t y) const { return x + y; } // (Mod64::add; no 32-bit kernel uses it)
             // 2 x + k (k wave-uniform unless VQ): one v_lshl_add_u32
             __device__ __forceinline__ uint32_t shl1_add(uint32_t x, uint32_t k) const
             {

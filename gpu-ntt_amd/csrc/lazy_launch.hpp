@@ -43,6 +43,14 @@ namespace gpuntt
         unsigned long long contig_p4_launches();
         // the ring whose K = 10 pass takes that tile (other rings with a 10-stage pass: each by its own measurement)
         constexpr int LAZY_P4_N_POWER = 16;
+        // The same calls, 16 q / 31 q ranges: the strided K = 6 pass (memory-bound, VALU time to spare) multiplies the
+        // bit-9 half of the ring by the first-stage twiddles of the VALU-bound last pass, which then starts from the
+        // finished products (kern::pass_body<..., PRE>, contig_p4_map.hpp: premul).  Only together with the
+        // four-polynomial tile; the one-polynomial K = 10 tile has no such variant, so calls that run it keep the plain
+        // strided kernel.  Test hook premul = 0 | 1.
+        bool lazy_premul();
+        void note_premul_launch();                  // test hook: counts the calls that took the pair of kernels (prep.hip)
+        unsigned long long premul_launches();
         // 32-bit ring 2^13: every call takes the 8192-coefficient tile
         constexpr unsigned long long lazy_u32_small_batch() { return 0x7fffffffull; }
         // `inverse` and `polys` (transforms in the call) must be the same wherever one call asks:
@@ -680,6 +688,27 @@ namespace gpuntt
             // range bounds of the values in flight and hand-off caps (forward 64-bit, 16 q / 31 q ranges)
             if (!INV && sizeof(T) == 8 && (base.lim == 31 || base.lim == 0))
                 fwd_plan_bounds(pl, tl, partial, base.lim == 31 ? 31 : 16);
+            // Decided for the whole call before its first launch: does the last pass run on the four-polynomial tile, and
+            // does the strided pass in front of it do that pass's first twiddle product (both kernels switch together).
+            bool p4_last = false, premul = false;
+            if constexpr (sizeof(T) == 8 && !INV)
+            {
+                // plain Merge call or plan (no *_Ordered, no fused product, no 4-step route), whole groups of four
+                // polynomials per modulus; everything else keeps the one-polynomial tile, no tail launch
+                // (a ring of 2^16 never takes the poly-minor block order: a.batch stays 0)
+                const Pass& lp = pl.pass[pl.count - 1];
+                const unsigned long long polys = base.total >> base.n;
+                const unsigned long long mc = base.mods != nullptr ? static_cast<unsigned long long>(base.mod_count) : 1ull;
+                p4_last = lp.contig && lp.k == 10 && fwd_pass_tile64(lp, tl) == 12 && pl.count > 1 && !partial &&
+                          base.n == LAZY_P4_N_POWER && base.poly_shift == base.n && mc >= 1 && polys % (4ull * mc) == 0 &&
+                          (polys << base.n) == base.total && base.poly_order == nullptr && base.mod_order == nullptr &&
+                          base.mul_in == nullptr && lazy_contig_p4();
+                // 16 q / 31 q ranges, the two-pass plan 6 + 10 with the capped hand-off
+                const int limit = base.lim == 31 ? 31 : 16;
+                premul = p4_last && (base.lim == 31 || base.lim == 0) && pl.count == 2 && !pl.pass[0].contig &&
+                         pl.pass[0].k == 6 && pl.pass[0].cap != 0 && pl.pass[0].cap == fwd_handoff_cap10(limit) &&
+                         fwd_inst_bound(lp, 12, false, true, limit) == pl.pass[0].cap && lazy_premul();
+            }
             for (int i = 0; i < pl.count; i++)
             {
                 Pass p = INV ? pl.pass[pl.count - 1 - i] : pl.pass[i];
@@ -708,13 +737,8 @@ namespace gpuntt
                               : 0;
                 if constexpr (sizeof(T) == 8 && !INV)
                 {
-                    // plain Merge call or plan (no *_Ordered, no fused product, no 4-step route), whole groups of four
-                    // polynomials per modulus; everything else keeps the one-polynomial tile, no tail launch
-                    const unsigned long long mc = base.mods != nullptr ? static_cast<unsigned long long>(base.mod_count) : 1ull;
-                    p.p4 = p.contig && p.k == 10 && tlp == 12 && i == pl.count - 1 && pl.count > 1 && !partial &&
-                           base.n == LAZY_P4_N_POWER && base.poly_shift == base.n && mc >= 1 && polys % (4ull * mc) == 0 &&
-                           (polys << base.n) == base.total && base.poly_order == nullptr && base.mod_order == nullptr &&
-                           base.mul_in == nullptr && a.batch == 0 && lazy_contig_p4();
+                    p.p4 = p4_last && i == pl.count - 1 && a.batch == 0;
+                    p.premul = premul; // both passes of the plan
                 }
                 if constexpr (sizeof(T) == 4)
                 {

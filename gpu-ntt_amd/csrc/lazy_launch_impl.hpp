@@ -8,12 +8,14 @@ namespace gpuntt
     namespace host
     {
         template <typename T, int TLOG, bool INV, bool CONTIG, int K, int IN_BOUND, bool LAST, int LIMSEL = 0, bool P4 = false,
-                  int CAP = 0>
+                  int CAP = 0, bool PRE = false>
         inline void launch_lazy_one(const kern::LazyArgsT<T>& a, unsigned grid, hipStream_t stream)
         {
             if constexpr (P4)
                 note_contig_p4_launch();
-            GPUNTT_LAUNCH_FAMILY(LIMSEL, (kern::merge_pass_lazy<T, TLOG, INV, CONTIG, K, IN_BOUND, LAST, LIMSEL, 0, P4, CAP>), dim3(grid),
+            if constexpr (PRE && !CONTIG)
+                note_premul_launch(); // once per call: the strided pass that multiplies
+            GPUNTT_LAUNCH_FAMILY(LIMSEL, (kern::merge_pass_lazy<T, TLOG, INV, CONTIG, K, IN_BOUND, LAST, LIMSEL, 0, P4, CAP, PRE>), dim3(grid),
                                dim3(kern::LTile<TLOG>::NT), 0, stream, a);
             GPUNTT_HIP_CHECK(hipGetLastError());
         }
@@ -22,6 +24,7 @@ namespace gpuntt
         //   single pass       CONTIG K = n <= TLOG              (IN 1, last)   [TLOG 14: K = 13, 14 only]
         //   forward, n > TLOG STRIDED K 1..8 (IN 1 | LIMIT, not last) + CONTIG K (IN LIMIT, last)
         //                     64-bit, 16 q / 31 q ranges, 2^14 / 2^16: STRIDED K 4 / 6 (IN 1, hand-off cap) + CONTIG 10 (IN cap)
+        //                     ... 2^16 on the four-polynomial tile: STRIDED K 6 (cap, PRE) + CONTIG 10 (IN cap, P4, PRE), a pair
         //   inverse, n > TLOG CONTIG K (IN 1, not last) + STRIDED K 1..8 (IN LIMIT / 2, last | not last)
         //   with CONTIG K in 8..12 for 4096-coefficient tiles and K = 14 for 16384-coefficient tiles
         template <typename T, int TLOG, bool INV, int LIMSEL = 0>
@@ -39,8 +42,11 @@ namespace gpuntt
             // forward 64-bit, 16 q / 31 q ranges: two-pass plans of 2^14 / 2^16 are planned across their passes (lazy_launch.hpp)
             constexpr bool CAPPED = sizeof(T) == 8 && !INV && TLOG == 12 && (LIM == 16 || LIM == 31);
             constexpr int CAP10 = CAPPED ? FwdBounds<CAPPED ? LIM : 16>::CAP10 : LIM;
-            if (!CAPPED && p.cap != 0)
+            if (!CAPPED && (p.cap != 0 || p.premul))
                 throw std::invalid_argument("internal: no capped hand-off in this kernel family");
+            // the hoisted first product exists for exactly one pair of kernels; a half-switched call would be wrong words
+            if (p.premul && !(p.contig ? (p.p4 && p.k == 10 && !in_first && last) : (p.cap != 0 && p.k == 6 && in_first && !last)))
+                throw std::invalid_argument("internal: hoisted first product on a pass that has no such kernel");
 #define GPUNTT_ONE(CONTIG_, K_, IN_, LAST_)                                                      \
     return launch_lazy_one<T, TLOG, INV, CONTIG_, K_, IN_, LAST_, LIMSEL>(a, grid, stream)
             if constexpr (sizeof(T) == 8 && TLOG >= 13)
@@ -129,6 +135,14 @@ namespace gpuntt
                                     if constexpr (sizeof(T) == 8)
                                         if (p.p4)
                                         {
+                                            // (Pass::premul: the strided pass in front stored the first stage's products)
+                                            if constexpr (CAPPED)
+                                                if (p.premul)
+                                                {
+                                                    if (fwd_inst_bound(p, TLOG, in_first, last, LIM) != CAP10)
+                                                        throw std::invalid_argument("internal: hoisted first product without the capped hand-off");
+                                                    return launch_lazy_one<T, TLOG, INV, true, 10, CAP10, true, LIMSEL, true, 0, true>(a, grid, stream);
+                                                }
                                             if constexpr (CAPPED)
                                                 if (fwd_inst_bound(p, TLOG, in_first, last, LIM) == CAP10)
                                                     return launch_lazy_one<T, TLOG, INV, true, 10, CAP10, true, LIMSEL, true>(a, grid, stream);
@@ -182,6 +196,14 @@ namespace gpuntt
                     if constexpr (CAPPED)
                         if (p.cap != 0)
                         {
+                            // Pass::premul: the K = 6 pass of the ring 2^16 also multiplies its bit-9 tiles by the next
+                            // pass's first-stage twiddles (run_transform_lazy switches both kernels together)
+                            if (p.premul)
+                            {
+                                if (!last && in_first && p.cap == CAP10 && p.k == 6)
+                                    return launch_lazy_one<T, TLOG, INV, false, 6, 1, false, LIMSEL, false, CAP10, true>(a, grid, stream);
+                                throw std::invalid_argument("internal: unsupported strided pass with the hoisted product");
+                            }
                             if (!last && in_first && p.cap == CAP10)
                                 switch (p.k)
                                 {

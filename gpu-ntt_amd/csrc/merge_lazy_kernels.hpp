@@ -434,7 +434,7 @@ namespace gpuntt
         // and only the operand classes change: q, -q, twiddles and n^-1 in vector registers (lazy::Mod<T, LIM, true>).
         template <typename T, int TLOG, bool INV, bool CONTIG, int K, int IN_BOUND, bool LAST,
                   Fst FST = Fst::none, int LIM = 0, Xp XP = Xp::none, int SKIP = 0, bool VQ = false, int ROWLEN = 0,
-                  bool P4 = false, int CAP = 0>
+                  bool P4 = false, int CAP = 0, bool PRE = false>
         __device__ __forceinline__ void pass_body(const LazyArgsT<T>& a, T* lds, T q_value, T q_bit, T q_mu,
                                                   int mi, unsigned long long fst_poly = 0,
                                                   unsigned fst_tile = 0, long long blk_override = -1,
@@ -454,6 +454,13 @@ namespace gpuntt
             static_assert(!P4 || (sizeof(T) == 8 && TLOG == p4::TLOG && !INV && CONTIG && K == p4::K && IN_BOUND != 1 && LAST &&
                                   FST == Fst::none && XP == Xp::none && SKIP == 0 && !VQ),
                           "four-polynomial tile: the forward 64-bit 10-stage last pass");
+            // PRE: the first twiddle product of the last pass is done by the strided pass in front of it (contig_p4_map.hpp,
+            // premul).  STRIDED (K = 6, capped hand-off): tiles on the bit-9 half of the ring multiply by the next pass's
+            // first-stage twiddle of their row before they store; CONTIG (the four-polynomial tile): the first stage
+            // takes its second operand as the finished product.  The host switches both kernels of a call together.
+            static_assert(!PRE || (sizeof(T) == 8 && !INV && !VQ && EST && FST == Fst::none && XP == Xp::none && TLOG == p4::TLOG &&
+                                   (CONTIG ? P4 : (K == 6 && IN_BOUND == 1 && !LAST && CAP != 0))),
+                          "hoisted first product: the capped forward 64-bit strided pass and the four-polynomial last pass");
             constexpr bool HAS_FST = (FST != Fst::none);
             constexpr int TL = TLOG;
             constexpr int NT = LTile<TLOG>::NT;
@@ -565,9 +572,13 @@ namespace gpuntt
                         constexpr int CNT = 1 << (R - 1 - (p - WL));
                         const TW* ps = tw_mod + (r == 2 ? p4::tw_lane_index(a.n, p4_seg, static_cast<unsigned>(t), p, 0)
                                                         : p4::tw_uniform_index(a.n, p4_seg, r == 1 ? p4_wave : 0u, p, 0));
+                        // (PRE: the first stage's product came with the hand-off -- no twiddle)
                         static_for<CNT>([&](auto k_) {
                             constexpr int kk = decltype(k_)::value;
-                            tws[o4 + kk] = ps[r == 2 ? kk * NT : kk];
+                            if constexpr (PRE && r == 0 && s == 0)
+                                tws[o4 + kk] = TW{0, 0}; // never read
+                            else
+                                tws[o4 + kk] = ps[r == 2 ? kk * NT : kk];
                         });
                         o4 += CNT;
                     });
@@ -957,6 +968,14 @@ namespace gpuntt
                                 unit = (tw.w == 1);
                             // U' = U + T comes out of the product's own multiply-add chain;
                             // V' = U - T + TB q = 2 U + TB q - U'  (mod 2^W; the true value is below LIMIT q)
+                            if constexpr (PRE && CONTIG && r == 0 && s == 0)
+                            {
+                                // v[j1] IS the product T (below 4 q): the strided pass multiplied on its way out
+                                const T nu = m.add(U, v[j1]);
+                                v[j0] = nu;
+                                v[j1] = static_cast<T>(m.shl1_add(U, m.kq(M::TB)) - nu);
+                            }
+                            else
                             {
                                 const T nu = unit ? static_cast<T>(U + v[j1]) : m.template mul_acc<UNI_TW>(v[j1], tw, U);
                                 v[j0] = nu;
@@ -1037,6 +1056,29 @@ namespace gpuntt
                             constexpr int j = decltype(j_)::value;
                             v[j] = lazy::normalize<SCH::d.bout[r][j]>(m, v[j]);
                         });
+                    }
+                    if constexpr (PRE && !CONTIG)
+                    {
+                        // The tile is 2^K rows (= 1024-coefficient segments of the ring) x 2^L contiguous columns, and ring
+                        // bit 9 is the same for all of it.  On the bit-9 half every element is the V operand of the next
+                        // pass's first stage, whose twiddle depends on the row alone: register j of a wave holds row
+                        // (wave << 4) | j, so the 16 Shoup pairs are wave-uniform, 256 contiguous bytes of the table
+                        // (scalar loads; the pass's own twiddles are dead by now).  mul takes any 64-bit value, so no
+                        // range correction is needed in front of it, and T < 4 q is inside every hand-off cap.
+                        static_assert(WL == G::L && WL >= 6 && DIRECT_IO, "rows in registers, columns in lanes");
+                        const unsigned pos0 =
+                            uniform32(static_cast<unsigned>(map.flat(elem_of<WL>(__builtin_amdgcn_readfirstlane(t), 0))) & nmask);
+                        if (premul::premultiplied(pos0)) // block-uniform
+                        {
+                            const TW* ps = tw_mod + premul::tw_index(a.n, pos0);
+                            TW pw[EPT];
+#pragma unroll
+                            for (int j = 0; j < EPT; j++)
+                                pw[j] = ps[j];
+#pragma unroll
+                            for (int j = 0; j < EPT; j++)
+                                v[j] = m.template mul<true>(v[j], pw[j]);
+                        }
                     }
                     if constexpr (XP == Xp::small_inv)
                     {
@@ -1472,8 +1514,9 @@ namespace gpuntt
         // P4 (forward 64-bit, CONTIG, K = 10, 4096-coefficient tile, last pass): the tile is one 1024-coefficient segment
         // of FOUR polynomials that share a modulus (contig_p4_map.hpp) -- block b -> segment b % 2^(n-10) of modulus
         // (b >> (n-10)) % mod_count of polynomial group (b >> (n-10)) / mod_count; the host sends whole groups only
+        // PRE: the hoisted first product of the last pass (pass_body) -- the strided K = 6 pass multiplies, the P4 pass adds
         template <typename T, int TLOG, bool INV, bool CONTIG, int K, int IN_BOUND, bool LAST, int LIM = 0, int SKIP = 0,
-                  bool P4 = false, int CAP = 0>
+                  bool P4 = false, int CAP = 0, bool PRE = false>
         __global__ __launch_bounds__(LTile<TLOG>::NT, (LOcc<TLOG, T>::WAVES)) void merge_pass_lazy(LazyArgsT<T> a)
         {
             using M = lazy::Mod<T, LIM>;
@@ -1529,7 +1572,7 @@ namespace gpuntt
                     qb = md.bit;
                     qm = md.mu;
                 }
-                pass_body<T, TLOG, INV, CONTIG, K, IN_BOUND, LAST, Fst::none, LIM, Xp::none, SK, false, 0, true, CAP>(
+                pass_body<T, TLOG, INV, CONTIG, K, IN_BOUND, LAST, Fst::none, LIM, Xp::none, SK, false, 0, true, CAP, PRE>(
                     a, lds, qv, qb, qm, mi, uniform64((poly0 << a.n) + (static_cast<unsigned long long>(seg) << K)), seg);
                 return;
             }
@@ -1556,7 +1599,7 @@ namespace gpuntt
                 qb = md.bit;
                 qm = md.mu;
             }
-            pass_body<T, TLOG, INV, CONTIG, K, IN_BOUND, LAST, Fst::none, LIM, Xp::none, SK, false, 0, false, CAP>(a, lds, qv, qb,
+            pass_body<T, TLOG, INV, CONTIG, K, IN_BOUND, LAST, Fst::none, LIM, Xp::none, SK, false, 0, false, CAP, (PRE && !P4)>(a, lds, qv, qb,
                                                                                                                    qm, mi, 0, 0, blk);
                 });
         }

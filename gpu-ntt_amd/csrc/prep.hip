@@ -628,7 +628,7 @@ namespace gpuntt
         // The library reads NO environment variable.  PRODUCT options (GPU_NTT_SetOption / gpuntt_set_option, listed in
         // include/gpuntt/ntt_merge/ntt.cuh): path = default | generic | fast, check_4step_tables, rns_predict.  TEST HOOKS
         // (set_test_hook / gpuntt_test_set_hook -- a symbol the public headers do not declare; csrc/test_hooks.h): path =
-        // fast-strict | generic-capped, no_scratch, rns_force_fallback, u32_e32, contig_p4.  Every public entry point opens a
+        // fast-strict | generic-capped, no_scratch, rns_force_fallback, u32_e32, contig_p4, premul.  Every public entry point opens a
         // WorkspaceScope, and the outermost scope of a thread takes ONE snapshot of all of them: a call sees the same values
         // from its first decision to its last launch, whatever another thread sets meanwhile.
         void baseconv_set_ksplit(int v); // base_conversion.hip
@@ -647,6 +647,7 @@ namespace gpuntt
                                             // full-tile contiguous pass of larger rings)
                 int two_sweep_big = 0;      // test hook (experiment): 64-bit rings 2^23 / 2^24 forward in two sweeps on 16384-coefficient tiles
                 int contig_p4 = 1;          // test hook: forward 64-bit ring 2^16, 10-stage last pass on tiles of four polynomials x one segment
+                int premul = 1;             // test hook: the same calls, 16 q / 31 q ranges: the strided pass does the last pass's first twiddle product
             };
             std::mutex g_opt_mutex;
             std::atomic<int> g_reset_predictions{0};   // test hook reset_predictions: consumed by the next rns_guess
@@ -714,6 +715,8 @@ namespace gpuntt
                     g_opt.two_sweep_big = iv;
                 else if (test_hooks && k == "contig_p4" && bit)
                     g_opt.contig_p4 = iv;
+                else if (test_hooks && k == "premul" && bit)
+                    g_opt.premul = iv;
                 else if (test_hooks && k == "baseconv_ksplit" && is_num && lv >= 0 && lv <= 16)
                     // base_conversion.hip: workgroups per column tile, 0 = its own choice.  NOT part of the per-call
                     // snapshot below: a measurement knob of tools/bench_baseconv.py, read once per launch from a
@@ -743,6 +746,7 @@ namespace gpuntt
         int forced_path() { return options().path; }
         bool lazy_two_sweep_big() { return options().two_sweep_big != 0; }
         bool lazy_contig_p4() { return options().contig_p4 != 0; }
+        bool lazy_premul() { return options().premul != 0; }
         static bool rns_predict_enabled() { return options().rns_predict != 0; }
         static bool rns_force_fallback() { return options().rns_force_fallback != 0; }
         bool check_4step_tables() { return options().check_4step != 0; }
@@ -780,7 +784,10 @@ namespace gpuntt
         namespace
         {
             std::atomic<unsigned long long> g_contig_p4_launches{0};
+            std::atomic<unsigned long long> g_premul_launches{0}; // calls whose strided pass did the last pass's first product
         }
+        void note_premul_launch() { g_premul_launches.fetch_add(1, std::memory_order_relaxed); }
+        unsigned long long premul_launches() { return g_premul_launches.load(std::memory_order_relaxed); }
         void note_contig_p4_launch() { g_contig_p4_launches.fetch_add(1, std::memory_order_relaxed); }
         unsigned long long contig_p4_launches() { return g_contig_p4_launches.load(std::memory_order_relaxed); }
         void launch_log_start()

@@ -10,6 +10,9 @@
  *                                bit 16: the full-tile contiguous pass of larger rings)
  *       contig_p4 = 0 | 1        forward 64-bit Merge transforms of the ring 2^16: the 10-stage last pass on tiles of four
  *                                polynomials x one 1024-coefficient segment (1), or on the one-polynomial tile (0)
+ *       premul = 0 | 1           the same calls, 16 q / 31 q ranges, when they take the four-polynomial tile: the strided pass
+ *                                multiplies the bit-9 half of the ring by the last pass's first-stage twiddles and the last pass
+ *                                starts from the products (1), or both passes as before (0)
  *       two_sweep_big = 0 | 1    experiment: 64-bit rings 2^23 / 2^24 forward in two sweeps on 16384-coefficient tiles
  *       baseconv_ksplit = 0..16  base conversion: workgroups per column tile that share its outputs (0: the library's choice)
  *       keyswitch_split = 0..64  key switching: workgroups per column tile that share the (digit, block) pairs of the ModUp
@@ -31,6 +34,8 @@
  *   gpuntt_test_contig_p4_launches()    launches of the four-polynomial tile of the forward 64-bit contiguous pass since the
  *                                       library was loaded (hook contig_p4): the launch log shows them under the name of the
  *                                       one-polynomial tile
+ *   gpuntt_test_premul_launches()       calls since the library was loaded whose strided pass did the last pass's first twiddle
+ *                                       product (hook premul); the launch log shows both kernels under their usual names
  *   gpuntt_test_keyswitch_hoist_chunk(word_bytes, digits, n_power)  host only: log2 of the chunk inner_product_galois takes
  *                                       for this word size, D and ring under the hook's current value; -1: bad argument
  *   gpuntt_test_keyswitch_hoist_sum_chunk(word_bytes, digits, n_power)  the same for the destination chunk of
@@ -53,6 +58,7 @@ extern "C"
     int gpuntt_test_launch_log_take(char* buf, int capacity);
     int gpuntt_test_scratch_stats(unsigned long long out[6]);
     unsigned long long gpuntt_test_contig_p4_launches(void);
+    unsigned long long gpuntt_test_premul_launches(void);
     unsigned long long gpuntt_test_alloc_count(void);
     int gpuntt_test_keyswitch_hoist_chunk(int word_bytes, int digits, int n_power);
     int gpuntt_test_keyswitch_hoist_sum_chunk(int word_bytes, int digits, int n_power);
