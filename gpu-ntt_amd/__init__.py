@@ -125,7 +125,10 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "keyswitch_plan_rotate_hoisted_sum_rescale", "keyswitch_reference_mod_down_rescale",
               "keyswitch_reference_rescale",
               "keyswitch_plan_bsgs_scratch_bytes", "keyswitch_plan_linear_transform_bsgs",
-              "keyswitch_plan_linear_transform_bsgs_rescale")
+              "keyswitch_plan_linear_transform_bsgs_rescale",
+              "bfv_plan_workspace_bytes", "bfv_plan_scratch_bytes", "bfv_plan_create", "bfv_plan_extend",
+              "bfv_plan_scale_round", "bfv_plan_multiply", "bfv_plan_owns_workspace", "bfv_plan_destroy",
+              "bfv_constants", "bfv_reference_extend", "bfv_reference_scale_round")
     for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option", "gpuntt_galois_element_u32",
                                 "gpuntt_automorphism_index_map"]
 
@@ -1466,6 +1469,172 @@ class KeySwitchPlan:
     def close(self):
         if self._h:
             getattr(load_library(), "gpuntt_keyswitch_plan_destroy_u%d" % self.bits)(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bfv_constants(q_moduli, b_moduli, plain_modulus, n_power, bits=64):
+    """Host (no GPU): the constants a BfvMultiplyPlan of these bases and this t uploads (BfvConstants<T>), as a dict of
+    numpy arrays -- up_* the seven arrays of baseconv_constants({q} -> {b}), down_* those of {b} -> {q}, t_mod[M],
+    t_mod_shoup[M], t_qhat_inv[L] ((t qhat_i^-1) mod q_i) and t_qhat_inv_shoup[L].  Raises ValueError where the plan's
+    constructor would ("Auxiliary base too small!" among them)."""
+    qs, qarr = _keyswitch_moduli(q_moduli, bits)
+    bs, barr = _keyswitch_moduli(b_moduli, bits)
+    L, K, dt = len(qs), len(bs), np_dtype(bits)
+    side = lambda a, b: (("qhat_inv", (a,)), ("qhat_inv_shoup", (a,)), ("matrix", (a, b)), ("q_mod_p", (b,)),
+                         ("q_inv_mod_p", (b,)), ("recip", (a,)), ("bit_length", (a,)))
+    shapes = tuple(("up_" + n, s) for n, s in side(L, K)) + tuple(("down_" + n, s) for n, s in side(K, L)) + \
+        (("t_mod", (L + K,)), ("t_mod_shoup", (L + K,)), ("t_qhat_inv", (L,)), ("t_qhat_inv_shoup", (L,)))
+    out = {name: np.zeros(tuple(max(1, d) for d in shape), dtype=dt) for name, shape in shapes}
+    ptrs = (ctypes.c_void_p * len(shapes))(*[out[name].ctypes.data for name, _ in shapes])
+    fn = getattr(load_library(), "gpuntt_bfv_constants_u%d" % bits)
+    _check(fn(qarr, L, barr, K, _ct(bits)(int(plain_modulus) & ((1 << bits) - 1)), int(n_power), ptrs))
+    return out
+
+
+def bfv_reference_extend(q_moduli, b_moduli, x, full, n_power, stacks, bits=64):
+    """Host (no GPU): BfvMultiplyPlan<T>::reference_extend on numpy arrays of the plan's word type -- x holds stacks x L
+    x N words, full stacks x M x N (written and returned) -- after the argument checks of extend (ValueError).  None for
+    an array is the C NULL."""
+    qs, qarr = _keyswitch_moduli(q_moduli, bits)
+    bs, barr = _keyswitch_moduli(b_moduli, bits)
+    L, M = len(qs), len(qs) + len(bs)
+    ok = 1 <= int(n_power) <= 28 and int(stacks) >= 0
+    cols = (int(stacks) << int(n_power)) if ok else None
+    px = _keyswitch_host_array(x, bits, cols * L if ok else None, "in (stacks x L x N)")
+    pf = _keyswitch_host_array(full, bits, cols * M if ok else None, "full (stacks x M x N)")
+    fn = getattr(load_library(), "gpuntt_bfv_reference_extend_u%d" % bits)
+    _check(fn(qarr, len(qs), barr, len(bs), px, pf, int(n_power), int(stacks)))
+    return full
+
+
+def bfv_reference_scale_round(q_moduli, b_moduli, plain_modulus, full, out, n_power, stacks, bits=64):
+    """Host (no GPU): BfvMultiplyPlan<T>::reference_scale_round -- full holds stacks x M x N words, out stacks x L x N
+    (written and returned)."""
+    qs, qarr = _keyswitch_moduli(q_moduli, bits)
+    bs, barr = _keyswitch_moduli(b_moduli, bits)
+    L, M = len(qs), len(qs) + len(bs)
+    ok = 1 <= int(n_power) <= 28 and int(stacks) >= 0
+    cols = (int(stacks) << int(n_power)) if ok else None
+    pf = _keyswitch_host_array(full, bits, cols * M if ok else None, "full (stacks x M x N)")
+    po = _keyswitch_host_array(out, bits, cols * L if ok else None, "out (stacks x L x N)")
+    fn = getattr(load_library(), "gpuntt_bfv_reference_scale_round_u%d" % bits)
+    _check(fn(qarr, len(qs), barr, len(bs), _ct(bits)(int(plain_modulus) & ((1 << bits) - 1)), pf, po, int(n_power),
+              int(stacks)))
+    return out
+
+
+class BfvMultiplyPlan:
+    """Extension BfvMultiplyPlan<T> (include/gpuntt/rns/bfv_multiply.cuh): the scale-invariant product
+    round(t (x (x) y) / Q) for the q-base `q_moduli` (L), the auxiliary base `b_moduli` (K, B >= 2 t N Q or ValueError
+    "Auxiliary base too small!") and the plaintext modulus `plain_modulus` on a ring of 2^n_power, M = L + K <= 64.
+    forward_table / inverse_table: device tensors as for GPU_NTT / GPU_INTT over the full base (slot i at i << n_power),
+    mod_inverse the M host n^-1 values; all three None: a plan without transforms (extend / scale_round only).
+    `workspace`: an optional uint8 device tensor of workspace_bytes() bytes owned by the caller.  `scratch` of multiply:
+    a device tensor of at least plan.scratch_bytes(count) bytes, 256-byte aligned, owned by the caller; nothing is
+    allocated by any call."""
+
+    def __init__(self, q_moduli, b_moduli, plain_modulus, n_power, forward_table=None, inverse_table=None,
+                 mod_inverse=None, reduction_poly=X_N_plus, batch_hint=1024, bits=64, stream=None, workspace=None):
+        lib = load_library()
+        qs, qarr = _keyswitch_moduli(q_moduli, bits)
+        bs, barr = _keyswitch_moduli(b_moduli, bits)
+        _require_gpu(workspace, forward_table, inverse_table)
+        self.bits, self.q_count, self.b_count, self.mod_count = bits, len(qs), len(bs), len(qs) + len(bs)
+        self.n_power, self.plain_modulus = int(n_power), int(plain_modulus)
+        for t in (forward_table, inverse_table):
+            if t is not None and (t.element_size() * 8 != bits or t.numel() < self.mod_count << self.n_power):
+                raise ValueError("a table holds M x N %d-bit words" % bits)
+        ninv = None
+        if mod_inverse is not None:
+            vals = [int(v) for v in mod_inverse]
+            if len(vals) != self.mod_count:
+                raise ValueError("mod_inverse holds one n^-1 per modulus of the full base")
+            ninv = (_ct(bits) * max(1, len(vals)))(*vals)
+        if workspace is not None:
+            need = self.workspace_bytes(len(qs), len(bs), n_power, bits)  # raises for counts out of range
+            if workspace.numel() * workspace.element_size() < need:
+                raise ValueError("workspace holds fewer than workspace_bytes() bytes")
+        self._keep = (workspace, forward_table, inverse_table)
+        self._h = ctypes.c_void_p()
+        fn = getattr(lib, "gpuntt_bfv_plan_create_u%d" % bits)
+        _check(fn(ctypes.byref(self._h), qarr, len(qs), barr, len(bs),
+                  _ct(bits)(self.plain_modulus & ((1 << bits) - 1)), int(n_power), _ptr(forward_table),
+                  _ptr(inverse_table), ninv, int(reduction_poly), int(batch_hint), _ptr(workspace), _stream(stream)))
+
+    @staticmethod
+    def workspace_bytes(q_count, b_count, n_power, bits=64):
+        out = ctypes.c_uint64()
+        _check(getattr(load_library(), "gpuntt_bfv_plan_workspace_bytes_u%d" % bits)(
+            int(q_count), int(b_count), int(n_power), ctypes.byref(out)))
+        return int(out.value)
+
+    def scratch_bytes(self, count):
+        """BfvMultiplyPlan<T>::scratch_bytes: the caller-owned scratch of multiply, in bytes"""
+        out = ctypes.c_uint64()
+        _check(getattr(load_library(), "gpuntt_bfv_plan_scratch_bytes_u%d" % self.bits)(
+            self.q_count, self.b_count, self.n_power, int(count), ctypes.byref(out)))
+        return int(out.value)
+
+    @property
+    def owns_workspace(self):
+        """False: the plan lives in the caller's workspace and has allocated no device memory"""
+        return bool(getattr(load_library(), "gpuntt_bfv_plan_owns_workspace_u%d" % self.bits)(self._h))
+
+    def _check_buffers(self, sized):
+        """the library cannot see tensor sizes or types: sized = (tensor, words needed, name) ...; None is the C NULL,
+        which the library refuses"""
+        _require_gpu(*[t for t, _, _ in sized])
+        for t, words, name in sized:
+            if t is None:
+                continue
+            if t.element_size() * 8 != self.bits or t.dtype.is_floating_point:
+                raise ValueError("a %d-bit BfvMultiplyPlan takes %d-bit integer tensors" % (self.bits, self.bits))
+            if words > 0 and t.numel() < words:
+                raise ValueError("%s needs %d words; got %d" % (name, words, t.numel()))
+
+    def _cols(self, count):
+        return (int(count) << self.n_power) if int(count) > 0 else 0
+
+    def extend(self, device_in, device_full, stacks, stream=None):
+        """device_in T[stacks][L][N] -> device_full T[stacks][M][N]; one kernel launch"""
+        cols = self._cols(stacks)
+        self._check_buffers(((device_in, cols * self.q_count, "in (stacks x L x N)"),
+                             (device_full, cols * self.mod_count, "full (stacks x M x N)")))
+        fn = getattr(load_library(), "gpuntt_bfv_plan_extend_u%d" % self.bits)
+        _check(fn(self._h, _ptr(device_in), _ptr(device_full), int(stacks), _stream(stream)))
+
+    def scale_round(self, device_full, device_out, stacks, stream=None):
+        """device_full T[stacks][M][N] -> device_out T[stacks][L][N]; one kernel launch"""
+        cols = self._cols(stacks)
+        self._check_buffers(((device_full, cols * self.mod_count, "full (stacks x M x N)"),
+                             (device_out, cols * self.q_count, "out (stacks x L x N)")))
+        fn = getattr(load_library(), "gpuntt_bfv_plan_scale_round_u%d" % self.bits)
+        _check(fn(self._h, _ptr(device_full), _ptr(device_out), int(stacks), _stream(stream)))
+
+    def multiply(self, x, y, out, count, input_ntt=False, output_ntt=False, scratch=None, stream=None):
+        """x, y T[2][count][L][N] (y may be x) -> out T[3][count][L][N]; out may be x or y itself.  scratch: at least
+        scratch_bytes(count) bytes, 256-byte aligned"""
+        cols = self._cols(count)
+        self._check_buffers(((x, cols * self.q_count * 2, "x (2 x count x L x N)"),
+                             (y, cols * self.q_count * 2, "y (2 x count x L x N)"),
+                             (out, cols * self.q_count * 3, "out (3 x count x L x N)")))
+        _require_gpu(scratch)
+        if scratch is not None and int(count) > 0 and \
+                scratch.numel() * scratch.element_size() < self.scratch_bytes(count):
+            raise ValueError("scratch holds fewer than scratch_bytes(count) bytes")
+        fn = getattr(load_library(), "gpuntt_bfv_plan_multiply_u%d" % self.bits)
+        _check(fn(self._h, _ptr(x), _ptr(y), _ptr(out), int(count), int(bool(input_ntt)), int(bool(output_ntt)),
+                  _ptr(scratch), _stream(stream)))
+
+    def close(self):
+        if self._h:
+            getattr(load_library(), "gpuntt_bfv_plan_destroy_u%d" % self.bits)(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

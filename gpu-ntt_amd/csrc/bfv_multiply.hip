@@ -1,0 +1,829 @@
+// bfv_multiply.hip -- scale-invariant ciphertext multiplication (extension, include/gpuntt/rns/bfv_multiply.cuh): the
+// three kernels of BfvMultiplyPlan<T> and the plan itself.
+//
+//   bfv_extend:       full[s][m] = in[s][m] mod q_m for m < L, and the centred conversion {q} -> {b} of the stack's L words
+//                     into limbs L .. M-1 -- KeySwitchPlan::mod_up at a single digit, as a sibling of its kernel
+//   bfv_tensor:       d0 = x0 y0, d1 = x0 y1 + x1 y0, d2 = x1 y1 modulo every modulus of the full base
+//   bfv_scale_round:  out = round(t X / Q) in the base q from the M words of X: t X, the centred conversion {q} -> {b} with
+//                     its division by Q, and the centred conversion {b} -> {q} of the result, in ONE pass over the stack
+//
+// The two conversion kernels keep the conventions of base_conversion.hip: one lane owns one coefficient
+// column; the y_i are parked in LDS at [i][lane], so a lane only reads back what it wrote itself -- no barrier, and
+// consecutive lanes hit consecutive banks; the outputs are produced BC_KB at a time, BC_CHUNK terms per 2W-bit partial sum
+// into a three-word accumulator; the accumulator leaves through three exact Shoup products against the plan's own
+// constants (never Modulus::mu); every constant is indexed by wave-uniform values only and is read through the constant
+// address space, hence by scalar loads.  bfv_block_mac and bfv_fold below are that arithmetic, written once for the three
+// conversions of this file.
+//
+// bfv_scale_round.  The lane reads the M words of its column once.  First conversion: y_i = full_i * [t qhat_i^-1 mod q_i]
+// -- t folded into the Shoup constant: the same canonical residue as ((t mod q_i) full_i mod q_i) * qhat_i^-1 mod q_i -- goes
+// to LDS row i, v is formed as base_convert forms it, and the K outputs come BC_KB at a time: conv_j, then c_j = full_{L+j}
+// scaled by t mod b_j, the difference as a congruent word, the product with Q^-1 mod b_j: r_j, step 2 of the definition.
+// Each r_j becomes y'_j = r_j * [Bhat_j^-1 mod b_j] on the spot and goes to LDS row L + j, with its z' term summed
+// for v'.  Second conversion: the L outputs of {b} -> {q} are accumulated over rows L .. M-1 and stored.  The K words r_j
+// never reach memory.  LDS: M x 128 words per workgroup, 64 KiB at M = 64 with u64 -- mod_down's ceiling.
+// A column tile is never split over workgroups: the second conversion needs every y'_j, so a split would recompute the
+// whole first conversion in each part (whether small calls would gain from it is not measured).
+//
+// bfv_tensor is tensor_top's arithmetic (relinearize.hip) for three terms: IpAcc::mac and IpFold of
+// inner_product_internal.hpp, the ONE copy of that arithmetic -- d1 is one exact two-term sum, folded once.  It may write
+// d over x: every word is written by the lane that read it, after its loads.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <memory>
+#include <stdexcept>
+#include <utility>
+#include <vector>
+
+#include "bfv_multiply_internal.hpp"
+#include "gpuntt/ntt_merge/ntt.cuh"
+#include "gpuntt/rns/bfv_multiply.cuh"
+#include "launch.hpp"
+#include "relinearize_internal.hpp"
+
+namespace gpuntt
+{
+    namespace kern
+    {
+        extern __shared__ __align__(16) unsigned char bfv_smem[]; // M (bfv_extend: L) rows of BC_NT words
+
+        // z = (y R) >> (b - 1) < 2^W, the term of base_conversion.cuh's v; a power of two q = 2^(b - 1) has R = 2^W,
+        // stored as 0
+        template <typename T> __device__ __forceinline__ T bfv_z(T y, T recip, T shift)
+        {
+            using W2 = typename RnsWide<T>::type;
+            constexpr int W = static_cast<int>(8 * sizeof(T));
+            const int sh = static_cast<int>(shift);
+            return (recip != 0) ? static_cast<T>((static_cast<W2>(y) * recip) >> sh) : (y << (W - sh));
+        }
+
+        // BC_KB outputs of one conversion: acc + carry 2^2W = v * negq[b] + sum_{i < n} ys[i * BC_NT] * row[i * stride + b].
+        // BC_CHUNK terms at a time go into a plain 2W-bit sum (no carry to watch); the sums go into the three-word
+        // accumulator, one carry test per chunk and output.  row and negq point at the block's first column; both are
+        // padded with zeros to a multiple of BC_KB
+        template <typename T>
+        __device__ __forceinline__ void bfv_block_mac(const T* ys, typename BcConsts<T>::CP row, int n, int stride, T v,
+                                                      typename BcConsts<T>::CP negq,
+                                                      typename RnsWide<T>::type (&acc)[BC_KB], T (&carry)[BC_KB])
+        {
+            using W2 = typename RnsWide<T>::type;
+#pragma unroll
+            for (int b = 0; b < BC_KB; b++)
+            {
+                acc[b] = static_cast<W2>(v) * negq[b];
+                carry[b] = 0;
+            }
+            for (int i0 = 0; i0 < n; i0 += BC_CHUNK)
+            {
+                const int i1 = ip_min(i0 + BC_CHUNK, n);
+                W2 part[BC_KB];
+#pragma unroll
+                for (int b = 0; b < BC_KB; b++)
+                    part[b] = 0;
+#pragma unroll 2
+                for (int i = i0; i < i1; i++)
+                {
+                    const T y = ys[i * BC_NT];
+#pragma unroll
+                    for (int b = 0; b < BC_KB; b++)
+                        part[b] += static_cast<W2>(y) * row[b];
+                    row += stride;
+                }
+#pragma unroll
+                for (int b = 0; b < BC_KB; b++)
+                {
+                    acc[b] += part[b];
+                    carry[b] += (acc[b] < part[b]) ? 1u : 0u;
+                }
+            }
+        }
+
+        // (h [2^W]_p + c [2^2W]_p + l) mod p for the accumulator c 2^2W + h 2^W + l: three exact Shoup products, each
+        // canonical, their sum below 3 p < 2^W; k: the image whose output base holds p at index j
+        template <typename T>
+        __device__ __forceinline__ T bfv_fold(typename RnsWide<T>::type acc, T carry, const BcConsts<T>& k, int j, T p)
+        {
+            constexpr int W = static_cast<int>(8 * sizeof(T));
+            T r = rns_shoup<T>(static_cast<T>(acc >> W), k.t1[j], k.t1p[j], p);
+            r += rns_shoup<T>(carry, k.t2[j], k.t2p[j], p);
+            r += rns_shoup<T>(static_cast<T>(acc), T(1), k.onep[j], p);
+            r = r >= p ? r - p : r;
+            return r >= p ? r - p : r;
+        }
+
+        // in: T[stacks][L][N], full: T[stacks][M][N], M = L + K; total = stacks N columns.  grid: x = column tile
+        template <typename T>
+        __global__ __launch_bounds__(BC_NT) void bfv_extend(const T* __restrict__ in, T* __restrict__ full,
+                                                            const T* __restrict__ consts, BcOffsets up, BfvOffsets ex,
+                                                            int L, int K, int KP, int n_power, unsigned long long total)
+        {
+            const BcConsts<T> k(consts, up);
+            const typename BcConsts<T>::CP onepq = (typename BcConsts<T>::CP) (consts) + ex.onepq;
+            using W2 = typename RnsWide<T>::type;
+            constexpr int W = static_cast<int>(8 * sizeof(T));
+            T* ys = reinterpret_cast<T*>(bfv_smem) + threadIdx.x;
+
+            const unsigned long long t = static_cast<unsigned long long>(blockIdx.x) * BC_NT + threadIdx.x;
+            if (t >= total)
+                return; // (no barrier below)
+            const unsigned long long e = t >> n_power, col = t & ((1ull << n_power) - 1ull);
+            const T* src = in + ((e * static_cast<unsigned>(L)) << n_power) + col;
+            T* dst = full + ((e * static_cast<unsigned>(L + K)) << n_power) + col;
+
+            W2 zsum = static_cast<W2>(1) << (W - 1);
+#pragma unroll 4
+            for (int i = 0; i < L; i++)
+            {
+                const T q = k.q[i];
+                const T x = src[static_cast<unsigned long long>(i) << n_power];
+                const T y = rns_shoup<T>(x, k.w[i], k.wp[i], q);
+                ys[i * BC_NT] = y;
+                // the canonical word: a conditional subtraction does not reduce a 64-bit word modulo a 20-bit q
+                dst[static_cast<unsigned long long>(i) << n_power] = rns_shoup<T>(x, T(1), onepq[i], q);
+                zsum += bfv_z<T>(y, k.recip[i], k.shift[i]);
+            }
+            const T v = static_cast<T>(zsum >> W);
+
+            dst += static_cast<unsigned long long>(L) << n_power;
+            for (int j0 = 0; j0 < K; j0 += BC_KB)
+            {
+                W2 acc[BC_KB];
+                T carry[BC_KB];
+                bfv_block_mac<T>(ys, k.matrix + j0, L, KP, v, k.negq + j0, acc, carry);
+#pragma unroll
+                for (int b = 0; b < BC_KB; b++)
+                {
+                    const int j = j0 + b;
+                    if (j < K)
+                        dst[static_cast<unsigned long long>(j) << n_power] = bfv_fold<T>(acc[b], carry[b], k, j, k.p[j]);
+                }
+            }
+        }
+
+        // full: T[stacks][M][N], out: T[stacks][L][N]; total = stacks N columns.  grid: x = column tile.  up: the image of
+        // {q} -> {b} (KP = K padded), down: the image of {b} -> {q} (LP = L padded)
+        template <typename T>
+        __global__ __launch_bounds__(BC_NT) void bfv_scale_round(const T* __restrict__ full, T* __restrict__ out,
+                                                                 const T* __restrict__ consts, BcOffsets up,
+                                                                 BcOffsets down, BfvOffsets ex, int L, int K, int KP,
+                                                                 int LP, int n_power, unsigned long long total)
+        {
+            using CP = typename BcConsts<T>::CP;
+            using W2 = typename RnsWide<T>::type;
+            constexpr int W = static_cast<int>(8 * sizeof(T));
+            const BcConsts<T> ku(consts, up), kd(consts, down);
+            const CP wt = (CP) (consts) + ex.wt, wtp = (CP) (consts) + ex.wtp;
+            const CP tb = (CP) (consts) + ex.tb, tbp = (CP) (consts) + ex.tbp;
+            T* ys = reinterpret_cast<T*>(bfv_smem) + threadIdx.x; // y_i at row i < L, y'_j at row L + j
+            T* y2s = ys + L * BC_NT;
+
+            const unsigned long long t = static_cast<unsigned long long>(blockIdx.x) * BC_NT + threadIdx.x;
+            if (t >= total)
+                return; // (no barrier below)
+            const unsigned long long e = t >> n_power, col = t & ((1ull << n_power) - 1ull);
+            const T* src = full + ((e * static_cast<unsigned>(L + K)) << n_power) + col;
+
+            // {q} -> {b} of t X: y_i with t folded into the constant
+            W2 zsum = static_cast<W2>(1) << (W - 1);
+#pragma unroll 4
+            for (int i = 0; i < L; i++)
+            {
+                const T y = rns_shoup<T>(src[static_cast<unsigned long long>(i) << n_power], wt[i], wtp[i], ku.q[i]);
+                ys[i * BC_NT] = y;
+                zsum += bfv_z<T>(y, ku.recip[i], ku.shift[i]);
+            }
+            const T v = static_cast<T>(zsum >> W);
+
+            src += static_cast<unsigned long long>(L) << n_power;
+            W2 zsum2 = static_cast<W2>(1) << (W - 1);
+            for (int j0 = 0; j0 < K; j0 += BC_KB)
+            {
+                W2 acc[BC_KB];
+                T carry[BC_KB];
+                bfv_block_mac<T>(ys, ku.matrix + j0, L, KP, v, ku.negq + j0, acc, carry);
+#pragma unroll
+                for (int b = 0; b < BC_KB; b++)
+                {
+                    const int j = j0 + b;
+                    if (j < K)
+                    {
+                        const T p = ku.p[j];
+                        const T conv = bfv_fold<T>(acc[b], carry[b], ku, j, p);
+                        // c_j = (t mod b_j) full_{L+j} mod b_j; c - conv as a word that is congruent to it
+                        const T c = rns_shoup<T>(src[static_cast<unsigned long long>(j) << n_power], tb[j], tbp[j], p);
+                        const T d = c >= conv ? c - conv : c + (p - conv);
+                        const T r = rns_shoup<T>(d, ku.qinv[j], ku.qinvp[j], p); // step 2's word
+                        const T y2 = rns_shoup<T>(r, kd.w[j], kd.wp[j], p);
+                        y2s[j * BC_NT] = y2;
+                        zsum2 += bfv_z<T>(y2, kd.recip[j], kd.shift[j]);
+                    }
+                }
+            }
+            const T v2 = static_cast<T>(zsum2 >> W);
+
+            // {b} -> {q} of r
+            T* dst = out + ((e * static_cast<unsigned>(L)) << n_power) + col;
+            for (int i0 = 0; i0 < L; i0 += BC_KB)
+            {
+                W2 acc[BC_KB];
+                T carry[BC_KB];
+                bfv_block_mac<T>(y2s, kd.matrix + i0, K, LP, v2, kd.negq + i0, acc, carry);
+#pragma unroll
+                for (int b = 0; b < BC_KB; b++)
+                {
+                    const int i = i0 + b;
+                    if (i < L)
+                        dst[static_cast<unsigned long long>(i) << n_power] = bfv_fold<T>(acc[b], carry[b], kd, i, kd.p[i]);
+                }
+            }
+        }
+
+        // grid: x = r * tiles + tile, y = m < M; xe, ye: T[2][count][M][N], d: T[3][count][M][N]; fold: the six arrays of M
+        // words IpFold reads.  d may be xe's memory; ye may be xe (a squaring: two loads instead of four)
+        template <typename T, int V>
+        __global__ __launch_bounds__(IP_NT) void bfv_tensor(const T* xe, const T* ye, T* d, const T* __restrict__ fold_consts,
+                                                            int count, int M, int n_power, unsigned tiles)
+        {
+            using Vec = IpVec<T, V>;
+            const unsigned tile = blockIdx.x % tiles, r = blockIdx.x / tiles;
+            const unsigned m = blockIdx.y;
+            const unsigned long long col = (static_cast<unsigned long long>(tile) * blockDim.x + threadIdx.x) * V;
+            if (col >= (1ull << n_power))
+                return;
+            const unsigned long long at =
+                ((static_cast<unsigned long long>(r) * static_cast<unsigned>(M) + m) << n_power) + col;
+            const unsigned long long comp = (static_cast<unsigned long long>(count) * static_cast<unsigned>(M)) << n_power;
+            const Vec x0 = *reinterpret_cast<const Vec*>(xe + at);
+            const Vec x1 = *reinterpret_cast<const Vec*>(xe + comp + at);
+            Vec y0 = x0, y1 = x1;
+            if (ye != xe) // uniform over the grid
+            {
+                y0 = *reinterpret_cast<const Vec*>(ye + at);
+                y1 = *reinterpret_cast<const Vec*>(ye + comp + at);
+            }
+            const IpFold<T> fold(fold_consts, M, m);
+            Vec o0, o1, o2;
+#pragma unroll
+            for (int v = 0; v < V; v++)
+            {
+                IpAcc<T> s0{T(0), T(0), 0u}, s1{T(0), T(0), 0u}, s2{T(0), T(0), 0u};
+                s0.mac(x0.x[v], y0.x[v]);
+                s1.mac(x0.x[v], y1.x[v]);
+                s1.mac(x1.x[v], y0.x[v]);
+                s2.mac(x1.x[v], y1.x[v]);
+                o0.x[v] = fold.reduce(fold.sum(s0)); // each sum is below 3 q < 2^W
+                o1.x[v] = fold.reduce(fold.sum(s1));
+                o2.x[v] = fold.reduce(fold.sum(s2));
+            }
+            *reinterpret_cast<Vec*>(d + at) = o0;
+            *reinterpret_cast<Vec*>(d + comp + at) = o1;
+            *reinterpret_cast<Vec*>(d + 2 * comp + at) = o2;
+        }
+    } // namespace kern
+
+    namespace
+    {
+        using U128 = unsigned __int128;
+
+        size_t bfv_align(size_t bytes) { return (bytes + 255) / 256 * 256; }
+        int bfv_padded(int K) { return (K + kern::BC_KB - 1) / kern::BC_KB * kern::BC_KB; }
+
+        void bfv_check_counts(int L, int K)
+        {
+            if (L < 1 || L > BASECONV_MAX_COUNT)
+                throw std::invalid_argument("Invalid q_count!");
+            if (K < 1 || K > BASECONV_MAX_COUNT || L + K > BASECONV_MAX_COUNT)
+                throw std::invalid_argument("Invalid b_count!");
+        }
+        void bfv_check_n_power(int n_power)
+        {
+            if (n_power <= 0 || n_power >= 29)
+                throw std::invalid_argument("Invalid n_power range!");
+        }
+        bool bfv_overlap(const void* a, std::uint64_t a_bytes, const void* b, std::uint64_t b_bytes)
+        {
+            const auto al = reinterpret_cast<uintptr_t>(a), bl = reinterpret_cast<uintptr_t>(b);
+            return al < bl + b_bytes && bl < al + a_bytes;
+        }
+
+        // a product of words in exact integers, little-endian 64-bit limbs: the size check B >= 2 t N Q
+        using Big = std::vector<std::uint64_t>;
+        void big_mul(Big& a, std::uint64_t f)
+        {
+            std::uint64_t carry = 0;
+            for (std::uint64_t& w : a)
+            {
+                const U128 p = static_cast<U128>(w) * f + carry;
+                w = static_cast<std::uint64_t>(p);
+                carry = static_cast<std::uint64_t>(p >> 64);
+            }
+            if (carry != 0)
+                a.push_back(carry);
+        }
+        bool big_less(const Big& a, const Big& b) // no leading zero limbs on either side
+        {
+            if (a.size() != b.size())
+                return a.size() < b.size();
+            for (size_t i = a.size(); i-- > 0;)
+                if (a[i] != b[i])
+                    return a[i] < b[i];
+            return false;
+        }
+
+        // everything the host derives for one (q-base, auxiliary base, t), in exact integers
+        struct BfvHost
+        {
+            int L = 0, K = 0, M = 0;
+            std::vector<std::uint64_t> mod;                    // [M] the full base
+            host::BcHostConsts up, down;                       // {q} -> {b}, {b} -> {q}
+            std::vector<std::uint64_t> tm, tmp;                // [M] t mod m_m and its Shoup companion
+            std::vector<std::uint64_t> wt, wtp;                // [L] (t qhat_i^-1) mod q_i and its companion
+            std::vector<std::uint64_t> t1, t1p, t2, t2p, onep; // [M] the fold constants of bfv_tensor
+        };
+
+        // n_power < 0: without the size check (the host references are defined for any bases)
+        template <typename T>
+        BfvHost bfv_derive(const Modulus<T>* qm, int L, const Modulus<T>* bm, int K, std::uint64_t t, int n_power)
+        {
+            constexpr int W = static_cast<int>(8 * sizeof(T));
+            bfv_check_counts(L, K);
+            if (qm == nullptr || bm == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            if (t < 2)
+                throw std::invalid_argument("Invalid plaintext modulus!");
+            BfvHost h;
+            h.L = L, h.K = K, h.M = L + K;
+            // {q} -> {b} checks the q pairwise and every q against every b, {b} -> {q} the b pairwise; both check every
+            // modulus ("Invalid modulus!")
+            h.up = host::bc_derive<T>(qm, L, bm, K);
+            h.down = host::bc_derive<T>(bm, K, qm, L);
+            h.mod = h.up.q;
+            h.mod.insert(h.mod.end(), h.up.p.begin(), h.up.p.end());
+            if (n_power >= 0)
+            {
+                bfv_check_n_power(n_power);
+                Big B{1}, need{2};
+                for (int j = 0; j < K; j++)
+                    big_mul(B, h.mod[L + j]);
+                big_mul(need, t);
+                big_mul(need, std::uint64_t(1) << n_power);
+                for (int i = 0; i < L; i++)
+                    big_mul(need, h.mod[i]);
+                if (big_less(B, need))
+                    throw std::invalid_argument("Auxiliary base too small!");
+            }
+            for (int m = 0; m < h.M; m++)
+            {
+                const std::uint64_t q = h.mod[m];
+                auto shoup = [&](std::uint64_t v) { return static_cast<std::uint64_t>((static_cast<U128>(v) << W) / q); };
+                const std::uint64_t tq = t % q;
+                const std::uint64_t t1 = static_cast<std::uint64_t>((static_cast<U128>(1) << W) % q);
+                const std::uint64_t t2 = static_cast<std::uint64_t>(static_cast<U128>(t1) * t1 % q);
+                h.tm.push_back(tq), h.tmp.push_back(shoup(tq));
+                h.t1.push_back(t1), h.t1p.push_back(shoup(t1)), h.t2.push_back(t2), h.t2p.push_back(shoup(t2));
+                h.onep.push_back(shoup(1));
+                if (m < L)
+                {
+                    const std::uint64_t w = static_cast<std::uint64_t>(static_cast<U128>(tq) * h.up.w[m] % q);
+                    h.wt.push_back(w), h.wtp.push_back(shoup(w));
+                }
+            }
+            return h;
+        }
+
+        struct BfvLayout // the workspace, in bytes; the constants are the run [up, ntt_q_i)
+        {
+            size_t up, down, extra, fold, ntt_q_i, ntt_q_f, ntt_full_f, ntt_full_i, total;
+        };
+        template <typename T> BfvLayout bfv_layout(int L, int K, int n_power)
+        {
+            bfv_check_counts(L, K);
+            bfv_check_n_power(n_power);
+            const int M = L + K;
+            BfvLayout w{};
+            size_t at = 0;
+            auto take = [&](size_t bytes) {
+                const size_t first = at;
+                at += bfv_align(bytes);
+                return first;
+            };
+            w.up = take(host::bc_image_words(L, K) * sizeof(T));
+            w.down = take(host::bc_image_words(K, L) * sizeof(T));
+            w.extra = take((3 * static_cast<size_t>(L) + 2 * static_cast<size_t>(bfv_padded(K))) * sizeof(T));
+            w.fold = take(6 * static_cast<size_t>(M) * sizeof(T));
+            w.ntt_q_i = take(NTTPlan<T>::workspace_bytes(n_power, L));
+            w.ntt_q_f = take(NTTPlan<T>::workspace_bytes(n_power, L));
+            w.ntt_full_f = take(NTTPlan<T>::workspace_bytes(n_power, M));
+            w.ntt_full_i = take(NTTPlan<T>::workspace_bytes(n_power, M));
+            w.total = at;
+            return w;
+        }
+
+        // BcOffsets of an image that starts `words` words into the run of constants
+        kern::BcOffsets bfv_shift(kern::BcOffsets o, size_t words)
+        {
+            const unsigned s = static_cast<unsigned>(words);
+            return kern::BcOffsets{o.q + s,     o.w + s,  o.wp + s,  o.recip + s, o.shift + s,
+                                   o.matrix + s, o.p + s,  o.negq + s, o.qinv + s,  o.qinvp + s,
+                                   o.t1 + s,    o.t1p + s, o.t2 + s,  o.t2p + s,   o.onep + s};
+        }
+
+        struct BfvScratch // the caller's scratch, in bytes
+        {
+            size_t e, coeff, total; // e: T[4][count][M][N]; coeff: T[2][count][L][N]
+        };
+        template <typename T> BfvScratch bfv_scratch(int L, int M, int n_power, int count)
+        {
+            if (count < 0)
+                throw std::invalid_argument("Invalid count!");
+            const size_t poly = (static_cast<size_t>(count) << n_power) * sizeof(T);
+            BfvScratch s{};
+            s.e = 0;
+            s.coeff = s.e + bfv_align(poly * M * 4);
+            s.total = s.coeff + bfv_align(poly * L * 2);
+            return s;
+        }
+
+        // the argument checks of extend / scale_round (device or host arrays alike): `narrow` limbs per stack at a,
+        // `wide` at b
+        template <typename T>
+        void bfv_check_stacks(int narrow, int wide, const T* a, const T* b, int n_power, int stacks, const char* what)
+        {
+            bfv_check_n_power(n_power);
+            if (stacks < 0)
+                throw std::invalid_argument("Invalid stacks!");
+            if (a == nullptr || b == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            const std::uint64_t cols = static_cast<std::uint64_t>(stacks) << n_power;
+            if (stacks > 0 && bfv_overlap(a, cols * narrow * sizeof(T), b, cols * wide * sizeof(T)))
+                throw std::invalid_argument(what);
+        }
+        unsigned bfv_tiles(int n_power, std::uint64_t stacks) // of bfv_extend and bfv_scale_round
+        {
+            const unsigned long long total = stacks << n_power;
+            const unsigned long long tiles = (total + kern::BC_NT - 1) / kern::BC_NT;
+            if (tiles * kern::BC_NT > 0xFFFFFFFFull) // HIP caps a launch at 2^32 - 1 work-items per dimension
+                throw std::invalid_argument("Invalid stacks!");
+            return static_cast<unsigned>(tiles);
+        }
+
+        template <typename T, int V>
+        void bfv_tensor_as(const T* xe, const T* ye, T* d, const T* fold, int count, int M, int n_power, bool enqueue,
+                           hipStream_t stream)
+        {
+            const host::RelinGrid g = host::relin_grid(n_power, V, static_cast<unsigned long long>(count));
+            if (!enqueue)
+                return;
+            GPUNTT_LAUNCH((kern::bfv_tensor<T, V>), dim3(g.blocks, static_cast<unsigned>(M)), dim3(g.nt), 0, stream, xe,
+                          ye, d, fold, count, M, n_power, g.tiles);
+            GPUNTT_HIP_CHECK(hipGetLastError());
+        }
+        // enqueue false: only the checks.  Throws std::invalid_argument beyond the grid limits
+        template <typename T>
+        void bfv_tensor_launch(const T* xe, const T* ye, T* d, const T* fold, int count, int M, int n_power, bool enqueue,
+                               hipStream_t stream)
+        {
+            constexpr int VW = 16 / sizeof(T);
+            if (host::relin_wide<T>(n_power, {xe, ye, d}))
+                bfv_tensor_as<T, VW>(xe, ye, d, fold, count, M, n_power, enqueue, stream);
+            else
+                bfv_tensor_as<T, 1>(xe, ye, d, fold, count, M, n_power, enqueue, stream);
+        }
+    } // namespace
+
+    template <typename T> struct BfvMultiplyPlan<T>::Impl
+    {
+        int L = 0, K = 0, M = 0, n = 0;
+        T t = 0;
+        char* ws = nullptr;
+        bool owns = false;
+        BfvLayout lay{};
+        kern::BcOffsets up_off{}, down_off{};
+        kern::BfvOffsets ex_off{};
+        std::unique_ptr<NTTPlan<T>> ntt_q_i, ntt_q_f, ntt_full_f, ntt_full_i;
+
+        const T* consts() const { return reinterpret_cast<const T*>(ws + lay.up); }
+        const T* fold() const { return reinterpret_cast<const T*>(ws + lay.fold); }
+
+        void extend(const T* in, T* full, int stacks, hipStream_t stream) const
+        {
+            bfv_check_stacks<T>(L, M, in, full, n, stacks, "extend input and output overlap!");
+            if (stacks == 0)
+                return;
+            const unsigned tiles = bfv_tiles(n, static_cast<std::uint64_t>(stacks));
+            GPUNTT_LAUNCH((kern::bfv_extend<T>), dim3(tiles), dim3(kern::BC_NT),
+                          static_cast<size_t>(L) * kern::BC_NT * sizeof(T), stream, in, full, consts(), up_off, ex_off, L,
+                          K, bfv_padded(K), n, static_cast<unsigned long long>(stacks) << n);
+            GPUNTT_HIP_CHECK(hipGetLastError());
+        }
+
+        void scale_round(const T* full, T* out, int stacks, hipStream_t stream) const
+        {
+            bfv_check_stacks<T>(L, M, out, full, n, stacks, "scale_round input and output overlap!");
+            if (stacks == 0)
+                return;
+            const unsigned tiles = bfv_tiles(n, static_cast<std::uint64_t>(stacks));
+            GPUNTT_LAUNCH((kern::bfv_scale_round<T>), dim3(tiles), dim3(kern::BC_NT),
+                          static_cast<size_t>(M) * kern::BC_NT * sizeof(T), stream, full, out, consts(), up_off, down_off,
+                          ex_off, L, K, bfv_padded(K), bfv_padded(L), n, static_cast<unsigned long long>(stacks) << n);
+            GPUNTT_HIP_CHECK(hipGetLastError());
+        }
+
+        void multiply(const T* x, const T* y, T* out, int count, bool input_ntt, bool output_ntt, void* scratch,
+                      hipStream_t stream) const
+        {
+            if (!ntt_full_f)
+                throw std::invalid_argument("The plan was built without transform tables!");
+            const BfvScratch s = bfv_scratch<T>(L, M, n, count); // checks count
+            if (x == nullptr || y == nullptr || out == nullptr || scratch == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
+                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            if (count == 0)
+                return;
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T), out_bytes = cols * L * 3 * sizeof(T);
+            for (const T* op : {x, y})
+            {
+                if (bfv_overlap(scratch, s.total, op, ct_bytes))
+                    throw std::invalid_argument("out or the scratch overlaps an operand!");
+                // out may be exactly x or exactly y: the last read of both (bfv_extend, or the INTT before it) precedes
+                // bfv_scale_round's first write on the stream.  Any other overlap is refused
+                if (bfv_overlap(out, out_bytes, op, ct_bytes) && op != out)
+                    throw std::invalid_argument("out or the scratch overlaps an operand!");
+            }
+            if (bfv_overlap(out, out_bytes, scratch, s.total))
+                throw std::invalid_argument("The scratch overlaps out!");
+            // every limit before the first launch: the batches of the transforms are ints, the grids as the launches check
+            if (4ull * static_cast<unsigned>(count) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
+                throw std::invalid_argument("Invalid count!");
+            (void) bfv_tiles(n, 3ull * static_cast<unsigned>(count));
+            const bool square = x == y;
+            T* e = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.e);
+            T* coeff = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.coeff);
+            T* xe = e;
+            T* ye = square ? e : e + cols * M * 2;
+            bfv_tensor_launch<T>(xe, ye, e, fold(), count, M, n, false, stream);
+
+            auto bring = [&](const T* op, T* full) { // steps 1 and 2 for one operand
+                if (input_ntt)
+                    ntt_q_i->execute(op, coeff, 2 * count * L, stream);
+                extend(input_ntt ? coeff : op, full, 2 * count, stream);
+            };
+            bring(x, xe);
+            if (!square) // a squaring: y is x, extended once
+                bring(y, ye);
+            ntt_full_f->execute(e, e, (square ? 2 : 4) * count * M, stream);
+            bfv_tensor_launch<T>(xe, ye, e, fold(), count, M, n, true, stream);
+            ntt_full_i->execute(e, e, 3 * count * M, stream);
+            scale_round(e, out, 3 * count, stream);
+            if (output_ntt)
+                ntt_q_f->execute(out, out, 3 * count * L, stream);
+        }
+    };
+
+    template <typename T> size_t BfvMultiplyPlan<T>::workspace_bytes(int q_count, int b_count, int n_power)
+    {
+        return bfv_layout<T>(q_count, b_count, n_power).total;
+    }
+
+    template <typename T> size_t BfvMultiplyPlan<T>::scratch_bytes(int q_count, int b_count, int n_power, int count)
+    {
+        bfv_check_counts(q_count, b_count);
+        bfv_check_n_power(n_power);
+        return bfv_scratch<T>(q_count, q_count + b_count, n_power, count).total;
+    }
+
+    template <typename T>
+    BfvMultiplyPlan<T>::BfvMultiplyPlan(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* b_moduli_host,
+                                        int b_count, T plain_modulus, int n_power, const Root<T>* forward_table_device,
+                                        const Root<T>* inverse_table_device, const Ninverse<T>* mod_inverse_host,
+                                        ReductionPolynomial reduction_poly, int batch_hint, stream_t stream,
+                                        void* workspace_device)
+        : p_(nullptr)
+    {
+        bfv_check_counts(q_count, b_count);
+        bfv_check_n_power(n_power);
+        const BfvHost h = bfv_derive<T>(q_moduli_host, q_count, b_moduli_host, b_count, plain_modulus, n_power);
+        const BfvLayout lay = bfv_layout<T>(h.L, h.K, n_power);
+        const bool transforms = forward_table_device != nullptr || inverse_table_device != nullptr;
+        if (transforms && (forward_table_device == nullptr || inverse_table_device == nullptr || mod_inverse_host == nullptr))
+            throw std::invalid_argument("null pointer argument");
+        std::unique_ptr<Impl> p(new Impl);
+        p->L = h.L, p->K = h.K, p->M = h.M, p->n = n_power, p->t = plain_modulus, p->lay = lay;
+
+        // the run of constants: the two images, the plan's own arrays, the fold image -- one host buffer, one copy
+        const int L = h.L, KP = bfv_padded(h.K);
+        std::vector<T> run((lay.ntt_q_i - lay.up) / sizeof(T), T(0));
+        kern::BcOffsets up_rel{}, down_rel{};
+        const std::vector<T> up_img = host::bc_image<T>(h.up, up_rel), down_img = host::bc_image<T>(h.down, down_rel);
+        const size_t o_down = (lay.down - lay.up) / sizeof(T), o_extra = (lay.extra - lay.up) / sizeof(T);
+        const size_t o_fold = (lay.fold - lay.up) / sizeof(T);
+        std::copy(up_img.begin(), up_img.end(), run.begin());
+        std::copy(down_img.begin(), down_img.end(), run.begin() + o_down);
+        p->up_off = up_rel, p->down_off = bfv_shift(down_rel, o_down);
+        auto u = [](size_t v) { return static_cast<unsigned>(v); };
+        p->ex_off = kern::BfvOffsets{u(o_extra), u(o_extra + L), u(o_extra + 2 * L), u(o_extra + 3 * L),
+                                     u(o_extra + 3 * L + KP)};
+        for (int i = 0; i < L; i++)
+        {
+            run[p->ex_off.wt + i] = static_cast<T>(h.wt[i]), run[p->ex_off.wtp + i] = static_cast<T>(h.wtp[i]);
+            run[p->ex_off.onepq + i] = static_cast<T>(h.onep[i]);
+        }
+        for (int j = 0; j < h.K; j++)
+        {
+            run[p->ex_off.tb + j] = static_cast<T>(h.tm[L + j]), run[p->ex_off.tbp + j] = static_cast<T>(h.tmp[L + j]);
+        }
+        {
+            size_t at = o_fold;
+            for (const std::vector<std::uint64_t>* v : {&h.mod, &h.t1, &h.t1p, &h.t2, &h.t2p, &h.onep})
+                for (std::uint64_t w : *v)
+                    run[at++] = static_cast<T>(w);
+        }
+        std::vector<Modulus<T>> full(q_moduli_host, q_moduli_host + h.L);
+        full.insert(full.end(), b_moduli_host, b_moduli_host + h.K);
+
+        void* raw = workspace_device;
+        if (raw == nullptr)
+        {
+            GPUNTT_HIP_CHECK(hipMalloc(&raw, lay.total));
+            p->owns = true;
+        }
+        p->ws = static_cast<char*>(raw);
+        try
+        {
+            GPUNTT_HIP_CHECK(hipMemcpyAsync(p->ws + lay.up, run.data(), run.size() * sizeof(T), hipMemcpyHostToDevice,
+                                            stream));
+            GPUNTT_HIP_CHECK(hipStreamSynchronize(stream)); // `run` dies with this scope
+            if (transforms)
+            {
+                p->ntt_q_i.reset(new NTTPlan<T>(inverse_table_device, full.data(), h.L, n_power, reduction_poly, INVERSE,
+                                                mod_inverse_host, batch_hint, stream, p->ws + lay.ntt_q_i));
+                p->ntt_q_f.reset(new NTTPlan<T>(forward_table_device, full.data(), h.L, n_power, reduction_poly, FORWARD,
+                                                nullptr, batch_hint, stream, p->ws + lay.ntt_q_f));
+                p->ntt_full_f.reset(new NTTPlan<T>(forward_table_device, full.data(), h.M, n_power, reduction_poly,
+                                                   FORWARD, nullptr, batch_hint, stream, p->ws + lay.ntt_full_f));
+                p->ntt_full_i.reset(new NTTPlan<T>(inverse_table_device, full.data(), h.M, n_power, reduction_poly,
+                                                   INVERSE, mod_inverse_host, batch_hint, stream,
+                                                   p->ws + lay.ntt_full_i));
+            }
+        }
+        catch (...)
+        {
+            p->ntt_q_i.reset(), p->ntt_q_f.reset(), p->ntt_full_f.reset(), p->ntt_full_i.reset();
+            if (p->owns)
+                (void) hipFree(p->ws);
+            throw;
+        }
+        p_ = p.release();
+    }
+
+    template <typename T> BfvMultiplyPlan<T>::~BfvMultiplyPlan()
+    {
+        if (p_ == nullptr)
+            return;
+        p_->ntt_q_i.reset(), p_->ntt_q_f.reset(), p_->ntt_full_f.reset(), p_->ntt_full_i.reset();
+        if (p_->owns)
+            (void) hipFree(p_->ws);
+        delete p_;
+    }
+
+    template <typename T> void BfvMultiplyPlan<T>::extend(const T* device_in, T* device_full, int stacks, stream_t stream) const
+    {
+        p_->extend(device_in, device_full, stacks, stream);
+    }
+    template <typename T>
+    void BfvMultiplyPlan<T>::scale_round(const T* device_full, T* device_out, int stacks, stream_t stream) const
+    {
+        p_->scale_round(device_full, device_out, stacks, stream);
+    }
+    template <typename T>
+    void BfvMultiplyPlan<T>::multiply(const T* device_x, const T* device_y, T* device_out, int count, bool input_ntt,
+                                      bool output_ntt, void* scratch_device, stream_t stream) const
+    {
+        p_->multiply(device_x, device_y, device_out, count, input_ntt, output_ntt, scratch_device, stream);
+    }
+
+    template <typename T> int BfvMultiplyPlan<T>::q_count() const { return p_->L; }
+    template <typename T> int BfvMultiplyPlan<T>::b_count() const { return p_->K; }
+    template <typename T> int BfvMultiplyPlan<T>::n_power() const { return p_->n; }
+    template <typename T> T BfvMultiplyPlan<T>::plain_modulus() const { return p_->t; }
+    template <typename T> bool BfvMultiplyPlan<T>::has_transforms() const { return static_cast<bool>(p_->ntt_full_f); }
+    template <typename T> bool BfvMultiplyPlan<T>::owns_workspace() const { return p_->owns; }
+    template <typename T> size_t BfvMultiplyPlan<T>::scratch_bytes(int count) const
+    {
+        return bfv_scratch<T>(p_->L, p_->M, p_->n, count).total;
+    }
+
+    template <typename T>
+    void BfvMultiplyPlan<T>::constants(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* b_moduli_host,
+                                       int b_count, T plain_modulus, int n_power, const BfvConstants<T>& out)
+    {
+        bfv_check_n_power(n_power);
+        const BfvHost h = bfv_derive<T>(q_moduli_host, q_count, b_moduli_host, b_count, plain_modulus, n_power);
+        for (const T* ptr : {out.t_mod, out.t_mod_shoup, out.t_qhat_inv, out.t_qhat_inv_shoup})
+            if (ptr == nullptr)
+                throw std::invalid_argument("null pointer argument");
+        auto copy = [](const std::vector<std::uint64_t>& v, T* dst) {
+            if (dst == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            for (size_t i = 0; i < v.size(); i++)
+                dst[i] = static_cast<T>(v[i]);
+        };
+        for (const auto& side : {std::pair<const host::BcHostConsts*, const BaseConvConstants<T>*>{&h.up, &out.up},
+                                 {&h.down, &out.down}})
+        {
+            const host::BcHostConsts& c = *side.first;
+            const BaseConvConstants<T>& o = *side.second;
+            copy(c.w, o.qhat_inv), copy(c.wp, o.qhat_inv_shoup), copy(c.matrix, o.matrix), copy(c.qmod, o.q_mod_p);
+            copy(c.qinv, o.q_inv_mod_p), copy(c.recip, o.recip), copy(c.blen, o.bit_length);
+        }
+        copy(h.tm, out.t_mod), copy(h.tmp, out.t_mod_shoup), copy(h.wt, out.t_qhat_inv), copy(h.wtp, out.t_qhat_inv_shoup);
+    }
+
+    namespace
+    {
+        // base_conversion.cuh's centred formulas for one column: x[i] (canonical) of the input base of `c` -> conv[j],
+        // every step reduced with %
+        template <typename T>
+        void bfv_ref_convert(const host::BcHostConsts& c, const std::uint64_t* x, std::uint64_t* conv)
+        {
+            constexpr int W = static_cast<int>(8 * sizeof(T));
+            std::uint64_t y[BASECONV_MAX_COUNT];
+            U128 zsum = static_cast<U128>(1) << (W - 1);
+            for (int i = 0; i < c.L; i++)
+            {
+                y[i] = static_cast<std::uint64_t>(static_cast<U128>(x[i] % c.q[i]) * c.w[i] % c.q[i]);
+                const int sh = static_cast<int>(c.blen[i]) - 1;
+                const U128 z = c.recip[i] != 0 ? (static_cast<U128>(y[i]) * c.recip[i]) >> sh
+                                               : static_cast<U128>(y[i]) << (W - sh);
+                zsum += static_cast<T>(z);
+            }
+            const std::uint64_t v = static_cast<std::uint64_t>(static_cast<T>(zsum >> W));
+            for (int j = 0; j < c.K; j++)
+            {
+                const U128 p = c.p[j];
+                U128 s = static_cast<U128>(v % c.p[j]) * c.negq[j] % p;
+                for (int i = 0; i < c.L; i++)
+                    s = (s + static_cast<U128>(y[i] % c.p[j]) * c.matrix[static_cast<size_t>(i) * c.K + j]) % p;
+                conv[j] = static_cast<std::uint64_t>(s);
+            }
+        }
+    } // namespace
+
+    template <typename T>
+    void BfvMultiplyPlan<T>::reference_extend(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* b_moduli_host,
+                                              int b_count, const T* in_host, T* full_host, int n_power, int stacks)
+    {
+        const BfvHost h = bfv_derive<T>(q_moduli_host, q_count, b_moduli_host, b_count, 2, -1);
+        bfv_check_stacks<T>(h.L, h.M, in_host, full_host, n_power, stacks, "extend input and output overlap!");
+        const size_t n = size_t(1) << n_power;
+        std::uint64_t x[BASECONV_MAX_COUNT], conv[BASECONV_MAX_COUNT];
+        for (int s = 0; s < stacks; s++)
+            for (size_t j = 0; j < n; j++)
+            {
+                const T* src = in_host + static_cast<size_t>(s) * h.L * n + j;
+                T* dst = full_host + static_cast<size_t>(s) * h.M * n + j;
+                for (int i = 0; i < h.L; i++)
+                {
+                    x[i] = src[i * n] % h.mod[i];
+                    dst[i * n] = static_cast<T>(x[i]);
+                }
+                bfv_ref_convert<T>(h.up, x, conv);
+                for (int k = 0; k < h.K; k++)
+                    dst[(h.L + k) * n] = static_cast<T>(conv[k]);
+            }
+    }
+
+    template <typename T>
+    void BfvMultiplyPlan<T>::reference_scale_round(const Modulus<T>* q_moduli_host, int q_count,
+                                                   const Modulus<T>* b_moduli_host, int b_count, T plain_modulus,
+                                                   const T* full_host, T* out_host, int n_power, int stacks)
+    {
+        const BfvHost h = bfv_derive<T>(q_moduli_host, q_count, b_moduli_host, b_count, plain_modulus, -1);
+        bfv_check_stacks<T>(h.L, h.M, out_host, full_host, n_power, stacks, "scale_round input and output overlap!");
+        const size_t n = size_t(1) << n_power;
+        std::uint64_t s[BASECONV_MAX_COUNT], conv[BASECONV_MAX_COUNT], r[BASECONV_MAX_COUNT];
+        for (int st = 0; st < stacks; st++)
+            for (size_t j = 0; j < n; j++)
+            {
+                const T* src = full_host + static_cast<size_t>(st) * h.M * n + j;
+                for (int m = 0; m < h.M; m++) // step 1
+                    s[m] = static_cast<std::uint64_t>(static_cast<U128>(h.tm[m]) * (src[m * n] % h.mod[m]) % h.mod[m]);
+                bfv_ref_convert<T>(h.up, s, conv); // step 2
+                for (int k = 0; k < h.K; k++)
+                {
+                    const std::uint64_t b = h.mod[h.L + k], c = s[h.L + k];
+                    const std::uint64_t diff = c >= conv[k] ? c - conv[k] : c + (b - conv[k]);
+                    r[k] = static_cast<std::uint64_t>(static_cast<U128>(diff) * h.up.qinv[k] % b);
+                }
+                bfv_ref_convert<T>(h.down, r, conv); // step 3
+                for (int i = 0; i < h.L; i++)
+                    out_host[(static_cast<size_t>(st) * h.L + i) * n + j] = static_cast<T>(conv[i]);
+            }
+    }
+
+    template class BfvMultiplyPlan<Data32>;
+    template class BfvMultiplyPlan<Data64>;
+} // namespace gpuntt

@@ -11,6 +11,7 @@
 #include "gpuntt/ntt_merge/galois.cuh"
 #include "gpuntt/ntt_merge/ntt.cuh"
 #include "gpuntt/rns/base_conversion.cuh"
+#include "gpuntt/rns/bfv_multiply.cuh"
 #include "gpuntt/rns/inner_product.cuh"
 #include "gpuntt/rns/key_switch.cuh"
 #include "gpuntt_c.h"
@@ -1218,6 +1219,105 @@ extern "C"
             const auto qs = to_mods<T>(q_moduli_host, q_count, "Invalid q_count!");                \
             KeySwitchPlan<T>::reference_rescale(qs.data(), q_count, rescale_limbs, x_host, out_host, n_power,     \
                                                 stacks);                                          \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_plan_workspace_bytes_##S(int q_count, int b_count, int n_power, uint64_t* bytes_host)          \
+    {                                                                                             \
+        GPUNTT_NEED(bytes_host)                                                                   \
+        return guarded([&] { *bytes_host = BfvMultiplyPlan<T>::workspace_bytes(q_count, b_count, n_power); });    \
+    }                                                                                             \
+    int gpuntt_bfv_plan_scratch_bytes_##S(int q_count, int b_count, int n_power, int count, uint64_t* bytes_host) \
+    {                                                                                             \
+        GPUNTT_NEED(bytes_host)                                                                   \
+        return guarded(                                                                           \
+            [&] { *bytes_host = BfvMultiplyPlan<T>::scratch_bytes(q_count, b_count, n_power, count); });          \
+    }                                                                                             \
+    int gpuntt_bfv_plan_create_##S(gpuntt_bfv_plan** plan_host, const CM* q_moduli_host, int q_count,             \
+                                   const CM* b_moduli_host, int b_count, T plain_modulus, int n_power,            \
+                                   const T* forward_table, const T* inverse_table, const T* mod_inverse_host,     \
+                                   int reduction_poly, int batch_hint, void* workspace_device, void* stream)      \
+    {                                                                                             \
+        GPUNTT_NEED(plan_host)                                                                    \
+        return guarded([&] {                                                                      \
+            const auto qs = to_mods<T>(q_moduli_host, q_count, "Invalid q_count!");                \
+            const auto bs = to_mods<T>(b_moduli_host, b_count, "Invalid b_count!");                \
+            if (reduction_poly != GPUNTT_X_N_PLUS && reduction_poly != GPUNTT_X_N_MINUS)          \
+                throw std::invalid_argument("Invalid reduction_poly!");                           \
+            *plan_host = reinterpret_cast<gpuntt_bfv_plan*>(new BfvMultiplyPlan<T>(               \
+                qs.data(), q_count, bs.data(), b_count, plain_modulus, n_power, forward_table, inverse_table,     \
+                mod_inverse_host, static_cast<ReductionPolynomial>(reduction_poly), batch_hint,   \
+                static_cast<hipStream_t>(stream), workspace_device));                             \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_plan_extend_##S(const gpuntt_bfv_plan* plan, const T* in, T* full, int stacks, void* stream)   \
+    {                                                                                             \
+        GPUNTT_NEED(plan, in, full)                                                               \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const BfvMultiplyPlan<T>*>(plan)->extend(in, full, stacks,            \
+                                                                      static_cast<hipStream_t>(stream));          \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_plan_scale_round_##S(const gpuntt_bfv_plan* plan, const T* full, T* out, int stacks,           \
+                                        void* stream)                                             \
+    {                                                                                             \
+        GPUNTT_NEED(plan, full, out)                                                              \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const BfvMultiplyPlan<T>*>(plan)->scale_round(full, out, stacks,      \
+                                                                           static_cast<hipStream_t>(stream));     \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_plan_multiply_##S(const gpuntt_bfv_plan* plan, const T* x, const T* y, T* out, int count,      \
+                                     int input_ntt, int output_ntt, void* scratch, void* stream)  \
+    {                                                                                             \
+        GPUNTT_NEED(plan, x, y, out, scratch)                                                     \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const BfvMultiplyPlan<T>*>(plan)->multiply(                          \
+                x, y, out, count, input_ntt != 0, output_ntt != 0, scratch, static_cast<hipStream_t>(stream));    \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_plan_owns_workspace_##S(const gpuntt_bfv_plan* plan)                           \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return reinterpret_cast<const BfvMultiplyPlan<T>*>(plan)->owns_workspace() ? 1 : 0;       \
+    }                                                                                             \
+    int gpuntt_bfv_plan_destroy_##S(gpuntt_bfv_plan* plan)                                        \
+    {                                                                                             \
+        return guarded([&] { delete reinterpret_cast<BfvMultiplyPlan<T>*>(plan); });              \
+    }                                                                                             \
+    int gpuntt_bfv_constants_##S(const CM* q_moduli_host, int q_count, const CM* b_moduli_host, int b_count,      \
+                                 T plain_modulus, int n_power, T* const* arrays_host)             \
+    {                                                                                             \
+        GPUNTT_NEED(arrays_host)                                                                  \
+        return guarded([&] {                                                                      \
+            const auto qs = to_mods<T>(q_moduli_host, q_count, "Invalid q_count!");                \
+            const auto bs = to_mods<T>(b_moduli_host, b_count, "Invalid b_count!");                \
+            T* const* v = arrays_host;                                                            \
+            BfvMultiplyPlan<T>::constants(                                                        \
+                qs.data(), q_count, bs.data(), b_count, plain_modulus, n_power,                   \
+                BfvConstants<T>{BaseConvConstants<T>{v[0], v[1], v[2], v[3], v[4], v[5], v[6]},   \
+                                BaseConvConstants<T>{v[7], v[8], v[9], v[10], v[11], v[12], v[13]}, v[14], v[15], \
+                                v[16], v[17]});                                                   \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_reference_extend_##S(const CM* q_moduli_host, int q_count, const CM* b_moduli_host,            \
+                                        int b_count, const T* in_host, T* full_host, int n_power, int stacks)     \
+    {                                                                                             \
+        return guarded([&] {                                                                      \
+            const auto qs = to_mods<T>(q_moduli_host, q_count, "Invalid q_count!");                \
+            const auto bs = to_mods<T>(b_moduli_host, b_count, "Invalid b_count!");                \
+            BfvMultiplyPlan<T>::reference_extend(qs.data(), q_count, bs.data(), b_count, in_host, full_host,      \
+                                                 n_power, stacks);                                \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_reference_scale_round_##S(const CM* q_moduli_host, int q_count, const CM* b_moduli_host,       \
+                                             int b_count, T plain_modulus, const T* full_host, T* out_host,       \
+                                             int n_power, int stacks)                             \
+    {                                                                                             \
+        return guarded([&] {                                                                      \
+            const auto qs = to_mods<T>(q_moduli_host, q_count, "Invalid q_count!");                \
+            const auto bs = to_mods<T>(b_moduli_host, b_count, "Invalid b_count!");                \
+            BfvMultiplyPlan<T>::reference_scale_round(qs.data(), q_count, bs.data(), b_count, plain_modulus,      \
+                                                      full_host, out_host, n_power, stacks);      \
         });                                                                                       \
     }                                                                                             \
     int gpuntt_4step_plan_workspace_bytes_##S(int n_power, uint64_t* bytes_host)                  \

@@ -1,0 +1,143 @@
+// gpuntt/rns/bfv_multiply.cuh -- scale-invariant ciphertext multiplication (extension: no counterpart in the reference).
+//
+// The product the BFV family needs, round(t (x (x) y) / Q) over the integers, as ONE plan that owns the constants, the
+// order of steps, the scratch layout and the size proof of the auxiliary base -- the third operation
+// rns/base_conversion.cuh was built for, beside ModUp / ModDown (rns/key_switch.cuh) and rescaling.  All integers,
+// W = 8 * sizeof(T).
+//
+// Bases.  q-primes q_0 .. q_{L-1}, Q = prod q_i; auxiliary primes b_0 .. b_{K-1}, B = prod b_j; the FULL base is
+// {q_0 .. q_{L-1}, b_0 .. b_{K-1}} in that order, M = L + K <= 64 limbs, modulus m_m of the full base is q_m for m < L and
+// b_{m-L} otherwise.  The plaintext modulus t is a word, t >= 2; it is reduced per limb on the host.  N = 2^n_power,
+// n_power in [1, 28].  The constructor requires
+//       B >= 2 t N Q,
+// checked in exact integers on the host: std::invalid_argument("Auxiliary base too small!") otherwise.
+//   Why that is enough.  extend chooses |x~| <= Q (1/2 + eps), eps = 3 L / 2^W, so every coefficient of a tensor
+//   component obeys |d_c| <= 2 N Q^2 (1/2 + eps)^2 (d_1 is a sum of two negacyclic or cyclic products of N terms each).
+//   Divide by Q and multiply by t: |round(t d_c / Q)| <= 2 t N Q (1/2 + eps)^2 + 1/2 <= (B / 4) (1 + 2 eps)^2 + 1/2, half of
+//   what the centred representation modulo B holds.  So t d_c is an integer whose quotient fits B / 2 (scale_round below),
+//   and the last conversion, from {b} back to {q}, never comes near its band [B / 2, B / 2 + eps B): it is exact.
+//
+//   extend(in, full, stacks):  in = T[stacks][L][N] in coefficient form, ANY word is accepted (read modulo q_i);
+//     full = T[stacks][M][N]:
+//       m < L:      full[s][m] = in[s][m] mod q_m                                   canonical
+//       m = L + j:  full[s][m] = WORD FOR WORD what BaseConvPlan({q} -> {b})::convert gives in centred mode for stack s
+//     -- the residues of the representative of x in [-Q/2, Q/2 + eps Q) (base_conversion.cuh).  ONE launch of bfv_extend
+//     (KeySwitchPlan::mod_up at a single digit; a sibling of its kernel).  `in` must not overlap `full`
+//   scale_round(full, out, stacks):  full = T[stacks][M][N] in coefficient form, ANY word; out = T[stacks][L][N].
+//     DEFINITION, word for word, through the calls that exist beside it:
+//       1. s_m = ((t mod m_m) * full_m) mod m_m for every limb            -- what operator_gpu's multiplication gives
+//       2. r = BaseConvPlan({q} -> {b})::convert_and_divide, centred, with in = the q-limbs of s and c = the b-limbs of
+//          s: T[K] per column
+//       3. out = BaseConvPlan({b} -> {q})::convert, centred, of r
+//     Outside step 2's rounding band this is round(t X / Q) mod q_i for ANY integer X with those residues whose quotient
+//     fits B / 2; inside the band it is that value +- 1, exactly as mod_down documents.  ONE launch of bfv_scale_round:
+//     the K intermediate words never reach memory.  out must not overlap full (stacks of full are M N words apart, those
+//     of out L N)
+//   multiply(x, y, out, count, input_ntt, output_ntt, scratch):  x, y = T[2][count][L][N], the component-major layout every
+//     plan call writes; y may be exactly x (a squaring).  In coefficient form (input_ntt false) every word may hold any
+//     value: extend reads it modulo q_m.  In NTT form the first step is a transform, which is defined on residues: the
+//     words are canonical, as GPU_INTT takes them.  out = T[3][count][L][N]: out[2] is directly the c_in of
+//     KeySwitchPlan::apply for relinearization (components = 2; add its two outputs to out[0], out[1] modulo q_m).
+//     DEFINITION, word for word:
+//       1. [input_ntt: GPU_INTT over the q-base, 2 * count * L polynomials per operand]
+//       2. extend over the 2 * count stacks of each operand
+//       3. the full-base GPU_NTT
+//       4. per limb m < M the canonical residues d0 = x0 y0, d1 = x0 y1 + x1 y0, d2 = x1 y1 modulo m_m -- each what
+//          InnerProductPlan::multiply_accumulate gives (D = 1 for d0 and d2, D = 2 for d1, C = 1), as in
+//          multiply_relinearize's step 1
+//       5. the full-base GPU_INTT over 3 * count * M polynomials
+//       6. scale_round over 3 * count stacks
+//       7. [output_ntt: the q-base GPU_NTT over 3 * count * L polynomials]
+//     What runs: [the q-base INTT and] bfv_extend once per operand (once in all for a squaring), ONE full-base NTT over
+//     both operands, ONE bfv_tensor, ONE full-base INTT, ONE bfv_scale_round, [ONE q-base NTT].  No step's launch count
+//     grows with count.  multiply allocates nothing and never synchronises: one stream, capturable into a hipGraph as it
+//     is.  count = 0 launches nothing.
+//   scratch: scratch_bytes(count) bytes owned by the CALLER, 256-byte aligned: the operands in the full base
+//     T[4][count][M][N] (x0, x1, y0, y1 -- bfv_tensor writes d0, d1, d2 over the first three, each word by the lane that
+//     read it) and T[2][count][L][N] for the coefficient form of one operand.
+//   overlap: out may be exactly x or exactly y -- their last read (bfv_extend, or the INTT before it) precedes the first
+//     write of out (bfv_scale_round) on the stream.  Any other overlap of out or the scratch with an operand or with each
+//     other: std::invalid_argument before anything is launched.  The same for a null pointer, a scratch that is not
+//     256-byte aligned, count < 0, a count beyond the grid and int limits of the transforms and kernels, and a multiply on
+//     a plan without transforms
+//   * transforms: as KeySwitchPlan -- ONE caller table pair in full-base order (slot i at i << n_power, the q-base is its
+//     first L slots), the M host n^-1 values, the reduction polynomial and a batch_hint; the plan builds four NTTPlan<T>
+//     inside its workspace (inverse and forward over the q-base, forward and inverse over the full base).  The tables
+//     must outlive the plan.  Both table pointers nullptr: a plan without transforms -- extend and scale_round work for
+//     any pairwise coprime Modulus<T> (not necessarily prime), multiply throws
+//   * workspace: every constant and every NTTPlan lives in workspace_bytes(L, K, n_power) bytes of device memory (nullptr =
+//     the plan allocates and owns it; owns_workspace()).  The constructor waits for `stream` once for its own constants
+//     and once in each NTTPlan it builds: up to five host waits per plan, none afterwards
+//   * std::invalid_argument from the constructor: "Auxiliary base too small!", a modulus that is not the Modulus<T> of
+//     its value ("Invalid modulus!"), n_power outside [1, 28] ("Invalid n_power range!"), moduli of the full base that are
+//     not pairwise coprime, L < 1, K < 1, M > 64, t < 2 ("Invalid plaintext modulus!"), one table pointer without the
+//     other or without the n^-1 values
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#include "gpuntt/common/common.cuh"
+#include "gpuntt/common/modular_arith.cuh"
+#include "gpuntt/common/nttparameters.cuh"
+#include "gpuntt/rns/base_conversion.cuh"
+
+namespace gpuntt
+{
+    // The plan's constants as the host derived them (BfvMultiplyPlan::constants, gpuntt_bfv_constants_*): every pointer
+    // is a caller array of the stated length.
+    template <typename T> struct BfvConstants
+    {
+        BaseConvConstants<T> up;   // BaseConvPlan::constants({q} -> {b}): extend, and step 2 of scale_round
+        BaseConvConstants<T> down; // BaseConvPlan::constants({b} -> {q}): step 3 of scale_round
+        T* t_mod;                  // [M] t mod m_m
+        T* t_mod_shoup;            // [M] floor((t mod m_m) 2^W / m_m)
+        // what bfv_scale_round multiplies with: t folded into the first constant of the first conversion
+        T* t_qhat_inv;       // [L] (t * qhat_i^-1) mod q_i
+        T* t_qhat_inv_shoup; // [L] its Shoup companion
+    };
+
+    template <typename T> class BfvMultiplyPlan
+    {
+      public:
+        static size_t workspace_bytes(int q_count, int b_count, int n_power);
+        static size_t scratch_bytes(int q_count, int b_count, int n_power, int count);
+
+        BfvMultiplyPlan(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* b_moduli_host, int b_count,
+                        T plain_modulus, int n_power, const Root<T>* forward_table_device,
+                        const Root<T>* inverse_table_device, const Ninverse<T>* mod_inverse_host,
+                        ReductionPolynomial reduction_poly, int batch_hint, stream_t stream,
+                        void* workspace_device = nullptr);
+        ~BfvMultiplyPlan();
+        BfvMultiplyPlan(const BfvMultiplyPlan&) = delete;
+        BfvMultiplyPlan& operator=(const BfvMultiplyPlan&) = delete;
+
+        void extend(const T* device_in, T* device_full, int stacks, stream_t stream) const;
+        void scale_round(const T* device_full, T* device_out, int stacks, stream_t stream) const;
+        void multiply(const T* device_x, const T* device_y, T* device_out, int count, bool input_ntt, bool output_ntt,
+                      void* scratch_device, stream_t stream) const;
+
+        int q_count() const;
+        int b_count() const;
+        int n_power() const;
+        T plain_modulus() const;
+        bool has_transforms() const;
+        bool owns_workspace() const; // false: the plan lives in the caller's workspace and has allocated nothing
+        size_t scratch_bytes(int count) const;
+
+        // host only (no GPU): the constants of these bases and this t, with the checks of the constructor
+        static void constants(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* b_moduli_host, int b_count,
+                              T plain_modulus, int n_power, const BfvConstants<T>& out);
+        // host only (no GPU): extend / scale_round on HOST arrays, with unsigned __int128 and %, after the same argument
+        // checks.  What tests and examples compare the kernels with; never a GPU fall-back
+        static void reference_extend(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* b_moduli_host,
+                                     int b_count, const T* in_host, T* full_host, int n_power, int stacks);
+        static void reference_scale_round(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* b_moduli_host,
+                                          int b_count, T plain_modulus, const T* full_host, T* out_host, int n_power,
+                                          int stacks);
+
+      private:
+        struct Impl;
+        Impl* p_;
+    };
+} // namespace gpuntt

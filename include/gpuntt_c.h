@@ -627,6 +627,75 @@ extern "C"
         const uint64_t* const* giant_keys_host, const uint32_t* giant_elements_host, int n2,
         const uint64_t* const* weights_host, uint64_t* out, int count, int output_ntt, void* scratch, void* stream);
 
+    /* ---- extension: scale-invariant ciphertext multiplication (BfvMultiplyPlan<T>, include/gpuntt/rns/bfv_multiply.cuh) ----
+     * round(t (x (x) y) / Q) for the q-base q_moduli_host (L), the auxiliary base b_moduli_host (K, B = prod b_j >=
+     * 2 t N Q or GPUNTT_ERR_INVALID_ARGUMENT "Auxiliary base too small!") and the plaintext modulus t >= 2; the full base
+     * is {q.., b..}, M = L + K <= 64.  forward_table / inverse_table / mod_inverse_host, reduction_poly, batch_hint and
+     * workspace_device as for gpuntt_keyswitch_plan_create_* (tables over the full base; all three NULL: a plan without
+     * transforms, extend and scale_round only); the workspace is gpuntt_bfv_plan_workspace_bytes_*() bytes.
+     *   extend       in T[stacks][L][N] (coefficient form, any words) -> full T[stacks][M][N]: the q-limbs reduced, the
+     *                b-limbs word for word the centred gpuntt_baseconv_plan_convert_* of {q} -> {b}; one kernel launch
+     *   scale_round  full T[stacks][M][N] (coefficient form, any words) -> out T[stacks][L][N]: every limb times t, the
+     *                centred convert_and_divide {q} -> {b}, the centred convert {b} -> {q}, word for word; one launch
+     *   multiply     x, y T[2][count][L][N] (y may be x) -> out T[3][count][L][N], the three components of the product;
+     *                input_ntt / output_ntt: the operands / the result are in NTT form over the q-base (operands in NTT
+     *                form are canonical residues; in coefficient form any word is read modulo its q).  The scratch is
+     *                gpuntt_bfv_plan_scratch_bytes_*() bytes, 256-byte aligned, owned by the caller; out may be exactly x
+     *                or exactly y.  out[2] is the c_in of gpuntt_keyswitch_plan_apply_* (components = 2) for
+     *                relinearization
+     * No call allocates or synchronises.
+     * host only (no GPU): constants -- arrays_host holds 18 caller arrays in the order of BfvConstants<T>: the seven of
+     * gpuntt_baseconv_constants_* for {q} -> {b} (qhat_inv[L], qhat_inv_shoup[L], matrix[L][K], q_mod_p[K],
+     * q_inv_mod_p[K], recip[L], bit_length[L]), the same seven for {b} -> {q}, then t_mod[M], t_mod_shoup[M],
+     * t_qhat_inv[L], t_qhat_inv_shoup[L]; reference_extend / reference_scale_round -- what extend / scale_round compute,
+     * on HOST arrays in exact integers after the same argument checks: what tests and examples compare the kernels with,
+     * never a fall-back */
+    typedef struct gpuntt_bfv_plan gpuntt_bfv_plan;
+    int gpuntt_bfv_plan_workspace_bytes_u32(int q_count, int b_count, int n_power, uint64_t* bytes_host);
+    int gpuntt_bfv_plan_workspace_bytes_u64(int q_count, int b_count, int n_power, uint64_t* bytes_host);
+    int gpuntt_bfv_plan_scratch_bytes_u32(int q_count, int b_count, int n_power, int count, uint64_t* bytes_host);
+    int gpuntt_bfv_plan_scratch_bytes_u64(int q_count, int b_count, int n_power, int count, uint64_t* bytes_host);
+    int gpuntt_bfv_plan_create_u32(gpuntt_bfv_plan** plan_host, const gpuntt_modulus32* q_moduli_host, int q_count,
+                                   const gpuntt_modulus32* b_moduli_host, int b_count, uint32_t plain_modulus, int n_power,
+                                   const uint32_t* forward_table, const uint32_t* inverse_table,
+                                   const uint32_t* mod_inverse_host, int reduction_poly, int batch_hint,
+                                   void* workspace_device, void* stream);
+    int gpuntt_bfv_plan_create_u64(gpuntt_bfv_plan** plan_host, const gpuntt_modulus64* q_moduli_host, int q_count,
+                                   const gpuntt_modulus64* b_moduli_host, int b_count, uint64_t plain_modulus, int n_power,
+                                   const uint64_t* forward_table, const uint64_t* inverse_table,
+                                   const uint64_t* mod_inverse_host, int reduction_poly, int batch_hint,
+                                   void* workspace_device, void* stream);
+    int gpuntt_bfv_plan_extend_u32(const gpuntt_bfv_plan* plan, const uint32_t* in, uint32_t* full, int stacks, void* stream);
+    int gpuntt_bfv_plan_extend_u64(const gpuntt_bfv_plan* plan, const uint64_t* in, uint64_t* full, int stacks, void* stream);
+    int gpuntt_bfv_plan_scale_round_u32(const gpuntt_bfv_plan* plan, const uint32_t* full, uint32_t* out, int stacks,
+                                        void* stream);
+    int gpuntt_bfv_plan_scale_round_u64(const gpuntt_bfv_plan* plan, const uint64_t* full, uint64_t* out, int stacks,
+                                        void* stream);
+    int gpuntt_bfv_plan_multiply_u32(const gpuntt_bfv_plan* plan, const uint32_t* x, const uint32_t* y, uint32_t* out,
+                                     int count, int input_ntt, int output_ntt, void* scratch, void* stream);
+    int gpuntt_bfv_plan_multiply_u64(const gpuntt_bfv_plan* plan, const uint64_t* x, const uint64_t* y, uint64_t* out,
+                                     int count, int input_ntt, int output_ntt, void* scratch, void* stream);
+    int gpuntt_bfv_plan_owns_workspace_u32(const gpuntt_bfv_plan* plan); /* 1 / 0, negative on error */
+    int gpuntt_bfv_plan_owns_workspace_u64(const gpuntt_bfv_plan* plan);
+    int gpuntt_bfv_plan_destroy_u32(gpuntt_bfv_plan* plan);
+    int gpuntt_bfv_plan_destroy_u64(gpuntt_bfv_plan* plan);
+    int gpuntt_bfv_constants_u32(const gpuntt_modulus32* q_moduli_host, int q_count, const gpuntt_modulus32* b_moduli_host,
+                                 int b_count, uint32_t plain_modulus, int n_power, uint32_t* const* arrays_host);
+    int gpuntt_bfv_constants_u64(const gpuntt_modulus64* q_moduli_host, int q_count, const gpuntt_modulus64* b_moduli_host,
+                                 int b_count, uint64_t plain_modulus, int n_power, uint64_t* const* arrays_host);
+    int gpuntt_bfv_reference_extend_u32(const gpuntt_modulus32* q_moduli_host, int q_count,
+                                        const gpuntt_modulus32* b_moduli_host, int b_count, const uint32_t* in_host,
+                                        uint32_t* full_host, int n_power, int stacks);
+    int gpuntt_bfv_reference_extend_u64(const gpuntt_modulus64* q_moduli_host, int q_count,
+                                        const gpuntt_modulus64* b_moduli_host, int b_count, const uint64_t* in_host,
+                                        uint64_t* full_host, int n_power, int stacks);
+    int gpuntt_bfv_reference_scale_round_u32(const gpuntt_modulus32* q_moduli_host, int q_count,
+                                             const gpuntt_modulus32* b_moduli_host, int b_count, uint32_t plain_modulus,
+                                             const uint32_t* full_host, uint32_t* out_host, int n_power, int stacks);
+    int gpuntt_bfv_reference_scale_round_u64(const gpuntt_modulus64* q_moduli_host, int q_count,
+                                             const gpuntt_modulus64* b_moduli_host, int b_count, uint64_t plain_modulus,
+                                             const uint64_t* full_host, uint64_t* out_host, int n_power, int stacks);
+
     /* ---- extension: prepared 4-step transforms (FourStepPlan<T>, include/gpuntt/ntt_4step/ntt_4step.cuh) ----
      * The Shoup pairs of the n1 / n2 / W tables are derived once, at creation, into workspace_device
      * (gpuntt_4step_plan_workspace_bytes_*() bytes owned by the caller) or a buffer the plan allocates (NULL).
