@@ -3,21 +3,14 @@
 // One lane owns one coefficient column of one ring element: it reads its L input words (coalesced: consecutive lanes,
 // consecutive columns), turns each into y_i with one exact Shoup product and parks the y_i in LDS -- at word
 // [i][lane], so a lane only ever reads what it wrote itself: no barrier, and consecutive lanes hit consecutive banks.
-// The K outputs are then produced KB at a time: for a block of KB outputs the lane walks i = 0 .. L-1 once, reads y_i
-// back from LDS and multiply-accumulates it into KB three-word accumulators (a 2W-bit sum plus a carry count: L = 64
-// terms of 2^124 do not fit 128 bits, 64 carries fit any word; 16 terms do fit, so the carry is looked at once per
-// 16 terms).  Blocking the OUTPUT loop keeps the live state at KB accumulators whatever L and K are; blocking the
-// input loop instead would need all K accumulators live (K = 64: 320 VGPRs).  Every constant -- the Shoup pair of
-// qhat_i^-1, the matrix row, the folding constants -- is indexed by
+// The K outputs are then produced BC_KB at a time: for a block of outputs the lane walks i = 0 .. L-1 once, reads y_i
+// back from LDS and multiply-accumulates it into BC_KB three-word accumulators, which leave through the three-product
+// fold -- the conversion unit of base_conversion_internal.hpp (bc_z, bc_block_mac, bc_fold), where the bounds are
+// proved.  Every constant -- the Shoup pair of qhat_i^-1, the matrix row, the folding constants -- is indexed by
 // wave-uniform values only, so it travels through the scalar cache.
 //
-// The accumulator S = c 2^2W + h 2^W + l leaves as  (h * [2^W]_p + c * [2^2W]_p + l) mod p: three exact Shoup
-// products against constants the plan derives (each canonical, their sum below 3 p < 2^W) and two conditional
-// subtractions.  Modulus<T>::mu is not used: its Barrett step is exact only for operands below 2^(2 bit + 1), and a
-// 20-bit p_j under 62-bit q_i sums to 2^88.
-//
-// Small count * N: the grid's second dimension splits the blocks of KB outputs over several workgroups, each of
-// which re-reads the column (from L2) and recomputes the y_i -- see base_conv_ksplit().
+// Small count * N: the grid's second dimension splits the blocks of BC_KB outputs over several workgroups, each of
+// which re-reads the column (from L2) and recomputes the y_i -- see host::bc_ksplit().
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -36,7 +29,7 @@ namespace gpuntt
     {
         namespace
         {
-            std::atomic<int> g_bc_ksplit{0}; // test hook baseconv_ksplit: 0 = base_conv_ksplit(), n = n workgroups per column tile
+            std::atomic<int> g_bc_ksplit{0}; // test hook baseconv_ksplit: 0 = rns_split(), n = n workgroups per column tile
         }
         void baseconv_set_ksplit(int v) { g_bc_ksplit.store(v, std::memory_order_relaxed); }
     } // namespace host
@@ -147,40 +140,19 @@ namespace gpuntt
                 const std::uint64_t p = h.p[j];
                 const std::uint64_t qm_p = qhat_mod(-1, p);
                 const std::uint64_t qi = bc_modinv(qm_p, p);
-                const std::uint64_t t1 = static_cast<std::uint64_t>((static_cast<U128>(1) << W) % p);
-                const std::uint64_t t2 = bc_mulmod(t1, t1, p);
+                const host::RnsFoldConsts f = host::rns_fold_consts(p, W);
                 h.qmod.push_back(qm_p);
                 h.negq.push_back(qm_p == 0 ? 0 : p - qm_p);
                 h.qinv.push_back(qi);
                 h.qinvp.push_back(shoup(qi, p));
-                h.t1.push_back(t1);
-                h.t1p.push_back(shoup(t1, p));
-                h.t2.push_back(t2);
-                h.t2p.push_back(shoup(t2, p));
-                h.onep.push_back(shoup(1, p));
+                h.t1.push_back(f.t1), h.t1p.push_back(f.t1p), h.t2.push_back(f.t2), h.t2p.push_back(f.t2p);
+                h.onep.push_back(f.onep);
             }
             return h;
         }
 
-        int padded(int K) { return (K + kern::BC_KB - 1) / kern::BC_KB * kern::BC_KB; }
-        size_t ws_words(int L, int K) { return 5 * static_cast<size_t>(L) + static_cast<size_t>(L + 9) * padded(K); }
-
-        // Workgroups per column tile.  A tile is BC_NT columns, and a workgroup that owns all of a tile's outputs
-        // reads the input once.  Below two workgroups per CU (256 CUs) the blocks of BC_KB outputs are spread over
-        // up to 8 workgroups per tile, which re-read the tile's input from L2.  Both numbers are estimates (two
-        // workgroups per CU as the fill target), not measured: DESIGN.md 3.10.
-        int base_conv_ksplit(unsigned long long tiles, int K)
-        {
-            const int jblocks = padded(K) / kern::BC_KB;
-            const int forced = host::g_bc_ksplit.load(std::memory_order_relaxed);
-            int s = 1;
-            if (forced > 0)
-                s = forced;
-            else
-                while (s < 8 && tiles * s < 512)
-                    s *= 2;
-            return s < jblocks ? s : jblocks;
-        }
+        using host::bc_padded;
+        size_t ws_words(int L, int K) { return 5 * static_cast<size_t>(L) + static_cast<size_t>(L + 9) * bc_padded(K); }
     } // namespace
 
     template <typename T> struct BaseConvPlan<T>::Impl
@@ -193,8 +165,7 @@ namespace gpuntt
         void launch(const T* in, const T* c, T* out, int n_power, int count, BaseConvMode mode, bool divide,
                     hipStream_t stream) const
         {
-            if (n_power <= 0 || n_power >= 29)
-                throw std::invalid_argument("Invalid n_power range!");
+            host::rns_check_n_power(n_power);
             if (mode != BaseConvMode::approximate && mode != BaseConvMode::centred)
                 throw std::invalid_argument("Invalid mode!");
             if (count < 0)
@@ -204,14 +175,10 @@ namespace gpuntt
             if (count == 0)
                 return;
             const unsigned long long total = static_cast<unsigned long long>(count) << n_power;
-            const unsigned long long tiles = (total + kern::BC_NT - 1) / kern::BC_NT;
-            if (tiles * kern::BC_NT > 0xFFFFFFFFull) // HIP caps a launch at 2^32 - 1 work-items per dimension
-                throw std::invalid_argument("Invalid count!");
-            const auto in_lo = reinterpret_cast<uintptr_t>(in), out_lo = reinterpret_cast<uintptr_t>(out);
-            const auto in_hi = in_lo + total * L * sizeof(T), out_hi = out_lo + total * K * sizeof(T);
-            if (in_lo < out_hi && out_lo < in_hi)
+            const unsigned long long tiles = host::column_tiles(total, kern::BC_NT, "Invalid count!");
+            if (host::rns_overlap(in, total * L * sizeof(T), out, total * K * sizeof(T)))
                 throw std::invalid_argument("Base conversion input and output overlap!");
-            const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(base_conv_ksplit(tiles, K)));
+            const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(host::bc_ksplit(tiles, K)));
             const size_t lds = static_cast<size_t>(L) * kern::BC_NT * sizeof(T);
             const bool cen = mode == BaseConvMode::centred;
 #define GPUNTT_BC_LAUNCH(CEN, DIV)                                                                                     \
@@ -241,7 +208,7 @@ namespace gpuntt
 
         template <typename T> std::vector<T> bc_image(const BcHostConsts& h, kern::BcOffsets& off)
         {
-            const int L = h.L, K = h.K, KP = padded(K);
+            const int L = h.L, K = h.K, KP = bc_padded(K);
             std::vector<T> img(ws_words(L, K), T(0));
             size_t at = 0;
             auto put = [&](const std::vector<std::uint64_t>& v, size_t slots) {
@@ -268,12 +235,41 @@ namespace gpuntt
             return img;
         }
 
-        int bc_ksplit(unsigned long long tiles, int K) { return base_conv_ksplit(tiles, K); }
+        int bc_ksplit(unsigned long long tiles, int K)
+        {
+            return rns_split(tiles, bc_padded(K) / kern::BC_KB, g_bc_ksplit.load(std::memory_order_relaxed));
+        }
+
+        template <typename T>
+        void bc_ref_convert(const BcHostConsts& c, const std::uint64_t* x, bool centred, std::uint64_t* conv)
+        {
+            constexpr int W = static_cast<int>(8 * sizeof(T));
+            std::uint64_t y[BASECONV_MAX_COUNT];
+            U128 zsum = static_cast<U128>(1) << (W - 1);
+            for (int i = 0; i < c.L; i++)
+            {
+                y[i] = static_cast<std::uint64_t>(static_cast<U128>(x[i] % c.q[i]) * c.w[i] % c.q[i]);
+                const int sh = static_cast<int>(c.blen[i]) - 1;
+                const U128 z = c.recip[i] != 0 ? (static_cast<U128>(y[i]) * c.recip[i]) >> sh
+                                               : static_cast<U128>(y[i]) << (W - sh);
+                zsum += static_cast<T>(z);
+            }
+            const std::uint64_t v = centred ? static_cast<std::uint64_t>(static_cast<T>(zsum >> W)) : 0;
+            for (int j = 0; j < c.K; j++)
+            {
+                const U128 p = c.p[j];
+                U128 s = static_cast<U128>(v % c.p[j]) * c.negq[j] % p;
+                for (int i = 0; i < c.L; i++)
+                    s = (s + static_cast<U128>(y[i] % c.p[j]) * c.matrix[static_cast<size_t>(i) * c.K + j]) % p;
+                conv[j] = static_cast<std::uint64_t>(s);
+            }
+        }
 
 #define GPUNTT_BC_INTERNAL(T)                                                                                          \
     template std::uint64_t bc_checked_value<T>(const Modulus<T>&);                                                     \
     template BcHostConsts bc_derive<T>(const Modulus<T>*, int, const Modulus<T>*, int);                                \
-    template std::vector<T> bc_image<T>(const BcHostConsts&, kern::BcOffsets&);
+    template std::vector<T> bc_image<T>(const BcHostConsts&, kern::BcOffsets&);                                        \
+    template void bc_ref_convert<T>(const BcHostConsts&, const std::uint64_t*, bool, std::uint64_t*);
         GPUNTT_BC_INTERNAL(Data32)
         GPUNTT_BC_INTERNAL(Data64)
 #undef GPUNTT_BC_INTERNAL
@@ -285,7 +281,7 @@ namespace gpuntt
             throw std::invalid_argument("Invalid in_count!");
         if (out_count < 1 || out_count > BASECONV_MAX_COUNT)
             throw std::invalid_argument("Invalid out_count!");
-        return (ws_words(in_count, out_count) * sizeof(T) + 255) / 256 * 256;
+        return host::rns_align(ws_words(in_count, out_count) * sizeof(T));
     }
 
     template <typename T>
@@ -294,7 +290,7 @@ namespace gpuntt
         : p_(nullptr)
     {
         const HostConsts h = derive<T>(in_moduli_host, in_count, out_moduli_host, out_count);
-        const int L = h.L, K = h.K, KP = padded(K);
+        const int L = h.L, K = h.K, KP = bc_padded(K);
         kern::BcOffsets off{};
         const std::vector<T> img = host::bc_image<T>(h, off);
 

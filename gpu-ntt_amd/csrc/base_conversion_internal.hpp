@@ -1,5 +1,7 @@
-// base_conversion_internal.hpp -- what key_switch.hip shares with base_conversion.hip: the constants of one pair of
-// bases in exact integers, their image in a workspace, the output-split policy and the kernel itself.  Not a public header.
+// base_conversion_internal.hpp -- what key_switch.hip and bfv_multiply.hip share with base_conversion.hip: the conversion
+// unit every conversion kernel of the library is made of (bc_z, bc_block_mac, bc_fold, with the proofs of their bounds),
+// the kernel base_convert itself, the constants of one pair of bases in exact integers, their image in a workspace, the
+// exact-integer column reference and the output-split policy.  Not a public header.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,6 +12,7 @@
 
 #include "gpuntt/rns/base_conversion.cuh"
 #include "rns_arith.hpp"
+#include "rns_host.hpp"
 
 namespace gpuntt
 {
@@ -39,27 +42,114 @@ namespace gpuntt
             unsigned onep;   // [KP] floor(2^W / p_j): the Shoup companion of 1
         };
 
-        // RnsWide, rns_mulhi, rns_shoup: rns_arith.hpp
+        // RnsWide, rns_mulhi, rns_shoup, ip_min: rns_arith.hpp
 
-        // the same as pointers into the workspace `base`, in the CONSTANT address space: nothing writes the workspace
-        // while a conversion runs, and a load from that address space at a wave-uniform address is a scalar load
-        // whatever the stores around it are (as plain global pointers the compiler could not rule out the stores to
-        // `out` -- which may alias c, so neither is __restrict__ -- and fetched the matrix rows with vector loads)
-        template <typename T> struct BcConsts
+        // Pointers into a workspace are in the CONSTANT address space: nothing writes the workspace while a conversion
+        // runs, and a load from that address space at a wave-uniform address is a scalar load whatever the stores around
+        // it are (as plain global pointers the compiler could not rule out the stores to `out` -- which may alias c, so
+        // neither is __restrict__ -- and fetched the matrix rows with vector loads)
+        template <typename T> using BcCP = const T __attribute__((address_space(4)))*;
+
+        // the five arrays bc_fold reads, indexed by the output modulus: what BcConsts and key_switch.hip's KsConsts share
+        template <typename T> struct BcFoldConsts
         {
-            using CP = const T __attribute__((address_space(4)))*;
-            CP q, w, wp, recip, shift, matrix, p, negq, qinv, qinvp, t1, t1p, t2, t2p, onep;
+            BcCP<T> t1, t1p, t2, t2p, onep;
+        };
+
+        // BcOffsets as pointers into the workspace `base`
+        template <typename T> struct BcConsts : BcFoldConsts<T>
+        {
+            using CP = BcCP<T>;
+            CP q, w, wp, recip, shift, matrix, p, negq, qinv, qinvp;
             __device__ BcConsts(const T* workspace, const BcOffsets& o)
             {
                 const CP base = (CP) (workspace);
                 q = base + o.q, w = base + o.w, wp = base + o.wp, recip = base + o.recip, shift = base + o.shift;
                 matrix = base + o.matrix, p = base + o.p, negq = base + o.negq, qinv = base + o.qinv;
-                qinvp = base + o.qinvp, t1 = base + o.t1, t1p = base + o.t1p, t2 = base + o.t2, t2p = base + o.t2p;
-                onep = base + o.onep;
+                qinvp = base + o.qinvp, this->t1 = base + o.t1, this->t1p = base + o.t1p, this->t2 = base + o.t2;
+                this->t2p = base + o.t2p, this->onep = base + o.onep;
             }
         };
 
         constexpr int BC_CHUNK = 16; // terms below 2^(2W-4) (moduli below 2^(W-2)) that a 2W-bit sum holds
+
+        // ---- the conversion unit: what base_convert, key_switch.hip's ks_mod_up and bfv_multiply.hip's two kernels are
+        // made of.  A lane owns one coefficient column; its y_i = x_i * qhat_i^-1 mod q_i lie in LDS at ys[i * ystride]
+
+        // z = (y R) >> (b - 1) < 2^W, the term of base_conversion.cuh's v; a power of two q = 2^(b - 1) has R = 2^W,
+        // stored as 0.  The z_i are summed from 2^(W-1) in a 2W-bit word whose high word is v
+        template <typename T> __device__ __forceinline__ T bc_z(T y, T recip, T shift)
+        {
+            using W2 = typename RnsWide<T>::type;
+            constexpr int W = static_cast<int>(8 * sizeof(T));
+            const int sh = static_cast<int>(shift);
+            return (recip != 0) ? static_cast<T>((static_cast<W2>(y) * recip) >> sh) : (y << (W - sh));
+        }
+
+        // BC_KB outputs of one conversion: acc[b] + carry[b] 2^2W = v * negq[b] + sum_{i < n} ys[i * ystride] * row[i *
+        // rstride + b]; without CENTRED the sum alone, and v and negq are not read.  row and negq point at the block's
+        // first column; both are padded with zeros to a multiple of BC_KB.  Blocking the OUTPUTS keeps the live state at
+        // BC_KB accumulators whatever n and the number of outputs are.  A term is below 2^(2W-4), so BC_CHUNK = 16 of
+        // them go into a plain 2W-bit sum with no carry to watch; the sums go into the three-word accumulator {carry,
+        // acc}, one carry test per chunk and output: n = 64 terms of 2^124 do not fit 128 bits, 64 carries fit any word.
+        // n >= 1 at every caller (every base has a modulus, every digit a limb); n = 0 would leave the seed alone
+        template <typename T, bool CENTRED>
+        __device__ __forceinline__ void bc_block_mac(const T* ys, int ystride, BcCP<T> row, int rstride, int n, T v,
+                                                     BcCP<T> negq, typename RnsWide<T>::type (&acc)[BC_KB],
+                                                     T (&carry)[BC_KB])
+        {
+            using W2 = typename RnsWide<T>::type;
+#pragma unroll
+            for (int b = 0; b < BC_KB; b++)
+            {
+                if constexpr (CENTRED)
+                    acc[b] = static_cast<W2>(v) * negq[b];
+                else
+                    acc[b] = 0;
+                carry[b] = 0;
+            }
+            for (int i0 = 0; i0 < n; i0 += BC_CHUNK)
+            {
+                const int i1 = ip_min(i0 + BC_CHUNK, n);
+                W2 part[BC_KB];
+#pragma unroll
+                for (int b = 0; b < BC_KB; b++)
+                    part[b] = 0;
+#pragma unroll 2
+                for (int i = i0; i < i1; i++)
+                {
+                    const T y = ys[i * ystride];
+#pragma unroll
+                    for (int b = 0; b < BC_KB; b++)
+                        part[b] += static_cast<W2>(y) * row[b];
+                    row += rstride;
+                }
+#pragma unroll
+                for (int b = 0; b < BC_KB; b++)
+                {
+                    acc[b] += part[b];
+                    carry[b] += (acc[b] < part[b]) ? 1u : 0u;
+                }
+            }
+        }
+
+        // The accumulator S = carry 2^2W + h 2^W + l modulo p, the output modulus at index j of k's arrays:
+        // h [2^W]_p + carry [2^2W]_p + l as three exact Shoup products against the plan's constants, each canonical, so
+        // their sum is below 3 p < 2^W, and two conditional subtractions.  Modulus<T>::mu is not used: its Barrett step is
+        // exact only for operands below 2^(2 bit + 1), and a 20-bit p_j under 62-bit q_i sums to 2^88.  Each constant is
+        // loaded where its product needs it.  (IpFold of inner_product_internal.hpp is the same fold over words held in
+        // registers; one function over the eight words for both put all five loads before the first product here and
+        // the four kernels were scheduled differently: DESIGN.md 3.10)
+        template <typename T>
+        __device__ __forceinline__ T bc_fold(typename RnsWide<T>::type acc, T carry, const BcFoldConsts<T>& k, int j, T p)
+        {
+            constexpr int W = static_cast<int>(8 * sizeof(T));
+            T r = rns_shoup<T>(static_cast<T>(acc >> W), k.t1[j], k.t1p[j], p);
+            r += rns_shoup<T>(carry, k.t2[j], k.t2p[j], p);
+            r += rns_shoup<T>(static_cast<T>(acc), T(1), k.onep[j], p);
+            r = r >= p ? r - p : r;
+            return r >= p ? r - p : r;
+        }
 
         // STRIDED: stack e of in, c and out starts e * stride words behind its pointer instead of at the dense
         // e L N, e K N and e K N -- a plan that converts limbs in place inside wider stacks (key_switch.hip).  A
@@ -79,6 +169,10 @@ namespace gpuntt
                                                               int L, int K, int KP, int n_power,
                                                               unsigned long long total, BcStrides<STRIDED> strides)
         {
+            // the plan refuses an empty input base.  Said here because with bc_block_mac inlined the compiler otherwise
+            // keeps an empty-sum path through every output block and zeroes the accumulators on both: 12 VALU
+            // instructions per block, 3 % of the u64 4 -> 28 ModUp
+            __builtin_assume(L > 0);
             const BcConsts<T> k(consts, off);
             using W2 = typename RnsWide<T>::type;
             constexpr int W = static_cast<int>(8 * sizeof(T));
@@ -103,13 +197,7 @@ namespace gpuntt
                 const T y = rns_shoup<T>(src[static_cast<unsigned long long>(i) << n_power], k.w[i], k.wp[i], q);
                 ys[i * BC_NT] = y;
                 if constexpr (CENTRED)
-                {
-                    const T r = k.recip[i];
-                    const int sh = static_cast<int>(k.shift[i]);
-                    // z_i = (y R_i) >> (b_i - 1) < 2^W; a power of two q_i = 2^(b_i - 1) has R_i = 2^W
-                    const T z = (r != 0) ? static_cast<T>((static_cast<W2>(y) * r) >> sh) : (y << (W - sh));
-                    zsum += z;
-                }
+                    zsum += bc_z<T>(y, k.recip[i], k.shift[i]);
             }
             T v = 0;
             if constexpr (CENTRED)
@@ -122,40 +210,9 @@ namespace gpuntt
                 obase = cbase = ((e * static_cast<unsigned>(K)) << n_power) + col;
             for (int j0 = static_cast<int>(blockIdx.y) * BC_KB; j0 < K; j0 += static_cast<int>(gridDim.y) * BC_KB)
             {
-                // BC_CHUNK terms at a time go into a plain 2W-bit sum (no carry to watch); the sums go into the
-                // three-word accumulator {carry, acc}, one carry test per chunk and output
                 W2 acc[BC_KB];
                 T carry[BC_KB];
-#pragma unroll
-                for (int b = 0; b < BC_KB; b++)
-                {
-                    acc[b] = CENTRED ? static_cast<W2>(v) * k.negq[j0 + b] : static_cast<W2>(0);
-                    carry[b] = 0;
-                }
-                typename BcConsts<T>::CP row = k.matrix + j0;
-                for (int i0 = 0; i0 < L; i0 += BC_CHUNK)
-                {
-                    const int i1 = min(i0 + BC_CHUNK, L);
-                    W2 part[BC_KB];
-#pragma unroll
-                    for (int b = 0; b < BC_KB; b++)
-                        part[b] = 0;
-#pragma unroll 2
-                    for (int i = i0; i < i1; i++)
-                    {
-                        const T y = ys[i * BC_NT];
-#pragma unroll
-                        for (int b = 0; b < BC_KB; b++)
-                            part[b] += static_cast<W2>(y) * row[b];
-                        row += KP;
-                    }
-#pragma unroll
-                    for (int b = 0; b < BC_KB; b++)
-                    {
-                        acc[b] += part[b];
-                        carry[b] += (acc[b] < part[b]) ? 1u : 0u;
-                    }
-                }
+                bc_block_mac<T, CENTRED>(ys, BC_NT, k.matrix + j0, KP, L, v, k.negq + j0, acc, carry);
 #pragma unroll
                 for (int b = 0; b < BC_KB; b++)
                 {
@@ -163,11 +220,7 @@ namespace gpuntt
                     if (j < K)
                     {
                         const T p = k.p[j];
-                        T r = rns_shoup<T>(static_cast<T>(acc[b] >> W), k.t1[j], k.t1p[j], p);
-                        r += rns_shoup<T>(carry[b], k.t2[j], k.t2p[j], p);
-                        r += rns_shoup<T>(static_cast<T>(acc[b]), T(1), k.onep[j], p); // r < 3 p < 2^W
-                        r = r >= p ? r - p : r;
-                        r = r >= p ? r - p : r;
+                        T r = bc_fold<T>(acc[b], carry[b], k, j, p);
                         const unsigned long long o = obase + (static_cast<unsigned long long>(j) << n_power);
                         if constexpr (DIVIDE)
                         {
@@ -201,7 +254,15 @@ namespace gpuntt
         // the workspace image of these constants (bc_image_words(L, K) words) and where its parts lie
         template <typename T> std::vector<T> bc_image(const BcHostConsts& h, kern::BcOffsets& off);
 
-        // workgroups per column tile that share the tile's outputs (base_conv_ksplit, with its test hook)
+        // base_conversion.cuh's formulas for one column in exact integers, every step reduced with %: x[i] (any words)
+        // of the input base of `c` -> conv[j]
+        template <typename T>
+        void bc_ref_convert(const BcHostConsts& c, const std::uint64_t* x, bool centred, std::uint64_t* conv);
+
+        // a count of outputs rounded up to whole blocks of BC_KB
+        inline int bc_padded(int count) { return (count + kern::BC_KB - 1) / kern::BC_KB * kern::BC_KB; }
+        // workgroups per column tile that share the tile's K outputs: rns_split over the blocks of BC_KB, with the test
+        // hook baseconv_ksplit
         int bc_ksplit(unsigned long long tiles, int K);
     } // namespace host
 } // namespace gpuntt

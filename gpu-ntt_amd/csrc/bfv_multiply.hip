@@ -7,13 +7,10 @@
 //   bfv_scale_round:  out = round(t X / Q) in the base q from the M words of X: t X, the centred conversion {q} -> {b} with
 //                     its division by Q, and the centred conversion {b} -> {q} of the result, in ONE pass over the stack
 //
-// The two conversion kernels keep the conventions of base_conversion.hip: one lane owns one coefficient
-// column; the y_i are parked in LDS at [i][lane], so a lane only reads back what it wrote itself -- no barrier, and
-// consecutive lanes hit consecutive banks; the outputs are produced BC_KB at a time, BC_CHUNK terms per 2W-bit partial sum
-// into a three-word accumulator; the accumulator leaves through three exact Shoup products against the plan's own
-// constants (never Modulus::mu); every constant is indexed by wave-uniform values only and is read through the constant
-// address space, hence by scalar loads.  bfv_block_mac and bfv_fold below are that arithmetic, written once for the three
-// conversions of this file.
+// The two conversion kernels keep the conventions of base_conversion.hip -- one lane owns one coefficient
+// column, the y_i are parked in LDS at [i][lane], every constant is indexed by wave-uniform values only and is read through
+// the constant address space -- and are made of its conversion unit: bc_z, bc_block_mac and bc_fold of
+// base_conversion_internal.hpp, where the bounds are proved.
 //
 // bfv_scale_round.  The lane reads the M words of its column once.  First conversion: y_i = full_i * [t qhat_i^-1 mod q_i]
 // -- t folded into the Shoup constant: the same canonical residue as ((t mod q_i) full_i mod q_i) * qhat_i^-1 mod q_i -- goes
@@ -48,70 +45,6 @@ namespace gpuntt
     {
         extern __shared__ __align__(16) unsigned char bfv_smem[]; // M (bfv_extend: L) rows of BC_NT words
 
-        // z = (y R) >> (b - 1) < 2^W, the term of base_conversion.cuh's v; a power of two q = 2^(b - 1) has R = 2^W,
-        // stored as 0
-        template <typename T> __device__ __forceinline__ T bfv_z(T y, T recip, T shift)
-        {
-            using W2 = typename RnsWide<T>::type;
-            constexpr int W = static_cast<int>(8 * sizeof(T));
-            const int sh = static_cast<int>(shift);
-            return (recip != 0) ? static_cast<T>((static_cast<W2>(y) * recip) >> sh) : (y << (W - sh));
-        }
-
-        // BC_KB outputs of one conversion: acc + carry 2^2W = v * negq[b] + sum_{i < n} ys[i * BC_NT] * row[i * stride + b].
-        // BC_CHUNK terms at a time go into a plain 2W-bit sum (no carry to watch); the sums go into the three-word
-        // accumulator, one carry test per chunk and output.  row and negq point at the block's first column; both are
-        // padded with zeros to a multiple of BC_KB
-        template <typename T>
-        __device__ __forceinline__ void bfv_block_mac(const T* ys, typename BcConsts<T>::CP row, int n, int stride, T v,
-                                                      typename BcConsts<T>::CP negq,
-                                                      typename RnsWide<T>::type (&acc)[BC_KB], T (&carry)[BC_KB])
-        {
-            using W2 = typename RnsWide<T>::type;
-#pragma unroll
-            for (int b = 0; b < BC_KB; b++)
-            {
-                acc[b] = static_cast<W2>(v) * negq[b];
-                carry[b] = 0;
-            }
-            for (int i0 = 0; i0 < n; i0 += BC_CHUNK)
-            {
-                const int i1 = ip_min(i0 + BC_CHUNK, n);
-                W2 part[BC_KB];
-#pragma unroll
-                for (int b = 0; b < BC_KB; b++)
-                    part[b] = 0;
-#pragma unroll 2
-                for (int i = i0; i < i1; i++)
-                {
-                    const T y = ys[i * BC_NT];
-#pragma unroll
-                    for (int b = 0; b < BC_KB; b++)
-                        part[b] += static_cast<W2>(y) * row[b];
-                    row += stride;
-                }
-#pragma unroll
-                for (int b = 0; b < BC_KB; b++)
-                {
-                    acc[b] += part[b];
-                    carry[b] += (acc[b] < part[b]) ? 1u : 0u;
-                }
-            }
-        }
-
-        // (h [2^W]_p + c [2^2W]_p + l) mod p for the accumulator c 2^2W + h 2^W + l: three exact Shoup products, each
-        // canonical, their sum below 3 p < 2^W; k: the image whose output base holds p at index j
-        template <typename T>
-        __device__ __forceinline__ T bfv_fold(typename RnsWide<T>::type acc, T carry, const BcConsts<T>& k, int j, T p)
-        {
-            constexpr int W = static_cast<int>(8 * sizeof(T));
-            T r = rns_shoup<T>(static_cast<T>(acc >> W), k.t1[j], k.t1p[j], p);
-            r += rns_shoup<T>(carry, k.t2[j], k.t2p[j], p);
-            r += rns_shoup<T>(static_cast<T>(acc), T(1), k.onep[j], p);
-            r = r >= p ? r - p : r;
-            return r >= p ? r - p : r;
-        }
-
         // in: T[stacks][L][N], full: T[stacks][M][N], M = L + K; total = stacks N columns.  grid: x = column tile
         template <typename T>
         __global__ __launch_bounds__(BC_NT) void bfv_extend(const T* __restrict__ in, T* __restrict__ full,
@@ -141,7 +74,7 @@ namespace gpuntt
                 ys[i * BC_NT] = y;
                 // the canonical word: a conditional subtraction does not reduce a 64-bit word modulo a 20-bit q
                 dst[static_cast<unsigned long long>(i) << n_power] = rns_shoup<T>(x, T(1), onepq[i], q);
-                zsum += bfv_z<T>(y, k.recip[i], k.shift[i]);
+                zsum += bc_z<T>(y, k.recip[i], k.shift[i]);
             }
             const T v = static_cast<T>(zsum >> W);
 
@@ -150,13 +83,13 @@ namespace gpuntt
             {
                 W2 acc[BC_KB];
                 T carry[BC_KB];
-                bfv_block_mac<T>(ys, k.matrix + j0, L, KP, v, k.negq + j0, acc, carry);
+                bc_block_mac<T, true>(ys, BC_NT, k.matrix + j0, KP, L, v, k.negq + j0, acc, carry);
 #pragma unroll
                 for (int b = 0; b < BC_KB; b++)
                 {
                     const int j = j0 + b;
                     if (j < K)
-                        dst[static_cast<unsigned long long>(j) << n_power] = bfv_fold<T>(acc[b], carry[b], k, j, k.p[j]);
+                        dst[static_cast<unsigned long long>(j) << n_power] = bc_fold<T>(acc[b], carry[b], k, j, k.p[j]);
                 }
             }
         }
@@ -191,7 +124,7 @@ namespace gpuntt
             {
                 const T y = rns_shoup<T>(src[static_cast<unsigned long long>(i) << n_power], wt[i], wtp[i], ku.q[i]);
                 ys[i * BC_NT] = y;
-                zsum += bfv_z<T>(y, ku.recip[i], ku.shift[i]);
+                zsum += bc_z<T>(y, ku.recip[i], ku.shift[i]);
             }
             const T v = static_cast<T>(zsum >> W);
 
@@ -201,7 +134,7 @@ namespace gpuntt
             {
                 W2 acc[BC_KB];
                 T carry[BC_KB];
-                bfv_block_mac<T>(ys, ku.matrix + j0, L, KP, v, ku.negq + j0, acc, carry);
+                bc_block_mac<T, true>(ys, BC_NT, ku.matrix + j0, KP, L, v, ku.negq + j0, acc, carry);
 #pragma unroll
                 for (int b = 0; b < BC_KB; b++)
                 {
@@ -209,14 +142,14 @@ namespace gpuntt
                     if (j < K)
                     {
                         const T p = ku.p[j];
-                        const T conv = bfv_fold<T>(acc[b], carry[b], ku, j, p);
+                        const T conv = bc_fold<T>(acc[b], carry[b], ku, j, p);
                         // c_j = (t mod b_j) full_{L+j} mod b_j; c - conv as a word that is congruent to it
                         const T c = rns_shoup<T>(src[static_cast<unsigned long long>(j) << n_power], tb[j], tbp[j], p);
                         const T d = c >= conv ? c - conv : c + (p - conv);
                         const T r = rns_shoup<T>(d, ku.qinv[j], ku.qinvp[j], p); // step 2's word
                         const T y2 = rns_shoup<T>(r, kd.w[j], kd.wp[j], p);
                         y2s[j * BC_NT] = y2;
-                        zsum2 += bfv_z<T>(y2, kd.recip[j], kd.shift[j]);
+                        zsum2 += bc_z<T>(y2, kd.recip[j], kd.shift[j]);
                     }
                 }
             }
@@ -228,13 +161,13 @@ namespace gpuntt
             {
                 W2 acc[BC_KB];
                 T carry[BC_KB];
-                bfv_block_mac<T>(y2s, kd.matrix + i0, K, LP, v2, kd.negq + i0, acc, carry);
+                bc_block_mac<T, true>(y2s, BC_NT, kd.matrix + i0, LP, K, v2, kd.negq + i0, acc, carry);
 #pragma unroll
                 for (int b = 0; b < BC_KB; b++)
                 {
                     const int i = i0 + b;
                     if (i < L)
-                        dst[static_cast<unsigned long long>(i) << n_power] = bfv_fold<T>(acc[b], carry[b], kd, i, kd.p[i]);
+                        dst[static_cast<unsigned long long>(i) << n_power] = bc_fold<T>(acc[b], carry[b], kd, i, kd.p[i]);
                 }
             }
         }
@@ -286,8 +219,12 @@ namespace gpuntt
     {
         using U128 = unsigned __int128;
 
-        size_t bfv_align(size_t bytes) { return (bytes + 255) / 256 * 256; }
-        int bfv_padded(int K) { return (K + kern::BC_KB - 1) / kern::BC_KB * kern::BC_KB; }
+        // rns_host.hpp and, for bc_padded, base_conversion_internal.hpp
+        using host::bc_padded;
+        using host::column_tiles;
+        using host::rns_align;
+        using host::rns_check_n_power;
+        using host::rns_overlap;
 
         void bfv_check_counts(int L, int K)
         {
@@ -295,16 +232,6 @@ namespace gpuntt
                 throw std::invalid_argument("Invalid q_count!");
             if (K < 1 || K > BASECONV_MAX_COUNT || L + K > BASECONV_MAX_COUNT)
                 throw std::invalid_argument("Invalid b_count!");
-        }
-        void bfv_check_n_power(int n_power)
-        {
-            if (n_power <= 0 || n_power >= 29)
-                throw std::invalid_argument("Invalid n_power range!");
-        }
-        bool bfv_overlap(const void* a, std::uint64_t a_bytes, const void* b, std::uint64_t b_bytes)
-        {
-            const auto al = reinterpret_cast<uintptr_t>(a), bl = reinterpret_cast<uintptr_t>(b);
-            return al < bl + b_bytes && bl < al + a_bytes;
         }
 
         // a product of words in exact integers, little-endian 64-bit limbs: the size check B >= 2 t N Q
@@ -362,7 +289,7 @@ namespace gpuntt
             h.mod.insert(h.mod.end(), h.up.p.begin(), h.up.p.end());
             if (n_power >= 0)
             {
-                bfv_check_n_power(n_power);
+                rns_check_n_power(n_power);
                 Big B{1}, need{2};
                 for (int j = 0; j < K; j++)
                     big_mul(B, h.mod[L + j]);
@@ -378,11 +305,10 @@ namespace gpuntt
                 const std::uint64_t q = h.mod[m];
                 auto shoup = [&](std::uint64_t v) { return static_cast<std::uint64_t>((static_cast<U128>(v) << W) / q); };
                 const std::uint64_t tq = t % q;
-                const std::uint64_t t1 = static_cast<std::uint64_t>((static_cast<U128>(1) << W) % q);
-                const std::uint64_t t2 = static_cast<std::uint64_t>(static_cast<U128>(t1) * t1 % q);
+                const host::RnsFoldConsts f = host::rns_fold_consts(q, W);
                 h.tm.push_back(tq), h.tmp.push_back(shoup(tq));
-                h.t1.push_back(t1), h.t1p.push_back(shoup(t1)), h.t2.push_back(t2), h.t2p.push_back(shoup(t2));
-                h.onep.push_back(shoup(1));
+                h.t1.push_back(f.t1), h.t1p.push_back(f.t1p), h.t2.push_back(f.t2), h.t2p.push_back(f.t2p);
+                h.onep.push_back(f.onep);
                 if (m < L)
                 {
                     const std::uint64_t w = static_cast<std::uint64_t>(static_cast<U128>(tq) * h.up.w[m] % q);
@@ -399,18 +325,18 @@ namespace gpuntt
         template <typename T> BfvLayout bfv_layout(int L, int K, int n_power)
         {
             bfv_check_counts(L, K);
-            bfv_check_n_power(n_power);
+            rns_check_n_power(n_power);
             const int M = L + K;
             BfvLayout w{};
             size_t at = 0;
             auto take = [&](size_t bytes) {
                 const size_t first = at;
-                at += bfv_align(bytes);
+                at += rns_align(bytes);
                 return first;
             };
             w.up = take(host::bc_image_words(L, K) * sizeof(T));
             w.down = take(host::bc_image_words(K, L) * sizeof(T));
-            w.extra = take((3 * static_cast<size_t>(L) + 2 * static_cast<size_t>(bfv_padded(K))) * sizeof(T));
+            w.extra = take((3 * static_cast<size_t>(L) + 2 * static_cast<size_t>(bc_padded(K))) * sizeof(T));
             w.fold = take(6 * static_cast<size_t>(M) * sizeof(T));
             w.ntt_q_i = take(NTTPlan<T>::workspace_bytes(n_power, L));
             w.ntt_q_f = take(NTTPlan<T>::workspace_bytes(n_power, L));
@@ -440,8 +366,8 @@ namespace gpuntt
             const size_t poly = (static_cast<size_t>(count) << n_power) * sizeof(T);
             BfvScratch s{};
             s.e = 0;
-            s.coeff = s.e + bfv_align(poly * M * 4);
-            s.total = s.coeff + bfv_align(poly * L * 2);
+            s.coeff = s.e + rns_align(poly * M * 4);
+            s.total = s.coeff + rns_align(poly * L * 2);
             return s;
         }
 
@@ -450,22 +376,14 @@ namespace gpuntt
         template <typename T>
         void bfv_check_stacks(int narrow, int wide, const T* a, const T* b, int n_power, int stacks, const char* what)
         {
-            bfv_check_n_power(n_power);
+            rns_check_n_power(n_power);
             if (stacks < 0)
                 throw std::invalid_argument("Invalid stacks!");
             if (a == nullptr || b == nullptr)
                 throw std::invalid_argument("null pointer argument");
             const std::uint64_t cols = static_cast<std::uint64_t>(stacks) << n_power;
-            if (stacks > 0 && bfv_overlap(a, cols * narrow * sizeof(T), b, cols * wide * sizeof(T)))
+            if (stacks > 0 && rns_overlap(a, cols * narrow * sizeof(T), b, cols * wide * sizeof(T)))
                 throw std::invalid_argument(what);
-        }
-        unsigned bfv_tiles(int n_power, std::uint64_t stacks) // of bfv_extend and bfv_scale_round
-        {
-            const unsigned long long total = stacks << n_power;
-            const unsigned long long tiles = (total + kern::BC_NT - 1) / kern::BC_NT;
-            if (tiles * kern::BC_NT > 0xFFFFFFFFull) // HIP caps a launch at 2^32 - 1 work-items per dimension
-                throw std::invalid_argument("Invalid stacks!");
-            return static_cast<unsigned>(tiles);
         }
 
         template <typename T, int V>
@@ -511,10 +429,11 @@ namespace gpuntt
             bfv_check_stacks<T>(L, M, in, full, n, stacks, "extend input and output overlap!");
             if (stacks == 0)
                 return;
-            const unsigned tiles = bfv_tiles(n, static_cast<std::uint64_t>(stacks));
+            const unsigned long long total = static_cast<unsigned long long>(stacks) << n;
+            const unsigned tiles = static_cast<unsigned>(column_tiles(total, kern::BC_NT, "Invalid stacks!"));
             GPUNTT_LAUNCH((kern::bfv_extend<T>), dim3(tiles), dim3(kern::BC_NT),
                           static_cast<size_t>(L) * kern::BC_NT * sizeof(T), stream, in, full, consts(), up_off, ex_off, L,
-                          K, bfv_padded(K), n, static_cast<unsigned long long>(stacks) << n);
+                          K, bc_padded(K), n, total);
             GPUNTT_HIP_CHECK(hipGetLastError());
         }
 
@@ -523,10 +442,11 @@ namespace gpuntt
             bfv_check_stacks<T>(L, M, out, full, n, stacks, "scale_round input and output overlap!");
             if (stacks == 0)
                 return;
-            const unsigned tiles = bfv_tiles(n, static_cast<std::uint64_t>(stacks));
+            const unsigned long long total = static_cast<unsigned long long>(stacks) << n;
+            const unsigned tiles = static_cast<unsigned>(column_tiles(total, kern::BC_NT, "Invalid stacks!"));
             GPUNTT_LAUNCH((kern::bfv_scale_round<T>), dim3(tiles), dim3(kern::BC_NT),
                           static_cast<size_t>(M) * kern::BC_NT * sizeof(T), stream, full, out, consts(), up_off, down_off,
-                          ex_off, L, K, bfv_padded(K), bfv_padded(L), n, static_cast<unsigned long long>(stacks) << n);
+                          ex_off, L, K, bc_padded(K), bc_padded(L), n, total);
             GPUNTT_HIP_CHECK(hipGetLastError());
         }
 
@@ -546,19 +466,19 @@ namespace gpuntt
             const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T), out_bytes = cols * L * 3 * sizeof(T);
             for (const T* op : {x, y})
             {
-                if (bfv_overlap(scratch, s.total, op, ct_bytes))
+                if (rns_overlap(scratch, s.total, op, ct_bytes))
                     throw std::invalid_argument("out or the scratch overlaps an operand!");
                 // out may be exactly x or exactly y: the last read of both (bfv_extend, or the INTT before it) precedes
                 // bfv_scale_round's first write on the stream.  Any other overlap is refused
-                if (bfv_overlap(out, out_bytes, op, ct_bytes) && op != out)
+                if (rns_overlap(out, out_bytes, op, ct_bytes) && op != out)
                     throw std::invalid_argument("out or the scratch overlaps an operand!");
             }
-            if (bfv_overlap(out, out_bytes, scratch, s.total))
+            if (rns_overlap(out, out_bytes, scratch, s.total))
                 throw std::invalid_argument("The scratch overlaps out!");
             // every limit before the first launch: the batches of the transforms are ints, the grids as the launches check
             if (4ull * static_cast<unsigned>(count) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
                 throw std::invalid_argument("Invalid count!");
-            (void) bfv_tiles(n, 3ull * static_cast<unsigned>(count));
+            (void) column_tiles((3ull * static_cast<unsigned>(count)) << n, kern::BC_NT, "Invalid stacks!");
             const bool square = x == y;
             T* e = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.e);
             T* coeff = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.coeff);
@@ -591,7 +511,7 @@ namespace gpuntt
     template <typename T> size_t BfvMultiplyPlan<T>::scratch_bytes(int q_count, int b_count, int n_power, int count)
     {
         bfv_check_counts(q_count, b_count);
-        bfv_check_n_power(n_power);
+        rns_check_n_power(n_power);
         return bfv_scratch<T>(q_count, q_count + b_count, n_power, count).total;
     }
 
@@ -604,7 +524,7 @@ namespace gpuntt
         : p_(nullptr)
     {
         bfv_check_counts(q_count, b_count);
-        bfv_check_n_power(n_power);
+        rns_check_n_power(n_power);
         const BfvHost h = bfv_derive<T>(q_moduli_host, q_count, b_moduli_host, b_count, plain_modulus, n_power);
         const BfvLayout lay = bfv_layout<T>(h.L, h.K, n_power);
         const bool transforms = forward_table_device != nullptr || inverse_table_device != nullptr;
@@ -614,7 +534,7 @@ namespace gpuntt
         p->L = h.L, p->K = h.K, p->M = h.M, p->n = n_power, p->t = plain_modulus, p->lay = lay;
 
         // the run of constants: the two images, the plan's own arrays, the fold image -- one host buffer, one copy
-        const int L = h.L, KP = bfv_padded(h.K);
+        const int L = h.L, KP = bc_padded(h.K);
         std::vector<T> run((lay.ntt_q_i - lay.up) / sizeof(T), T(0));
         kern::BcOffsets up_rel{}, down_rel{};
         const std::vector<T> up_img = host::bc_image<T>(h.up, up_rel), down_img = host::bc_image<T>(h.down, down_rel);
@@ -720,7 +640,7 @@ namespace gpuntt
     void BfvMultiplyPlan<T>::constants(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* b_moduli_host,
                                        int b_count, T plain_modulus, int n_power, const BfvConstants<T>& out)
     {
-        bfv_check_n_power(n_power);
+        rns_check_n_power(n_power);
         const BfvHost h = bfv_derive<T>(q_moduli_host, q_count, b_moduli_host, b_count, plain_modulus, n_power);
         for (const T* ptr : {out.t_mod, out.t_mod_shoup, out.t_qhat_inv, out.t_qhat_inv_shoup})
             if (ptr == nullptr)
@@ -742,36 +662,6 @@ namespace gpuntt
         copy(h.tm, out.t_mod), copy(h.tmp, out.t_mod_shoup), copy(h.wt, out.t_qhat_inv), copy(h.wtp, out.t_qhat_inv_shoup);
     }
 
-    namespace
-    {
-        // base_conversion.cuh's centred formulas for one column: x[i] (canonical) of the input base of `c` -> conv[j],
-        // every step reduced with %
-        template <typename T>
-        void bfv_ref_convert(const host::BcHostConsts& c, const std::uint64_t* x, std::uint64_t* conv)
-        {
-            constexpr int W = static_cast<int>(8 * sizeof(T));
-            std::uint64_t y[BASECONV_MAX_COUNT];
-            U128 zsum = static_cast<U128>(1) << (W - 1);
-            for (int i = 0; i < c.L; i++)
-            {
-                y[i] = static_cast<std::uint64_t>(static_cast<U128>(x[i] % c.q[i]) * c.w[i] % c.q[i]);
-                const int sh = static_cast<int>(c.blen[i]) - 1;
-                const U128 z = c.recip[i] != 0 ? (static_cast<U128>(y[i]) * c.recip[i]) >> sh
-                                               : static_cast<U128>(y[i]) << (W - sh);
-                zsum += static_cast<T>(z);
-            }
-            const std::uint64_t v = static_cast<std::uint64_t>(static_cast<T>(zsum >> W));
-            for (int j = 0; j < c.K; j++)
-            {
-                const U128 p = c.p[j];
-                U128 s = static_cast<U128>(v % c.p[j]) * c.negq[j] % p;
-                for (int i = 0; i < c.L; i++)
-                    s = (s + static_cast<U128>(y[i] % c.p[j]) * c.matrix[static_cast<size_t>(i) * c.K + j]) % p;
-                conv[j] = static_cast<std::uint64_t>(s);
-            }
-        }
-    } // namespace
-
     template <typename T>
     void BfvMultiplyPlan<T>::reference_extend(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* b_moduli_host,
                                               int b_count, const T* in_host, T* full_host, int n_power, int stacks)
@@ -790,7 +680,7 @@ namespace gpuntt
                     x[i] = src[i * n] % h.mod[i];
                     dst[i * n] = static_cast<T>(x[i]);
                 }
-                bfv_ref_convert<T>(h.up, x, conv);
+                host::bc_ref_convert<T>(h.up, x, true, conv);
                 for (int k = 0; k < h.K; k++)
                     dst[(h.L + k) * n] = static_cast<T>(conv[k]);
             }
@@ -811,14 +701,14 @@ namespace gpuntt
                 const T* src = full_host + static_cast<size_t>(st) * h.M * n + j;
                 for (int m = 0; m < h.M; m++) // step 1
                     s[m] = static_cast<std::uint64_t>(static_cast<U128>(h.tm[m]) * (src[m * n] % h.mod[m]) % h.mod[m]);
-                bfv_ref_convert<T>(h.up, s, conv); // step 2
+                host::bc_ref_convert<T>(h.up, s, true, conv); // step 2
                 for (int k = 0; k < h.K; k++)
                 {
                     const std::uint64_t b = h.mod[h.L + k], c = s[h.L + k];
                     const std::uint64_t diff = c >= conv[k] ? c - conv[k] : c + (b - conv[k]);
                     r[k] = static_cast<std::uint64_t>(static_cast<U128>(diff) * h.up.qinv[k] % b);
                 }
-                bfv_ref_convert<T>(h.down, r, conv); // step 3
+                host::bc_ref_convert<T>(h.down, r, true, conv); // step 3
                 for (int i = 0; i < h.L; i++)
                     out_host[(static_cast<size_t>(st) * h.L + i) * n + j] = static_cast<T>(conv[i]);
             }

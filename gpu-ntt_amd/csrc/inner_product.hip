@@ -22,6 +22,7 @@
 #include "gpuntt/rns/inner_product.cuh"
 #include "inner_product_internal.hpp"
 #include "launch.hpp"
+#include "rns_host.hpp"
 
 namespace gpuntt
 {
@@ -70,21 +71,14 @@ namespace gpuntt
                 throw std::invalid_argument("Invalid mod_count!");
             if (mods == nullptr)
                 throw std::invalid_argument("null pointer argument");
-            auto shoup = [](std::uint64_t v, std::uint64_t m) {
-                return static_cast<std::uint64_t>((static_cast<U128>(v) << W) / m);
-            };
             IpHostConsts h;
             for (int i = 0; i < M; i++)
             {
                 const std::uint64_t q = ip_checked_value(mods[i]);
-                const std::uint64_t t1 = static_cast<std::uint64_t>((static_cast<U128>(1) << W) % q);
-                const std::uint64_t t2 = static_cast<std::uint64_t>(static_cast<U128>(t1) * t1 % q);
+                const host::RnsFoldConsts f = host::rns_fold_consts(q, W);
                 h.q.push_back(q);
-                h.t1.push_back(t1);
-                h.t1p.push_back(shoup(t1, q));
-                h.t2.push_back(t2);
-                h.t2p.push_back(shoup(t2, q));
-                h.onep.push_back(shoup(1, q));
+                h.t1.push_back(f.t1), h.t1p.push_back(f.t1p), h.t2.push_back(f.t2), h.t2p.push_back(f.t2p);
+                h.onep.push_back(f.onep);
             }
             return h;
         }
@@ -94,8 +88,7 @@ namespace gpuntt
         void ip_check_call(int M, const T* a, const T* key, const T* out, int n_power, int D, int C, int count, int KM,
                            const int* key_limbs, unsigned char limbs[INNERPROD_MAX_MODULI])
         {
-            if (n_power <= 0 || n_power >= 29)
-                throw std::invalid_argument("Invalid n_power range!");
+            host::rns_check_n_power(n_power);
             if (D < 1 || D > INNERPROD_MAX_DIGITS)
                 throw std::invalid_argument("Invalid digits!");
             if (C < 1 || C > INNERPROD_MAX_COMPONENTS)
@@ -114,10 +107,10 @@ namespace gpuntt
             if (a == nullptr || key == nullptr || out == nullptr)
                 throw std::invalid_argument("null pointer argument");
             const std::uint64_t stack = (static_cast<std::uint64_t>(count) * M) << n_power;
-            const auto lo = [](const T* p) { return reinterpret_cast<uintptr_t>(p); };
-            const uintptr_t out_hi = lo(out) + C * stack * sizeof(T), a_hi = lo(a) + D * stack * sizeof(T);
-            const uintptr_t key_hi = lo(key) + ((static_cast<std::uint64_t>(D) * C * KM) << n_power) * sizeof(T);
-            if ((lo(a) < out_hi && lo(out) < a_hi) || (lo(key) < out_hi && lo(out) < key_hi))
+            const std::uint64_t out_bytes = C * stack * sizeof(T);
+            const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * C * KM) << n_power) * sizeof(T);
+            if (host::rns_overlap(a, D * stack * sizeof(T), out, out_bytes) ||
+                host::rns_overlap(key, key_bytes, out, out_bytes))
                 throw std::invalid_argument("Inner product output overlaps an input!");
         }
     } // namespace
@@ -194,7 +187,7 @@ namespace gpuntt
     {
         if (mod_count < 1 || mod_count > INNERPROD_MAX_MODULI)
             throw std::invalid_argument("Invalid mod_count!");
-        return (6 * static_cast<size_t>(mod_count) * sizeof(T) + 255) / 256 * 256;
+        return host::rns_align(6 * static_cast<size_t>(mod_count) * sizeof(T));
     }
 
     template <typename T>

@@ -26,7 +26,7 @@ namespace gpuntt
             unsigned char v[INNERPROD_MAX_MODULI];
         };
 
-        // RnsWide, rns_mulhi, rns_shoup: rns_arith.hpp
+        // RnsWide, rns_mulhi, rns_shoup, ip_min: rns_arith.hpp
 
         __device__ __forceinline__ Data32 ip_addc(Data32 a, Data32 b, Data32 cin, Data32* cout)
         {
@@ -81,9 +81,6 @@ namespace gpuntt
                 return x >= q ? x - q : x;
             }
         };
-
-        // (plain C++, so that the text also compiles for the host: tests/cpp/emulate_relin.cpp)
-        __device__ __forceinline__ constexpr int ip_min(int a, int b) { return a < b ? a : b; }
 
         // a lane's 16-byte group (V = 1: one word)
         template <typename T, int V> struct alignas(V * sizeof(T)) IpVec

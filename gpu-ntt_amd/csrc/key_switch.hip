@@ -4,17 +4,17 @@
 // reads its L words once (coalesced: consecutive lanes, consecutive columns) and parks two words per limb in LDS, at
 // [i][lane] -- y_i, one exact Shoup product with the constants of the limb's OWN digit, and the canonical word, one Shoup
 // product against the companion of 1 (a conditional subtraction does not reduce a 64-bit word modulo a 20-bit q).  A lane
-// only reads back what it wrote: no barrier.  The outputs are then walked as (digit d, block of KS_KB moduli) pairs: a
-// block inside S_d is KS_KB stores of parked words; any other block is the multiply-accumulate of base_conversion.hip
-// over i in S_d only -- KS_KB three-word accumulators, BC_CHUNK terms per 2W-bit partial sum, the chunk hand-over kept
-// because alpha may exceed a chunk -- followed by the three-product fold, with the parked word stored instead for the
-// moduli of the block that do lie in S_d (their matrix column is zero).  The live state is KS_KB accumulators whatever
-// L, M and D are.  The centred mode's v_d is recomputed only when the walk enters another digit: once per digit and
-// workgroup.  Stores (D M words per column) dominate loads (L words) and carry no lane condition.  Every constant is
-// indexed by wave-uniform values and comes through the constant address space, hence the scalar cache.
+// only reads back what it wrote: no barrier.  The outputs are then walked as (digit d, block of BC_KB moduli) pairs: a
+// block inside S_d is BC_KB stores of parked words; any other block goes through the conversion unit of
+// base_conversion_internal.hpp over i in S_d only (bc_z, bc_block_mac, bc_fold: the bounds are proved there; alpha may
+// exceed a chunk of the multiply-accumulate), with the parked word stored instead for the moduli of the block that do lie
+// in S_d (their matrix column is zero).  The live state is BC_KB accumulators whatever L, M and D are.  The centred mode's
+// v_d is recomputed only when the walk enters another digit: once per digit and workgroup.  Stores (D M words per column)
+// dominate loads (L words) and carry no lane condition.  Every constant is indexed by wave-uniform values and comes
+// through the constant address space, hence the scalar cache.
 //
 // Small count * N: blockIdx.y splits the (d, block) pairs of a column tile over several workgroups, each of which
-// re-reads the tile's input (from L2) and recomputes the parked words -- ks_split(), as base_conv_ksplit().
+// re-reads the tile's input (from L2) and recomputes the parked words -- host::rns_split(), as for base_convert.
 //
 // mod_down: kern::base_convert<T, centred, divide, STRIDED> of base_conversion_internal.hpp -- the shared kernel, the same
 // constants image (bc_image) -- with the stack strides of the full base: the special limbs and the q-limbs are read where
@@ -73,12 +73,11 @@ namespace gpuntt
     namespace kern
     {
         constexpr int KS_NT = 128;    // lanes per workgroup at most; 64 when two words per limb and lane pass 64 KiB of LDS
-        constexpr int KS_KB = 4;      // moduli per pass over the y_i of a digit
         constexpr size_t KS_LDS = 65536;
 
-        // RnsWide, rns_shoup: rns_arith.hpp; BC_CHUNK: base_conversion_internal.hpp
+        // RnsWide, rns_shoup: rns_arith.hpp; BC_KB, bc_z, bc_block_mac, bc_fold: base_conversion_internal.hpp
 
-        // where the ModUp constants lie in the workspace, in words; MP = M rounded up to KS_KB (padding: zero)
+        // where the ModUp constants lie in the workspace, in words; MP = M rounded up to BC_KB (padding: zero)
         struct KsOffsets
         {
             unsigned q;      // [L]
@@ -95,16 +94,16 @@ namespace gpuntt
             unsigned onep;   // [MP] floor(2^W / modulus m): the Shoup companion of 1
             unsigned negq;   // [D][MP] (-Q_d) mod modulus m
         };
-        template <typename T> struct KsConsts
+        template <typename T> struct KsConsts : BcFoldConsts<T>
         {
-            using CP = const T __attribute__((address_space(4)))*;
-            CP q, w, wp, recip, shift, matrix, mod, t1, t1p, t2, t2p, onep, negq;
+            using CP = BcCP<T>;
+            CP q, w, wp, recip, shift, matrix, mod, negq;
             __device__ KsConsts(const T* workspace, const KsOffsets& o)
             {
                 const CP base = (CP) (workspace);
                 q = base + o.q, w = base + o.w, wp = base + o.wp, recip = base + o.recip, shift = base + o.shift;
-                matrix = base + o.matrix, mod = base + o.mod, t1 = base + o.t1, t1p = base + o.t1p, t2 = base + o.t2;
-                t2p = base + o.t2p, onep = base + o.onep, negq = base + o.negq;
+                matrix = base + o.matrix, mod = base + o.mod, this->t1 = base + o.t1, this->t1p = base + o.t1p;
+                this->t2 = base + o.t2, this->t2p = base + o.t2p, this->onep = base + o.onep, negq = base + o.negq;
             }
         };
 
@@ -138,18 +137,18 @@ namespace gpuntt
             }
 
             const unsigned long long abase = ((e * static_cast<unsigned>(M)) << n_power) + col;
-            const int jblocks = MP / KS_KB, pairs = D * jblocks;
+            const int jblocks = MP / BC_KB, pairs = D * jblocks;
             int v_digit = -1;
             T v = 0;
             for (int pi = static_cast<int>(blockIdx.y); pi < pairs; pi += static_cast<int>(gridDim.y))
             {
-                const int d = pi / jblocks, j0 = (pi - d * jblocks) * KS_KB;
-                const int lo = d * alpha, hi = min(lo + alpha, L); // S_d
+                const int d = pi / jblocks, j0 = (pi - d * jblocks) * BC_KB;
+                const int lo = d * alpha, hi = ip_min(lo + alpha, L); // S_d
                 T* dst = a + static_cast<unsigned long long>(d) * digit_stride + abase;
-                if (j0 >= lo && j0 + KS_KB <= hi)
+                if (j0 >= lo && j0 + BC_KB <= hi)
                 {
 #pragma unroll
-                    for (int b = 0; b < KS_KB; b++)
+                    for (int b = 0; b < BC_KB; b++)
                         dst[static_cast<unsigned long long>(j0 + b) << n_power] = cs[(j0 + b) * nt];
                     continue;
                 }
@@ -159,52 +158,17 @@ namespace gpuntt
                     {
                         W2 zsum = static_cast<W2>(1) << (W - 1);
                         for (int i = lo; i < hi; i++)
-                        {
-                            const T y = ys[i * nt];
-                            const T r = k.recip[i];
-                            const int sh = static_cast<int>(k.shift[i]);
-                            // z_i = (y R_i) >> (b_i - 1) < 2^W; a power of two q_i = 2^(b_i - 1) has R_i = 2^W
-                            const T z = (r != 0) ? static_cast<T>((static_cast<W2>(y) * r) >> sh) : (y << (W - sh));
-                            zsum += z;
-                        }
+                            zsum += bc_z<T>(ys[i * nt], k.recip[i], k.shift[i]);
                         v = static_cast<T>(zsum >> W);
                         v_digit = d;
                     }
                 }
-                W2 acc[KS_KB];
-                T carry[KS_KB];
+                W2 acc[BC_KB];
+                T carry[BC_KB];
+                bc_block_mac<T, CENTRED>(ys + lo * nt, nt, k.matrix + lo * MP + j0, MP, hi - lo, v,
+                                         k.negq + d * MP + j0, acc, carry);
 #pragma unroll
-                for (int b = 0; b < KS_KB; b++)
-                {
-                    acc[b] = CENTRED ? static_cast<W2>(v) * k.negq[d * MP + j0 + b] : static_cast<W2>(0);
-                    carry[b] = 0;
-                }
-                typename KsConsts<T>::CP row = k.matrix + lo * MP + j0;
-                for (int i0 = lo; i0 < hi; i0 += BC_CHUNK)
-                {
-                    const int i1 = min(i0 + BC_CHUNK, hi);
-                    W2 part[KS_KB];
-#pragma unroll
-                    for (int b = 0; b < KS_KB; b++)
-                        part[b] = 0;
-#pragma unroll 2
-                    for (int i = i0; i < i1; i++)
-                    {
-                        const T y = ys[i * nt];
-#pragma unroll
-                        for (int b = 0; b < KS_KB; b++)
-                            part[b] += static_cast<W2>(y) * row[b];
-                        row += MP;
-                    }
-#pragma unroll
-                    for (int b = 0; b < KS_KB; b++)
-                    {
-                        acc[b] += part[b];
-                        carry[b] += (acc[b] < part[b]) ? 1u : 0u;
-                    }
-                }
-#pragma unroll
-                for (int b = 0; b < KS_KB; b++)
+                for (int b = 0; b < BC_KB; b++)
                 {
                     const int m = j0 + b;
                     if (m < M)
@@ -213,14 +177,7 @@ namespace gpuntt
                         if (m >= lo && m < hi)
                             r = cs[m * nt];
                         else
-                        {
-                            const T p = k.mod[m];
-                            r = rns_shoup<T>(static_cast<T>(acc[b] >> W), k.t1[m], k.t1p[m], p);
-                            r += rns_shoup<T>(carry[b], k.t2[m], k.t2p[m], p);
-                            r += rns_shoup<T>(static_cast<T>(acc[b]), T(1), k.onep[m], p); // r < 3 p < 2^W
-                            r = r >= p ? r - p : r;
-                            r = r >= p ? r - p : r;
-                        }
+                            r = bc_fold<T>(acc[b], carry[b], k, m, k.mod[m]);
                         dst[static_cast<unsigned long long>(m) << n_power] = r;
                     }
                 }
@@ -233,7 +190,7 @@ namespace gpuntt
     {
         namespace
         {
-            std::atomic<int> g_ks_split{0}; // test hook keyswitch_split: 0 = ks_split(), n = n workgroups per column tile
+            std::atomic<int> g_ks_split{0}; // test hook keyswitch_split: 0 = rns_split(), n = n workgroups per column tile
         }
         void keyswitch_set_split(int v) { g_ks_split.store(v, std::memory_order_relaxed); }
     } // namespace host
@@ -242,8 +199,12 @@ namespace gpuntt
     {
         using U128 = unsigned __int128;
 
-        int ks_padded(int M) { return (M + kern::KS_KB - 1) / kern::KS_KB * kern::KS_KB; }
-        size_t ks_align(size_t bytes) { return (bytes + 255) / 256 * 256; }
+        // rns_host.hpp and, for bc_padded, base_conversion_internal.hpp
+        using host::bc_padded;
+        using host::column_tiles;
+        using host::rns_align;
+        using host::rns_check_n_power;
+        using host::rns_overlap;
 
         // everything the host derives for one (q-base, special base, alpha), in exact integers
         struct KsHost
@@ -265,11 +226,6 @@ namespace gpuntt
                 throw std::invalid_argument("Invalid p_count!");
             if (alpha < 1)
                 throw std::invalid_argument("Invalid alpha!");
-        }
-        void ks_check_n_power(int n_power)
-        {
-            if (n_power <= 0 || n_power >= 29)
-                throw std::invalid_argument("Invalid n_power range!");
         }
         int ks_digits(int L, int alpha) { return static_cast<int>((static_cast<long long>(L) + alpha - 1) / alpha); }
 
@@ -302,12 +258,9 @@ namespace gpuntt
             }
             for (int m = 0; m < h.M; m++)
             {
-                const std::uint64_t q = h.mod[m];
-                const std::uint64_t t1 = static_cast<std::uint64_t>((static_cast<U128>(1) << W) % q);
-                const std::uint64_t t2 = static_cast<std::uint64_t>(static_cast<U128>(t1) * t1 % q);
-                auto shoup = [&](std::uint64_t v) { return static_cast<std::uint64_t>((static_cast<U128>(v) << W) / q); };
-                h.t1.push_back(t1), h.t1p.push_back(shoup(t1)), h.t2.push_back(t2), h.t2p.push_back(shoup(t2));
-                h.onep.push_back(shoup(1));
+                const host::RnsFoldConsts f = host::rns_fold_consts(h.mod[m], W);
+                h.t1.push_back(f.t1), h.t1p.push_back(f.t1p), h.t2.push_back(f.t2), h.t2p.push_back(f.t2p);
+                h.onep.push_back(f.onep);
             }
             return h;
         }
@@ -317,13 +270,13 @@ namespace gpuntt
 
         size_t ks_up_words(int L, int M, int D)
         {
-            const size_t MP = static_cast<size_t>(ks_padded(M));
+            const size_t MP = static_cast<size_t>(bc_padded(M));
             return 5 * static_cast<size_t>(L) + static_cast<size_t>(L) * MP + 6 * MP + static_cast<size_t>(D) * MP;
         }
 
         template <typename T> std::vector<T> ks_up_image(const KsHost& h, kern::KsOffsets& off)
         {
-            const int L = h.L, M = h.M, D = h.D, MP = ks_padded(M);
+            const int L = h.L, M = h.M, D = h.D, MP = bc_padded(M);
             std::vector<T> img(ks_up_words(L, M, D), T(0));
             size_t at = 0;
             auto take = [&](size_t words) {
@@ -364,33 +317,11 @@ namespace gpuntt
             return img;
         }
 
-        // Workgroups per column tile.  A workgroup that owns all (digit, block) pairs of a tile reads the input once.
-        // Below two workgroups per CU (256 CUs) the pairs are spread over up to 8 workgroups per tile, which re-read
-        // the tile's input from L2 and recompute the parked words.  Both numbers are estimates, as in
-        // base_conv_ksplit(), not measured: DESIGN.md 3.12.
-        int ks_split(unsigned long long tiles, int pairs)
-        {
-            const int forced = host::g_ks_split.load(std::memory_order_relaxed);
-            int s = 1;
-            if (forced > 0)
-                s = forced;
-            else
-                while (s < 8 && tiles * s < 512)
-                    s *= 2;
-            return s < pairs ? s : pairs;
-        }
-
-        bool ks_overlap(const void* a, std::uint64_t a_bytes, const void* b, std::uint64_t b_bytes)
-        {
-            const auto al = reinterpret_cast<uintptr_t>(a), bl = reinterpret_cast<uintptr_t>(b);
-            return al < bl + b_bytes && bl < al + a_bytes;
-        }
-
         // the argument checks of mod_up / mod_down (device or host arrays alike)
         template <typename T>
         void ks_check_mod_up(int L, int M, int D, const T* in, const T* a, int n_power, int count, BaseConvMode mode)
         {
-            ks_check_n_power(n_power);
+            rns_check_n_power(n_power);
             if (mode != BaseConvMode::approximate && mode != BaseConvMode::centred)
                 throw std::invalid_argument("Invalid mode!");
             if (count < 0)
@@ -398,19 +329,19 @@ namespace gpuntt
             if (in == nullptr || a == nullptr)
                 throw std::invalid_argument("null pointer argument");
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n_power;
-            if (ks_overlap(in, cols * L * sizeof(T), a, cols * M * D * sizeof(T)) && count > 0)
+            if (rns_overlap(in, cols * L * sizeof(T), a, cols * M * D * sizeof(T)) && count > 0)
                 throw std::invalid_argument("ModUp input and output overlap!");
         }
         template <typename T>
         void ks_check_mod_down(int L, int M, const T* x, const T* out, int n_power, int stacks) // L out of M limbs
         {
-            ks_check_n_power(n_power);
+            rns_check_n_power(n_power);
             if (stacks < 0)
                 throw std::invalid_argument("Invalid stacks!");
             if (x == nullptr || out == nullptr)
                 throw std::invalid_argument("null pointer argument");
             const std::uint64_t cols = static_cast<std::uint64_t>(stacks) << n_power;
-            if (ks_overlap(x, cols * M * sizeof(T), out, cols * L * sizeof(T)) && stacks > 0)
+            if (rns_overlap(x, cols * M * sizeof(T), out, cols * L * sizeof(T)) && stacks > 0)
                 throw std::invalid_argument("ModDown input and output overlap!");
         }
 
@@ -428,14 +359,14 @@ namespace gpuntt
         template <typename T> KsLayout ks_layout(int L, int K, int alpha, int n_power, int R)
         {
             ks_check_counts(L, K, alpha);
-            ks_check_n_power(n_power);
+            rns_check_n_power(n_power);
             ks_check_rescale_limbs(L, R, 0);
             const int M = L + K, D = ks_digits(L, alpha > L ? L : alpha);
             KsLayout w{};
             size_t at = 0;
             auto take = [&](size_t bytes) {
                 const size_t first = at;
-                at += ks_align(bytes);
+                at += rns_align(bytes);
                 return first;
             };
             w.up = take(ks_up_words(L, M, D) * sizeof(T));
@@ -469,9 +400,9 @@ namespace gpuntt
             const size_t poly = (static_cast<size_t>(count) << n_power) * sizeof(T);
             KsScratch s{};
             s.a = 0;
-            s.c_coeff = s.a + ks_align(poly * M * D);
-            s.inner_out = s.c_coeff + ks_align(poly * L);
-            s.total = s.inner_out + ks_align(poly * M * components);
+            s.c_coeff = s.a + rns_align(poly * M * D);
+            s.inner_out = s.c_coeff + rns_align(poly * L);
+            s.total = s.inner_out + rns_align(poly * M * components);
             return s;
         }
 
@@ -482,7 +413,7 @@ namespace gpuntt
                 throw std::invalid_argument("Invalid count!");
             if (elements < 1 || elements > GALOIS_MAX_COUNT)
                 throw std::invalid_argument("Invalid galois_count!");
-            return ks_align((static_cast<size_t>(count) << n_power) * sizeof(T) * M * 2 * elements);
+            return rns_align((static_cast<size_t>(count) << n_power) * sizeof(T) * M * 2 * elements);
         }
 
         // the scratch of rotate_hoisted_sum, in bytes: the accumulators T[2][count][M][N], whatever G is
@@ -509,10 +440,10 @@ namespace gpuntt
             const size_t poly = (static_cast<size_t>(count) << n_power) * sizeof(T);
             KsBsgsScratch s{};
             s.u = 0;
-            s.v = s.u + ks_align(poly * M * 2 * n1);
-            s.t = s.v + ks_align(poly * M * 2 * n2);
-            s.a2 = s.t + ks_align(poly * L * n2);
-            s.total = s.a2 + ks_align(poly * M * D * n2);
+            s.v = s.u + rns_align(poly * M * 2 * n1);
+            s.t = s.v + rns_align(poly * M * 2 * n2);
+            s.a2 = s.t + rns_align(poly * L * n2);
+            s.total = s.a2 + rns_align(poly * M * D * n2);
             return s;
         }
     } // namespace
@@ -546,11 +477,11 @@ namespace gpuntt
             unsigned nt = kern::KS_NT;
             while (nt > 64 && 2 * static_cast<size_t>(L) * nt * sizeof(T) > kern::KS_LDS)
                 nt /= 2;
-            const unsigned long long tiles = (total + nt - 1) / nt;
-            if (tiles * nt > 0xFFFFFFFFull) // HIP caps a launch at 2^32 - 1 work-items per dimension
-                throw std::invalid_argument("Invalid count!");
-            const int MP = ks_padded(M), pairs = D * (MP / kern::KS_KB);
-            const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(ks_split(tiles, pairs)));
+            const unsigned long long tiles = column_tiles(total, nt, "Invalid count!");
+            const int MP = bc_padded(M), pairs = D * (MP / kern::BC_KB);
+            // workgroups per column tile over the (digit, block) pairs: DESIGN.md 3.12
+            const int split = host::rns_split(tiles, pairs, host::g_ks_split.load(std::memory_order_relaxed));
+            const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(split));
             const size_t lds = 2 * static_cast<size_t>(L) * nt * sizeof(T);
             const T* consts = reinterpret_cast<const T*>(ws + lay.up);
             const unsigned long long digit_stride = total * static_cast<unsigned>(M);
@@ -580,10 +511,8 @@ namespace gpuntt
         {
             const unsigned long long poly = 1ull << n, full = static_cast<unsigned long long>(limbs) << n;
             const unsigned long long total = static_cast<unsigned long long>(stacks) << n;
-            const unsigned long long tiles = (total + kern::BC_NT - 1) / kern::BC_NT;
-            if (tiles * kern::BC_NT > 0xFFFFFFFFull) // HIP caps a launch at 2^32 - 1 work-items per dimension
-                throw std::invalid_argument("Invalid stacks!");
-            const int KP = (out_count + kern::BC_KB - 1) / kern::BC_KB * kern::BC_KB;
+            const unsigned long long tiles = column_tiles(total, kern::BC_NT, "Invalid stacks!");
+            const int KP = bc_padded(out_count);
             const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(host::bc_ksplit(tiles, out_count)));
             const size_t lds = static_cast<size_t>(in_count) * kern::BC_NT * sizeof(T);
             GPUNTT_LAUNCH((kern::base_convert<T, true, true, true>), grid, dim3(kern::BC_NT), lds, stream,
@@ -613,7 +542,7 @@ namespace gpuntt
             need_rescale();
             if (stacks < 0)
                 throw std::invalid_argument("Invalid stacks!");
-            return ks_align((static_cast<size_t>(stacks) << n) * R * sizeof(T));
+            return rns_align((static_cast<size_t>(stacks) << n) * R * sizeof(T));
         }
 
         // x: T[stacks][L][N], out: T[stacks][Lk][N]; the scratch (ntt_form only): T[stacks][R][N]
@@ -637,16 +566,14 @@ namespace gpuntt
             if (stacks == 0)
                 return;
             const std::uint64_t cols = static_cast<std::uint64_t>(stacks) << n;
-            if (ks_overlap(scratch, scratch_bytes, x, cols * L * sizeof(T)))
+            if (rns_overlap(scratch, scratch_bytes, x, cols * L * sizeof(T)))
                 throw std::invalid_argument("The scratch overlaps an operand!");
-            if (ks_overlap(scratch, scratch_bytes, out, cols * Lk * sizeof(T)))
+            if (rns_overlap(scratch, scratch_bytes, out, cols * Lk * sizeof(T)))
                 throw std::invalid_argument("The scratch overlaps out!");
             // every limit before the first launch: the batches of the transforms are ints, the grids as their launches check
             if (static_cast<unsigned long long>(stacks) * static_cast<unsigned>(L) > 0x7FFFFFFFull)
                 throw std::invalid_argument("Invalid stacks!");
-            const unsigned long long tiles = (cols + kern::BC_NT - 1) / kern::BC_NT;
-            if (tiles * kern::BC_NT > 0xFFFFFFFFull)
-                throw std::invalid_argument("Invalid stacks!");
+            const unsigned long long tiles = column_tiles(cols, kern::BC_NT, "Invalid stacks!");
             T* dropped = static_cast<T*>(scratch);
             const T* image = reinterpret_cast<const T*>(ws + lay.rs);
             const kern::RsOffsets sub{rs_off.p, rs_off.onep, rs_off.qinv, rs_off.qinvp};
@@ -656,7 +583,7 @@ namespace gpuntt
             host::rescale_gather_launch<T>(x, dropped, dropped_mods, stacks, L, R, n, true, stream);
             ntt_drop_i->execute(dropped, dropped, stacks * R, stream);
             // the dense centred conversion {dropped q} -> {kept q}, no division: conv_j in coefficient form
-            const int KP = (Lk + kern::BC_KB - 1) / kern::BC_KB * kern::BC_KB;
+            const int KP = bc_padded(Lk);
             const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(host::bc_ksplit(tiles, Lk)));
             GPUNTT_LAUNCH((kern::base_convert<T, true, false, false>), grid, dim3(kern::BC_NT),
                           static_cast<size_t>(R) * kern::BC_NT * sizeof(T), stream, dropped, out, out, image, rs_off, R, Lk,
@@ -683,13 +610,13 @@ namespace gpuntt
             const T* coeff = c_in;
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
             const std::uint64_t c_bytes = cols * L * sizeof(T), a_bytes = cols * M * D * sizeof(T);
-            if (ks_overlap(c_in, c_bytes, a, a_bytes)) // every refusal comes before the first launch
+            if (rns_overlap(c_in, c_bytes, a, a_bytes)) // every refusal comes before the first launch
                 throw std::invalid_argument("ModUp input and output overlap!");
             if (input_ntt)
             {
                 T* tmp = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.c_coeff);
-                if (ks_overlap(tmp, s.inner_out - s.c_coeff, a, a_bytes) ||
-                    ks_overlap(tmp, s.inner_out - s.c_coeff, c_in, c_bytes))
+                if (rns_overlap(tmp, s.inner_out - s.c_coeff, a, a_bytes) ||
+                    rns_overlap(tmp, s.inner_out - s.c_coeff, c_in, c_bytes))
                     throw std::invalid_argument("The scratch overlaps an operand!");
                 ntt_q_i->execute(c_in, tmp, count * L, stream);
                 coeff = tmp;
@@ -709,7 +636,7 @@ namespace gpuntt
                 return;
             T* acc = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.inner_out);
             const std::uint64_t acc_bytes = (static_cast<std::uint64_t>(count) << n) * M * C * sizeof(T);
-            if (ks_overlap(acc, acc_bytes, out, (static_cast<std::uint64_t>(count) << n) * L * C * sizeof(T)))
+            if (rns_overlap(acc, acc_bytes, out, (static_cast<std::uint64_t>(count) << n) * L * C * sizeof(T)))
                 throw std::invalid_argument("The scratch overlaps out!");
             // a or key overlapping the accumulators in the scratch: refused by the inner product's own check of its
             // output against its inputs, before its launch -- the first of this call
@@ -772,23 +699,22 @@ namespace gpuntt
             const std::uint64_t weight_bytes = (static_cast<std::uint64_t>(M) << n) * sizeof(T);
             for (const auto& w : {std::pair<const void*, std::uint64_t>{out, out_bytes}, {scratch, acc_bytes}})
             {
-                bool hit = ks_overlap(w.first, w.second, a, a_bytes) ||
-                           (c0 != nullptr && ks_overlap(w.first, w.second, c0, c0_bytes));
+                bool hit = rns_overlap(w.first, w.second, a, a_bytes) ||
+                           (c0 != nullptr && rns_overlap(w.first, w.second, c0, c0_bytes));
                 for (int g = 0; g < G; g++)
-                    hit = hit || ks_overlap(w.first, w.second, keys[g], key_bytes) ||
+                    hit = hit || rns_overlap(w.first, w.second, keys[g], key_bytes) ||
                           (weights != nullptr && weights[g] != nullptr &&
-                           ks_overlap(w.first, w.second, weights[g], weight_bytes));
+                           rns_overlap(w.first, w.second, weights[g], weight_bytes));
                 if (hit)
                     throw std::invalid_argument("out or the scratch overlaps an operand!");
             }
-            if (ks_overlap(out, out_bytes, scratch, acc_bytes))
+            if (rns_overlap(out, out_bytes, scratch, acc_bytes))
                 throw std::invalid_argument("The scratch overlaps out!");
             const unsigned long long stacks = 2ull * static_cast<unsigned>(groups) * static_cast<unsigned>(count);
             if (stacks * static_cast<unsigned>(M) > 0x7FFFFFFFull) // the batch of the transforms is an int
                 throw std::invalid_argument("Invalid count!");
             // mod_down's own grid limit, checked before the first launch
-            if ((((stacks << n) + kern::BC_NT - 1) / kern::BC_NT) * kern::BC_NT > 0xFFFFFFFFull)
-                throw std::invalid_argument("Invalid count!");
+            (void) column_tiles(stacks << n, kern::BC_NT, "Invalid count!");
             return static_cast<int>(stacks);
         }
 
@@ -896,19 +822,19 @@ namespace gpuntt
             const std::uint64_t weight_bytes = (static_cast<std::uint64_t>(M) << n) * sizeof(T);
             for (const auto& w : {std::pair<const void*, std::uint64_t>{out, out_bytes}, {scratch, s.total}})
             {
-                bool hit = ks_overlap(w.first, w.second, a, a_bytes) ||
-                           (c0 != nullptr && ks_overlap(w.first, w.second, c0, c_bytes)) ||
-                           (c1 != nullptr && ks_overlap(w.first, w.second, c1, c_bytes));
+                bool hit = rns_overlap(w.first, w.second, a, a_bytes) ||
+                           (c0 != nullptr && rns_overlap(w.first, w.second, c0, c_bytes)) ||
+                           (c1 != nullptr && rns_overlap(w.first, w.second, c1, c_bytes));
                 for (int i = 0; i < n1k; i++)
-                    hit = hit || ks_overlap(w.first, w.second, bargs.key[i], key_bytes);
+                    hit = hit || rns_overlap(w.first, w.second, bargs.key[i], key_bytes);
                 for (int i = 0; i < n2k; i++)
-                    hit = hit || ks_overlap(w.first, w.second, gargs.key[i], key_bytes);
+                    hit = hit || rns_overlap(w.first, w.second, gargs.key[i], key_bytes);
                 for (int i = 0; i < n1 * n2; i++)
-                    hit = hit || (wa.w[i] != nullptr && ks_overlap(w.first, w.second, wa.w[i], weight_bytes));
+                    hit = hit || (wa.w[i] != nullptr && rns_overlap(w.first, w.second, wa.w[i], weight_bytes));
                 if (hit)
                     throw std::invalid_argument("out or the scratch overlaps an operand!");
             }
-            if (ks_overlap(out, out_bytes, scratch, s.total))
+            if (rns_overlap(out, out_bytes, scratch, s.total))
                 throw std::invalid_argument("The scratch overlaps out!");
             // every limit before the first launch, at n2 keyed giant steps whatever their number is: the batches of the
             // transforms are ints; the grids of mod_up, mod_down and the five kernels of hoisted_rotation.hip launch at
@@ -970,21 +896,20 @@ namespace gpuntt
             const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
             for (const auto& op : {std::pair<const void*, std::uint64_t>{x, ct_bytes}, {y, ct_bytes}, {key, key_bytes}})
             {
-                if (ks_overlap(scratch, s.total, op.first, op.second))
+                if (rns_overlap(scratch, s.total, op.first, op.second))
                     throw std::invalid_argument("out or the scratch overlaps an operand!");
                 // out may be exactly x or exactly y: the last read of both (inner_product_tensor) precedes mod_down's
                 // first write on the stream.  Any other overlap is refused
-                if (ks_overlap(out, out_bytes, op.first, op.second) && (op.first == key || op.first != out))
+                if (rns_overlap(out, out_bytes, op.first, op.second) && (op.first == key || op.first != out))
                     throw std::invalid_argument("out or the scratch overlaps an operand!");
             }
-            if (ks_overlap(out, out_bytes, scratch, s.total))
+            if (rns_overlap(out, out_bytes, scratch, s.total))
                 throw std::invalid_argument("The scratch overlaps out!");
             // the batches of the transforms are ints; the grids of mod_up and mod_down: as their own launches check
             if (static_cast<unsigned long long>(D) * static_cast<unsigned>(count) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
                 throw std::invalid_argument("Invalid count!");
-            if (((cols + kern::KS_NT - 1) / kern::KS_NT) * kern::KS_NT > 0xFFFFFFFFull ||
-                ((2 * cols + kern::BC_NT - 1) / kern::BC_NT) * kern::BC_NT > 0xFFFFFFFFull)
-                throw std::invalid_argument("Invalid count!");
+            (void) column_tiles(cols, kern::KS_NT, "Invalid count!");
+            (void) column_tiles(2 * cols, kern::BC_NT, "Invalid count!");
             kern::RelinArgs<T> args{};
             for (int m = 0; m < M; m++)
                 args.limbs.v[m] = static_cast<unsigned char>(limbs[m]);
@@ -1038,22 +963,21 @@ namespace gpuntt
             const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
             // out may be exactly any x[t] or y[t]: the last read of them (inner_product_tensor_sum) precedes mod_down's
             // first write on the stream.  Any other overlap is refused
-            if (ks_overlap(scratch, s.total, key, key_bytes) || ks_overlap(out, out_bytes, key, key_bytes))
+            if (rns_overlap(scratch, s.total, key, key_bytes) || rns_overlap(out, out_bytes, key, key_bytes))
                 throw std::invalid_argument("out or the scratch overlaps an operand!");
             for (int t = 0; t < 2 * terms; t++)
             {
                 const T* op = t < terms ? xs[t] : ys[t - terms];
-                if (ks_overlap(scratch, s.total, op, ct_bytes) || (ks_overlap(out, out_bytes, op, ct_bytes) && op != out))
+                if (rns_overlap(scratch, s.total, op, ct_bytes) || (rns_overlap(out, out_bytes, op, ct_bytes) && op != out))
                     throw std::invalid_argument("out or the scratch overlaps an operand!");
             }
-            if (ks_overlap(out, out_bytes, scratch, s.total))
+            if (rns_overlap(out, out_bytes, scratch, s.total))
                 throw std::invalid_argument("The scratch overlaps out!");
             // the batches of the transforms are ints; the grids of mod_up and mod_down: as their own launches check
             if (static_cast<unsigned long long>(D) * static_cast<unsigned>(count) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
                 throw std::invalid_argument("Invalid count!");
-            if (((cols + kern::KS_NT - 1) / kern::KS_NT) * kern::KS_NT > 0xFFFFFFFFull ||
-                ((2 * cols + kern::BC_NT - 1) / kern::BC_NT) * kern::BC_NT > 0xFFFFFFFFull)
-                throw std::invalid_argument("Invalid count!");
+            (void) column_tiles(cols, kern::KS_NT, "Invalid count!");
+            (void) column_tiles(2 * cols, kern::BC_NT, "Invalid count!");
             for (int m = 0; m < M; m++)
                 args.r.limbs.v[m] = static_cast<unsigned char>(limbs[m]);
             for (int j = 0; j < L; j++)
@@ -1092,7 +1016,7 @@ namespace gpuntt
     size_t KeySwitchPlan<T>::scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count, int components)
     {
         ks_check_counts(q_count, p_count, alpha);
-        ks_check_n_power(n_power);
+        rns_check_n_power(n_power);
         return ks_scratch<T>(q_count, q_count + p_count, ks_digits(q_count, alpha), n_power, count, components).total;
     }
 
@@ -1101,7 +1025,7 @@ namespace gpuntt
                                                    int elements)
     {
         ks_check_counts(q_count, p_count, alpha);
-        ks_check_n_power(n_power);
+        rns_check_n_power(n_power);
         return ks_hoisted_scratch<T>(q_count + p_count, n_power, count, elements);
     }
 
@@ -1109,7 +1033,7 @@ namespace gpuntt
     size_t KeySwitchPlan<T>::hoisted_sum_scratch_bytes(int q_count, int p_count, int alpha, int n_power, int count)
     {
         ks_check_counts(q_count, p_count, alpha);
-        ks_check_n_power(n_power);
+        rns_check_n_power(n_power);
         return ks_hoisted_sum_scratch<T>(q_count + p_count, n_power, count);
     }
 
@@ -1118,7 +1042,7 @@ namespace gpuntt
                                                 int n2)
     {
         ks_check_counts(q_count, p_count, alpha);
-        ks_check_n_power(n_power);
+        rns_check_n_power(n_power);
         return ks_bsgs_scratch<T>(q_count, q_count + p_count, ks_digits(q_count, alpha > q_count ? q_count : alpha),
                                   n_power, count, n1, n2)
             .total;
@@ -1383,8 +1307,8 @@ namespace gpuntt
             throw std::invalid_argument("null pointer argument");
         T* a = reinterpret_cast<T*>(static_cast<char*>(scratch_device) + s.a);
         if (device_c_in != nullptr && device_out != nullptr && count > 0 &&
-            (ks_overlap(scratch_device, s.total, device_c_in, (static_cast<size_t>(count) << p_->n) * p_->L * sizeof(T)) ||
-             ks_overlap(scratch_device, s.total, device_out,
+            (rns_overlap(scratch_device, s.total, device_c_in, (static_cast<size_t>(count) << p_->n) * p_->L * sizeof(T)) ||
+             rns_overlap(scratch_device, s.total, device_out,
                         (static_cast<size_t>(count) << p_->n) * p_->L * components * sizeof(T))))
             throw std::invalid_argument("The scratch overlaps an operand!");
         p_->decompose(device_c_in, a, count, input_ntt, scratch_device, stream);
@@ -1455,33 +1379,6 @@ namespace gpuntt
 
     namespace
     {
-        // base_conversion.cuh's formulas for one column: x[i] (any words) of the input base of `c` -> conv[j], every
-        // step reduced with %
-        template <typename T>
-        void ks_ref_convert(const host::BcHostConsts& c, const std::uint64_t* x, bool centred, std::uint64_t* conv)
-        {
-            constexpr int W = static_cast<int>(8 * sizeof(T));
-            std::uint64_t y[BASECONV_MAX_COUNT];
-            U128 zsum = static_cast<U128>(1) << (W - 1);
-            for (int i = 0; i < c.L; i++)
-            {
-                y[i] = static_cast<std::uint64_t>(static_cast<U128>(x[i] % c.q[i]) * c.w[i] % c.q[i]);
-                const int sh = static_cast<int>(c.blen[i]) - 1;
-                const U128 z = c.recip[i] != 0 ? (static_cast<U128>(y[i]) * c.recip[i]) >> sh
-                                               : static_cast<U128>(y[i]) << (W - sh);
-                zsum += static_cast<T>(z);
-            }
-            const std::uint64_t v = centred ? static_cast<std::uint64_t>(static_cast<T>(zsum >> W)) : 0;
-            for (int j = 0; j < c.K; j++)
-            {
-                const U128 p = c.p[j];
-                U128 s = static_cast<U128>(v % c.p[j]) * c.negq[j] % p;
-                for (int i = 0; i < c.L; i++)
-                    s = (s + static_cast<U128>(y[i] % c.p[j]) * c.matrix[static_cast<size_t>(i) * c.K + j]) % p;
-                conv[j] = static_cast<std::uint64_t>(s);
-            }
-        }
-
         // convert_and_divide (centred) inside stacks of `limbs` limbs: the input base of `c` is limbs c.K .. c.K + c.L - 1
         // of every stack, its output base limbs 0 .. c.K - 1; out: T[stacks][c.K][N]
         template <typename T>
@@ -1495,7 +1392,7 @@ namespace gpuntt
                     const T* src = x_host + static_cast<size_t>(s) * limbs * n + j;
                     for (int k = 0; k < c.L; k++)
                         x[k] = src[(c.K + k) * n];
-                    ks_ref_convert<T>(c, x, true, conv);
+                    host::bc_ref_convert<T>(c, x, true, conv);
                     for (int i = 0; i < c.K; i++)
                     {
                         const std::uint64_t q = c.p[i];
@@ -1526,7 +1423,7 @@ namespace gpuntt
                     T* dst = a_host + (static_cast<size_t>(d) * count + r) * M * n + j;
                     for (int i = h.lo(d); i < h.hi(d); i++)
                         x[i - h.lo(d)] = src[i * n];
-                    ks_ref_convert<T>(h.up[d], x, mode == BaseConvMode::centred, conv);
+                    host::bc_ref_convert<T>(h.up[d], x, mode == BaseConvMode::centred, conv);
                     for (int m = 0; m < M; m++)
                         dst[m * n] = (m >= h.lo(d) && m < h.hi(d)) ? static_cast<T>(src[m * n] % h.mod[m])
                                                                    : static_cast<T>(conv[ks_column(h, d, m)]);

@@ -21,6 +21,9 @@ namespace gpuntt
             using type = unsigned __int128;
         };
 
+        // (plain C++, so that the kernels' text also compiles for the host: the emulators of tests/cpp)
+        __device__ __forceinline__ constexpr int ip_min(int a, int b) { return a < b ? a : b; }
+
         __device__ __forceinline__ Data32 rns_mulhi(Data32 a, Data32 b) { return __umulhi(a, b); }
         __device__ __forceinline__ Data64 rns_mulhi(Data64 a, Data64 b) { return __umul64hi(a, b); }
 

@@ -17,8 +17,6 @@
 #include <thread>
 #include <vector>
 
-using std::min; // base_conversion_internal.hpp's kernel names it unqualified
-
 #include "bfv_multiply_internal.hpp"
 #include "relinearize_internal.hpp"
 
