@@ -111,7 +111,8 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "innerprod_plan_owns_workspace", "innerprod_plan_destroy", "innerprod_constants",
               "innerprod_reference",
               "keyswitch_plan_workspace_bytes", "keyswitch_plan_scratch_bytes", "keyswitch_plan_create",
-              "keyswitch_plan_mod_up", "keyswitch_plan_mod_down", "keyswitch_plan_decompose",
+              "keyswitch_plan_mod_up", "keyswitch_plan_mod_down", "keyswitch_plan_mod_down_add",
+              "keyswitch_plan_relinearize", "keyswitch_plan_decompose",
               "keyswitch_plan_switch_digits", "keyswitch_plan_apply", "keyswitch_plan_hoisted_scratch_bytes",
               "keyswitch_plan_rotate_hoisted", "keyswitch_plan_hoisted_sum_scratch_bytes",
               "keyswitch_plan_rotate_hoisted_sum", "keyswitch_plan_multiply_relinearize",
@@ -127,7 +128,8 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "keyswitch_plan_bsgs_scratch_bytes", "keyswitch_plan_linear_transform_bsgs",
               "keyswitch_plan_linear_transform_bsgs_rescale",
               "bfv_plan_workspace_bytes", "bfv_plan_scratch_bytes", "bfv_plan_create", "bfv_plan_extend",
-              "bfv_plan_scale_round", "bfv_plan_multiply", "bfv_plan_owns_workspace", "bfv_plan_destroy",
+              "bfv_plan_scale_round", "bfv_plan_multiply", "bfv_plan_multiply_relinearize", "bfv_plan_owns_workspace",
+              "bfv_plan_destroy",
               "bfv_constants", "bfv_reference_extend", "bfv_reference_scale_round")
     for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option", "gpuntt_galois_element_u32",
                                 "gpuntt_automorphism_index_map"]
@@ -1175,6 +1177,18 @@ class KeySwitchPlan:
         fn = getattr(load_library(), "gpuntt_keyswitch_plan_mod_down_u%d" % self.bits)
         _check(fn(self._h, _ptr(device_x), _ptr(device_out), int(stacks), _stream(stream)))
 
+    def mod_down_add(self, device_x, device_addend, device_out, stacks, stream=None):
+        """device_x T[stacks][M][N], device_addend T[stacks][L][N] (any words; it may be device_out itself) ->
+        device_out T[stacks][L][N] = (mod_down(x) + addend) mod q; one kernel launch"""
+        if device_x is None or device_addend is None or device_out is None:
+            raise ValueError("null pointer argument")
+        cols = self._cols(stacks)
+        self._check_buffers(((device_x, cols * self.mod_count, "x (stacks x M x N)"),
+                             (device_addend, cols * self.q_count, "addend (stacks x L x N)"),
+                             (device_out, cols * self.q_count, "out (stacks x L x N)")))
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_mod_down_add_u%d" % self.bits)
+        _check(fn(self._h, _ptr(device_x), _ptr(device_addend), _ptr(device_out), int(stacks), _stream(stream)))
+
     def decompose(self, device_c_in, device_a, count, input_ntt=False, scratch=None, stream=None):
         cols = self._cols(count)
         self._check_buffers(((device_c_in, cols * self.q_count, "c_in (count x L x N)"),
@@ -1309,6 +1323,25 @@ class KeySwitchPlan:
         fn = self._pipeline_fn("multiply_relinearize", _rescale)
         _check(fn(self._h, _ptr(x), _ptr(y), _ptr(key), _ptr(out), int(count), int(bool(output_ntt)), _ptr(scratch),
                   _stream(stream)))
+
+    def relinearize(self, c01, c2, key, out, count, input_ntt, output_ntt, scratch, stream=None):
+        """The key switch of `count` three-component ciphertexts: c01 T[2][count][L][N] (any words), c2 T[count][L][N]
+        (a contiguous T[3][count][L][N] is c2 = a view of it from word 2 x count x L x N), key the relinearization key,
+        out T[2][count][L][N] (may be exactly c01); scratch: at least scratch_bytes(count, 2) bytes, 256-byte aligned.
+        out equals apply on c2 plus c01 modulo q, word for word (key_switch.cuh)."""
+        if c01 is None or c2 is None or key is None or out is None or scratch is None:
+            raise ValueError("null pointer argument")
+        cols = self._cols(count)
+        self._check_buffers(((c01, cols * self.q_count * 2, "c01 (2 x count x L x N)"),
+                             (c2, cols * self.q_count, "c2 (count x L x N)"),
+                             (key, self._key_words(2) if cols else 0, "key (D x 2 x key_mod_count x N)"),
+                             (out, cols * self.q_count * 2, "out (2 x count x L x N)")))
+        _require_gpu(scratch)
+        if int(count) >= 0 and scratch.numel() * scratch.element_size() < self.scratch_bytes(count, 2):
+            raise ValueError("scratch holds fewer than scratch_bytes(count, 2) bytes")
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_relinearize_u%d" % self.bits)
+        _check(fn(self._h, _ptr(c01), _ptr(c2), _ptr(key), _ptr(out), int(count), int(bool(input_ntt)),
+                  int(bool(output_ntt)), _ptr(scratch), _stream(stream)))
 
     def multiply_relinearize_sum(self, xs, ys, key, out, count, output_ntt, scratch, stream=None, _rescale=False):
         """sum_t xs[t] * ys[t] over T = len(xs) pairs of two-component ciphertexts with ONE key switch and ONE ModDown
@@ -1631,6 +1664,31 @@ class BfvMultiplyPlan:
         fn = getattr(load_library(), "gpuntt_bfv_plan_multiply_u%d" % self.bits)
         _check(fn(self._h, _ptr(x), _ptr(y), _ptr(out), int(count), int(bool(input_ntt)), int(bool(output_ntt)),
                   _ptr(scratch), _stream(stream)))
+
+    def multiply_relinearize(self, x, y, key_switch, key, out, count, input_ntt=False, output_ntt=False, scratch=None,
+                             key_switch_scratch=None, stream=None):
+        """BFV ct x ct in one call: x, y T[2][count][L][N] (y may be x) -> out T[2][count][L][N], the product
+        relinearized by the KeySwitchPlan `key_switch` (the same q-base, ring and reduction polynomial, or ValueError
+        "The key-switching plan does not match!") under `key`; out may be x or y itself.  scratch: at least
+        scratch_bytes(count) bytes; key_switch_scratch: at least key_switch.scratch_bytes(count, 2) bytes; both 256-byte
+        aligned.  out equals multiply(output_ntt=False) then key_switch.relinearize word for word (bfv_multiply.cuh)."""
+        if not isinstance(key_switch, KeySwitchPlan) or key_switch.bits != self.bits:
+            raise ValueError("key_switch is a KeySwitchPlan of the same word width")
+        cols = self._cols(count)
+        self._check_buffers(((x, cols * self.q_count * 2, "x (2 x count x L x N)"),
+                             (y, cols * self.q_count * 2, "y (2 x count x L x N)"),
+                             (key, key_switch._key_words(2) if cols else 0, "key (D x 2 x key_mod_count x N)"),
+                             (out, cols * self.q_count * 2, "out (2 x count x L x N)")))
+        _require_gpu(scratch, key_switch_scratch)
+        if scratch is not None and int(count) > 0 and \
+                scratch.numel() * scratch.element_size() < self.scratch_bytes(count):
+            raise ValueError("scratch holds fewer than scratch_bytes(count) bytes")
+        if key_switch_scratch is not None and int(count) > 0 and \
+                key_switch_scratch.numel() * key_switch_scratch.element_size() < key_switch.scratch_bytes(count, 2):
+            raise ValueError("key_switch_scratch holds fewer than key_switch.scratch_bytes(count, 2) bytes")
+        fn = getattr(load_library(), "gpuntt_bfv_plan_multiply_relinearize_u%d" % self.bits)
+        _check(fn(self._h, _ptr(x), _ptr(y), key_switch._h, _ptr(key), _ptr(out), int(count), int(bool(input_ntt)),
+                  int(bool(output_ntt)), _ptr(scratch), _ptr(key_switch_scratch), _stream(stream)))
 
     def close(self):
         if self._h:

@@ -1,6 +1,6 @@
 // base_conversion_internal.hpp -- what key_switch.hip and bfv_multiply.hip share with base_conversion.hip: the conversion
 // unit every conversion kernel of the library is made of (bc_z, bc_block_mac, bc_fold, with the proofs of their bounds),
-// the kernel base_convert itself, the constants of one pair of bases in exact integers, their image in a workspace, the
+// the kernel base_convert itself and mod_down_add, its strided division with an addend epilogue, the constants of one pair of bases in exact integers, their image in a workspace, the
 // exact-integer column reference and the output-split policy.  Not a public header.
 #pragma once
 
@@ -163,11 +163,26 @@ namespace gpuntt
         {
         };
 
-        template <typename T, bool CENTRED, bool DIVIDE, bool STRIDED = false>
-        __global__ __launch_bounds__(BC_NT) void base_convert(const T* __restrict__ in, const T* c_in, T* out,
-                                                              const T* __restrict__ consts, BcOffsets off,
-                                                              int L, int K, int KP, int n_power,
-                                                              unsigned long long total, BcStrides<STRIDED> strides)
+        // ADD: an addend epilogue -- out = (the conversion's word + (addend mod p_j)) mod p_j, canonical, with addend laid
+        // out as `out` is, so a lane reads its addend word at the index it then writes: addend may be exactly out.  Any
+        // word is accepted: one Shoup product against the companion of 1 makes it canonical, and two canonical words of a
+        // modulus below 2^(W-1) add without a carry.  A compile-time switch like STRIDED, and for the same reason: the
+        // argument is empty where there is no addend, and the kernels without one keep their registers
+        template <typename T, bool ADD> struct BcAddend
+        {
+            const T* words;
+        };
+        template <typename T> struct BcAddend<T, false>
+        {
+        };
+
+        // The body of every launch of this unit: base_convert below, and mod_down_add, which is the strided centred
+        // division with the addend epilogue under a name of its own, so that the launch log tells the two apart
+        template <typename T, bool CENTRED, bool DIVIDE, bool STRIDED, bool ADD>
+        __device__ __forceinline__ void bc_convert_body(const T* __restrict__ in, const T* c_in, T* out,
+                                                        const T* __restrict__ consts, const BcOffsets& off, int L, int K,
+                                                        int KP, int n_power, unsigned long long total,
+                                                        const BcStrides<STRIDED>& strides, const BcAddend<T, ADD>& addend)
         {
             // the plan refuses an empty input base.  Said here because with bc_block_mac inlined the compiler otherwise
             // keeps an empty-sum path through every output block and zeroes the accumulators on both: 12 VALU
@@ -229,10 +244,37 @@ namespace gpuntt
                             const T d = cj >= r ? cj - r : cj + (p - r);
                             r = rns_shoup<T>(d, k.qinv[j], k.qinvp[j], p);
                         }
+                        if constexpr (ADD)
+                        {
+                            r += rns_shoup<T>(addend.words[o], T(1), k.onep[j], p);
+                            r = r >= p ? r - p : r;
+                        }
                         out[o] = r;
                     }
                 }
             }
+        }
+
+        template <typename T, bool CENTRED, bool DIVIDE, bool STRIDED = false>
+        __global__ __launch_bounds__(BC_NT) void base_convert(const T* __restrict__ in, const T* c_in, T* out,
+                                                              const T* __restrict__ consts, BcOffsets off,
+                                                              int L, int K, int KP, int n_power,
+                                                              unsigned long long total, BcStrides<STRIDED> strides)
+        {
+            bc_convert_body<T, CENTRED, DIVIDE, STRIDED, false>(in, c_in, out, consts, off, L, K, KP, n_power, total,
+                                                                strides, BcAddend<T, false>{});
+        }
+
+        // KeySwitchPlan::mod_down_add: base_convert<T, centred, divide, STRIDED> with the addend epilogue.  addend:
+        // T[stacks][K][N], dense like out; it may be exactly out and must not overlap anything else (the host refuses)
+        template <typename T>
+        __global__ __launch_bounds__(BC_NT) void mod_down_add(const T* __restrict__ in, const T* c_in, const T* addend,
+                                                              T* out, const T* __restrict__ consts, BcOffsets off, int L,
+                                                              int K, int KP, int n_power, unsigned long long total,
+                                                              BcStrides<true> strides)
+        {
+            bc_convert_body<T, true, true, true, true>(in, c_in, out, consts, off, L, K, KP, n_power, total, strides,
+                                                       BcAddend<T, true>{addend});
         }
     } // namespace kern
 

@@ -414,6 +414,8 @@ namespace gpuntt
     {
         int L = 0, K = 0, M = 0, n = 0;
         T t = 0;
+        std::vector<Modulus<T>> moduli; // [M] the full base as the caller gave it: modulus(m)
+        ReductionPolynomial poly = ReductionPolynomial::X_N_plus;
         char* ws = nullptr;
         bool owns = false;
         BfvLayout lay{};
@@ -450,8 +452,9 @@ namespace gpuntt
             GPUNTT_HIP_CHECK(hipGetLastError());
         }
 
-        void multiply(const T* x, const T* y, T* out, int count, bool input_ntt, bool output_ntt, void* scratch,
-                      hipStream_t stream) const
+        // What multiply and multiply_relinearize share up to the first launch: every refusal of multiply, with `comps`
+        // components at out.  Returns false when count is 0 and nothing is to be launched
+        bool product_check(const T* x, const T* y, const T* out, int comps, int count, void* scratch) const
         {
             if (!ntt_full_f)
                 throw std::invalid_argument("The plan was built without transform tables!");
@@ -461,9 +464,9 @@ namespace gpuntt
             if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
                 throw std::invalid_argument("The scratch is not 256-byte aligned!");
             if (count == 0)
-                return;
+                return false;
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
-            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T), out_bytes = cols * L * 3 * sizeof(T);
+            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T), out_bytes = cols * L * comps * sizeof(T);
             for (const T* op : {x, y})
             {
                 if (rns_overlap(scratch, s.total, op, ct_bytes))
@@ -481,11 +484,21 @@ namespace gpuntt
             (void) column_tiles((3ull * static_cast<unsigned>(count)) << n, kern::BC_NT, "Invalid stacks!");
             const bool square = x == y;
             T* e = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.e);
+            bfv_tensor_launch<T>(e, square ? e : e + cols * M * 2, e, fold(), count, M, n, false, nullptr);
+            return true;
+        }
+
+        // steps 1 to 5 of multiply: the three tensor components in coefficient form over the full base, T[3][count][M][N]
+        // at the start of the scratch
+        T* product(const T* x, const T* y, int count, bool input_ntt, void* scratch, hipStream_t stream) const
+        {
+            const BfvScratch s = bfv_scratch<T>(L, M, n, count);
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const bool square = x == y;
+            T* e = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.e);
             T* coeff = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.coeff);
             T* xe = e;
             T* ye = square ? e : e + cols * M * 2;
-            bfv_tensor_launch<T>(xe, ye, e, fold(), count, M, n, false, stream);
-
             auto bring = [&](const T* op, T* full) { // steps 1 and 2 for one operand
                 if (input_ntt)
                     ntt_q_i->execute(op, coeff, 2 * count * L, stream);
@@ -497,9 +510,63 @@ namespace gpuntt
             ntt_full_f->execute(e, e, (square ? 2 : 4) * count * M, stream);
             bfv_tensor_launch<T>(xe, ye, e, fold(), count, M, n, true, stream);
             ntt_full_i->execute(e, e, 3 * count * M, stream);
+            return e;
+        }
+
+        void multiply(const T* x, const T* y, T* out, int count, bool input_ntt, bool output_ntt, void* scratch,
+                      hipStream_t stream) const
+        {
+            if (!product_check(x, y, out, 3, count, scratch))
+                return;
+            const T* e = product(x, y, count, input_ntt, scratch, stream);
             scale_round(e, out, 3 * count, stream);
             if (output_ntt)
                 ntt_q_f->execute(out, out, 3 * count * L, stream);
+        }
+
+        void multiply_relinearize(const T* x, const T* y, const KeySwitchPlan<T>& ks, const T* key, T* out, int count,
+                                  bool input_ntt, bool output_ntt, void* scratch, void* ks_scratch,
+                                  hipStream_t stream) const
+        {
+            bool match = ntt_full_f && ks.has_transforms() && ks.q_count() == L && ks.n_power() == n &&
+                         ks.reduction_poly() == poly;
+            for (int m = 0; match && m < L; m++)
+                match = ks.modulus(m).value == moduli[m].value;
+            if (!match)
+                throw std::invalid_argument("The key-switching plan does not match!");
+            if (key == nullptr || ks_scratch == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            const size_t ks_bytes = ks.scratch_bytes(count, 2); // checks count
+            if (reinterpret_cast<uintptr_t>(ks_scratch) % 256 != 0)
+                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            if (!product_check(x, y, out, 2, count, scratch))
+                return;
+            const BfvScratch s = bfv_scratch<T>(L, M, n, count);
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T);
+            const std::uint64_t key_bytes =
+                ((static_cast<std::uint64_t>(ks.digits()) * 2 * ks.key_mod_count()) << n) * sizeof(T);
+            if (rns_overlap(ks_scratch, ks_bytes, x, ct_bytes) || rns_overlap(ks_scratch, ks_bytes, y, ct_bytes) ||
+                rns_overlap(ks_scratch, ks_bytes, key, key_bytes) || rns_overlap(scratch, s.total, key, key_bytes) ||
+                rns_overlap(out, ct_bytes, key, key_bytes) || rns_overlap(x, ct_bytes, key, key_bytes) ||
+                rns_overlap(y, ct_bytes, key, key_bytes))
+                throw std::invalid_argument("out or the scratch overlaps an operand!");
+            if (rns_overlap(ks_scratch, ks_bytes, out, ct_bytes) || rns_overlap(ks_scratch, ks_bytes, scratch, s.total))
+                throw std::invalid_argument("The scratch overlaps out!");
+            // the limits of relinearize's coefficient path, before the first launch: the batch of its widest transform is
+            // an int, and its grids (mod_up, the inner product, mod_down_add) launch at most 2 * count * max(N, 256)
+            // work-items
+            const unsigned long long ks_m = static_cast<unsigned>(L + ks.p_count());
+            if (static_cast<unsigned long long>(ks.digits()) * static_cast<unsigned>(count) * ks_m > 0x7FFFFFFFull ||
+                2ull * static_cast<unsigned>(count) * ((1ull << n) > 256ull ? (1ull << n) : 256ull) > 0xFFFFFFFFull)
+                throw std::invalid_argument("Invalid count!");
+            const T* e = product(x, y, count, input_ntt, scratch, stream);
+            // the low components straight into out, the top one into the coeff region: dead since bfv_extend, and
+            // T[count][L][N] fits its T[2][count][L][N]
+            T* top = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.coeff);
+            scale_round(e, out, 2 * count, stream);
+            scale_round(e + 2 * cols * M, top, count, stream);
+            ks.relinearize(out, top, key, out, count, false, output_ntt, ks_scratch, stream);
         }
     };
 
@@ -532,6 +599,7 @@ namespace gpuntt
             throw std::invalid_argument("null pointer argument");
         std::unique_ptr<Impl> p(new Impl);
         p->L = h.L, p->K = h.K, p->M = h.M, p->n = n_power, p->t = plain_modulus, p->lay = lay;
+        p->poly = reduction_poly;
 
         // the run of constants: the two images, the plan's own arrays, the fold image -- one host buffer, one copy
         const int L = h.L, KP = bc_padded(h.K);
@@ -563,6 +631,7 @@ namespace gpuntt
         }
         std::vector<Modulus<T>> full(q_moduli_host, q_moduli_host + h.L);
         full.insert(full.end(), b_moduli_host, b_moduli_host + h.K);
+        p->moduli = full;
 
         void* raw = workspace_device;
         if (raw == nullptr)
@@ -624,6 +693,23 @@ namespace gpuntt
     {
         p_->multiply(device_x, device_y, device_out, count, input_ntt, output_ntt, scratch_device, stream);
     }
+
+    template <typename T>
+    void BfvMultiplyPlan<T>::multiply_relinearize(const T* device_x, const T* device_y, const KeySwitchPlan<T>& key_switch,
+                                                  const T* device_key, T* device_out, int count, bool input_ntt,
+                                                  bool output_ntt, void* scratch_device, void* key_switch_scratch_device,
+                                                  stream_t stream) const
+    {
+        p_->multiply_relinearize(device_x, device_y, key_switch, device_key, device_out, count, input_ntt, output_ntt,
+                                 scratch_device, key_switch_scratch_device, stream);
+    }
+    template <typename T> Modulus<T> BfvMultiplyPlan<T>::modulus(int m) const
+    {
+        if (m < 0 || m >= p_->M)
+            throw std::invalid_argument("Invalid modulus index!");
+        return p_->moduli[m];
+    }
+    template <typename T> ReductionPolynomial BfvMultiplyPlan<T>::reduction_poly() const { return p_->poly; }
 
     template <typename T> int BfvMultiplyPlan<T>::q_count() const { return p_->L; }
     template <typename T> int BfvMultiplyPlan<T>::b_count() const { return p_->K; }

@@ -938,6 +938,26 @@ extern "C"
                                                                       static_cast<hipStream_t>(stream));          \
         });                                                                                       \
     }                                                                                             \
+    int gpuntt_keyswitch_plan_mod_down_add_##S(const gpuntt_keyswitch_plan* plan, const T* x, const T* addend, \
+                                               T* out, int stacks, void* stream)                  \
+    {                                                                                             \
+        GPUNTT_NEED(plan, x, addend, out)                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->mod_down_add(x, addend, out, stacks, \
+                                                                          static_cast<hipStream_t>(stream)); \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_relinearize_##S(const gpuntt_keyswitch_plan* plan, const T* c01, const T* c2, \
+                                              const T* key, T* out, int count, int input_ntt, int output_ntt, \
+                                              void* scratch, void* stream)                        \
+    {                                                                                             \
+        GPUNTT_NEED(plan, c01, c2, key, out, scratch)                                             \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->relinearize(                         \
+                c01, c2, key, out, count, input_ntt != 0, output_ntt != 0, scratch,               \
+                static_cast<hipStream_t>(stream));                                                \
+        });                                                                                       \
+    }                                                                                             \
     int gpuntt_keyswitch_plan_decompose_##S(const gpuntt_keyswitch_plan* plan, const T* c_in, T* a, int count,     \
                                             int input_ntt, void* scratch, void* stream)           \
     {                                                                                             \
@@ -1273,6 +1293,18 @@ extern "C"
         return guarded([&] {                                                                      \
             reinterpret_cast<const BfvMultiplyPlan<T>*>(plan)->multiply(                          \
                 x, y, out, count, input_ntt != 0, output_ntt != 0, scratch, static_cast<hipStream_t>(stream));    \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_plan_multiply_relinearize_##S(const gpuntt_bfv_plan* plan, const T* x, const T* y, \
+                                                 const gpuntt_keyswitch_plan* key_switch, const T* key, T* out, \
+                                                 int count, int input_ntt, int output_ntt, void* scratch, \
+                                                 void* key_switch_scratch, void* stream)          \
+    {                                                                                             \
+        GPUNTT_NEED(plan, x, y, key_switch, key, out, scratch, key_switch_scratch)                \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const BfvMultiplyPlan<T>*>(plan)->multiply_relinearize(              \
+                x, y, *reinterpret_cast<const KeySwitchPlan<T>*>(key_switch), key, out, count, input_ntt != 0, \
+                output_ntt != 0, scratch, key_switch_scratch, static_cast<hipStream_t>(stream));  \
         });                                                                                       \
     }                                                                                             \
     int gpuntt_bfv_plan_owns_workspace_##S(const gpuntt_bfv_plan* plan)                           \

@@ -43,6 +43,11 @@
 // multiply_relinearize_sum: the same sequence with tensor_top_sum and inner_product_tensor_sum of relinearize_sum.hip,
 // which loop over the terms: one key switch and one ModDown for sum_t x_t y_t.
 //
+// relinearize: the key switch of a three-component ciphertext whose components exist already.  In NTT
+// form decompose, inner_product_seeded of relinearize.hip (the inner product seeded with P c01) and finish; in coefficient
+// form mod_up, the transforms and the plain inner product, then mod_down_add -- mod_down's kernel with an addend epilogue
+// (base_conversion_internal.hpp) -- so c01 is never transformed on its own.
+//
 // Rescaling (a plan built with rescale_limbs = R > 0).  mod_down_rescale is mod_down's launch with a second
 // constants image, {q_{L-R} .. q_{L-1}, p_0 .. p_{K-1}} -> {q_0 .. q_{L-R-1}}: the R dropped q-limbs and the K special
 // limbs are one contiguous run of the full-base stack, (L - R) N words behind its start, so the strided kernel reads them
@@ -452,6 +457,7 @@ namespace gpuntt
     {
         int L = 0, K = 0, M = 0, alpha = 0, D = 0, n = 0, KM = 0;
         bool negacyclic = true;
+        std::vector<Modulus<T>> moduli; // [M] the full base as the caller gave it: modulus(m)
         std::vector<int> limbs;
         std::vector<T> p_mod_q, p_mod_q_shoup; // [L] P mod q_j and its Shoup companion: the c0 term of rotate_hoisted
         char* ws = nullptr;
@@ -506,8 +512,9 @@ namespace gpuntt
         // ONE launch of the strided base_convert (centred, divide): stacks of `limbs` limbs at x, the last `in_count` of the
         // first out_count + in_count are the input base, read in place, the first out_count are c; out is dense,
         // T[stacks][out_count][N].  The constants image lies `image` bytes into the workspace
+        // addend != nullptr (dense like out): ONE launch of mod_down_add instead, the same kernel with the addend epilogue
         void divide_in_stack(const T* x, T* out, int stacks, int limbs, int in_count, int out_count, size_t image,
-                             const kern::BcOffsets& off, hipStream_t stream) const
+                             const kern::BcOffsets& off, hipStream_t stream, const T* addend = nullptr) const
         {
             const unsigned long long poly = 1ull << n, full = static_cast<unsigned long long>(limbs) << n;
             const unsigned long long total = static_cast<unsigned long long>(stacks) << n;
@@ -515,10 +522,31 @@ namespace gpuntt
             const int KP = bc_padded(out_count);
             const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(host::bc_ksplit(tiles, out_count)));
             const size_t lds = static_cast<size_t>(in_count) * kern::BC_NT * sizeof(T);
-            GPUNTT_LAUNCH((kern::base_convert<T, true, true, true>), grid, dim3(kern::BC_NT), lds, stream,
-                          x + out_count * poly, x, out, reinterpret_cast<const T*>(ws + image), off, in_count, out_count, KP,
-                          n, total, kern::BcStrides<true>{full, full, static_cast<unsigned long long>(out_count) << n});
+            const kern::BcStrides<true> strides{full, full, static_cast<unsigned long long>(out_count) << n};
+            if (addend != nullptr)
+                GPUNTT_LAUNCH((kern::mod_down_add<T>), grid, dim3(kern::BC_NT), lds, stream, x + out_count * poly, x, addend,
+                              out, reinterpret_cast<const T*>(ws + image), off, in_count, out_count, KP, n, total, strides);
+            else
+                GPUNTT_LAUNCH((kern::base_convert<T, true, true, true>), grid, dim3(kern::BC_NT), lds, stream,
+                              x + out_count * poly, x, out, reinterpret_cast<const T*>(ws + image), off, in_count,
+                              out_count, KP, n, total, strides);
             GPUNTT_HIP_CHECK(hipGetLastError());
+        }
+
+        // x: T[stacks][M][N], addend and out: T[stacks][L][N]; addend may be exactly out
+        void mod_down_add(const T* x, const T* addend, T* out, int stacks, hipStream_t stream) const
+        {
+            ks_check_mod_down<T>(L, M, x, out, n, stacks);
+            if (addend == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            if (stacks == 0)
+                return;
+            const std::uint64_t cols = static_cast<std::uint64_t>(stacks) << n;
+            const std::uint64_t low_bytes = cols * L * sizeof(T);
+            if (rns_overlap(addend, low_bytes, x, cols * M * sizeof(T)) ||
+                (addend != out && rns_overlap(addend, low_bytes, out, low_bytes)))
+                throw std::invalid_argument("The addend overlaps an operand!");
+            divide_in_stack(x, out, stacks, M, K, L, lay.down, down_off, stream, addend);
         }
 
         void need_rescale() const
@@ -997,6 +1025,66 @@ namespace gpuntt
             host::relin_sum_inner_launch<T>(a, key, acc, consts, args, D, count, L, M, KM, n, true, stream);
             finish(acc, out, 2 * count, output_ntt, rescale, stream);
         }
+
+        // c01: T[2][count][L][N], c2: T[count][L][N], out: T[2][count][L][N]; key: T[D_key][2][KM][N]; the scratch:
+        // ks_scratch(count, 2)
+        void relinearize(const T* c01, const T* c2, const T* key, T* out, int count, bool input_ntt, bool output_ntt,
+                         void* scratch, hipStream_t stream) const
+        {
+            need_transforms();
+            const KsScratch s = ks_scratch<T>(L, M, D, n, count, 2); // checks count
+            if (c01 == nullptr || c2 == nullptr || key == nullptr || out == nullptr || scratch == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
+                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            if (count == 0)
+                return;
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const std::uint64_t low_bytes = cols * L * 2 * sizeof(T), top_bytes = cols * L * sizeof(T);
+            const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
+            for (const auto& op :
+                 {std::pair<const void*, std::uint64_t>{c01, low_bytes}, {c2, top_bytes}, {key, key_bytes}})
+                if (rns_overlap(scratch, s.total, op.first, op.second))
+                    throw std::invalid_argument("out or the scratch overlaps an operand!");
+            // out may be exactly c01: every word of c01 is read by the lane that later writes it (mod_down_add), or all of
+            // it is read before mod_down's first write on the stream (inner_product_seeded).  Any other overlap is refused
+            if (rns_overlap(out, low_bytes, c2, top_bytes) || rns_overlap(out, low_bytes, key, key_bytes) ||
+                (rns_overlap(out, low_bytes, c01, low_bytes) && out != c01) || rns_overlap(c01, low_bytes, c2, top_bytes) ||
+                rns_overlap(c01, low_bytes, key, key_bytes) || rns_overlap(c2, top_bytes, key, key_bytes))
+                throw std::invalid_argument("out or the scratch overlaps an operand!");
+            if (rns_overlap(out, low_bytes, scratch, s.total))
+                throw std::invalid_argument("The scratch overlaps out!");
+            // the batches of the transforms are ints; the grids of mod_up and mod_down: as their own launches check
+            if (static_cast<unsigned long long>(D) * static_cast<unsigned>(count) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
+                throw std::invalid_argument("Invalid count!");
+            (void) column_tiles(cols, kern::KS_NT, "Invalid count!");
+            (void) column_tiles(2 * cols, kern::BC_NT, "Invalid count!");
+            T* a = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.a);
+            T* acc = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.inner_out);
+            if (!input_ntt)
+            {
+                // c01 is in coefficient form: it joins after the division, in mod_down's own epilogue
+                mod_up(c2, a, count, BaseConvMode::centred, stream);
+                ntt_full_f->execute(a, a, D * count * M, stream);
+                inner->multiply_accumulate(a, key, acc, n, D, 2, count, false, KM, limbs.data(), stream);
+                ntt_full_i->execute(acc, acc, 2 * count * M, stream);
+                mod_down_add(acc, c01, out, 2 * count, stream);
+                if (output_ntt)
+                    ntt_q_f->execute(out, out, 2 * count * L, stream);
+                return;
+            }
+            kern::RelinArgs<T> args{};
+            for (int m = 0; m < M; m++)
+                args.limbs.v[m] = static_cast<unsigned char>(limbs[m]);
+            for (int j = 0; j < L; j++)
+                args.p_mod_q[j] = p_mod_q[j], args.p_mod_q_shoup[j] = p_mod_q_shoup[j];
+            const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
+            // the grid limit of the kernel, before the first launch
+            host::relin_seeded_launch<T>(a, key, acc, consts, c01, args, D, count, L, M, KM, n, false, stream);
+            decompose(c2, a, count, true, scratch, stream);
+            host::relin_seeded_launch<T>(a, key, acc, consts, c01, args, D, count, L, M, KM, n, true, stream);
+            finish(acc, out, 2 * count, output_ntt, false, stream);
+        }
     };
 
     template <typename T> int KeySwitchPlan<T>::digits(int q_count, int alpha)
@@ -1087,7 +1175,7 @@ namespace gpuntt
         const std::vector<T> down_img = host::bc_image<T>(h.down, p->down_off);
         std::vector<Modulus<T>> full(q_moduli_host, q_moduli_host + h.L);
         full.insert(full.end(), p_moduli_host, p_moduli_host + h.K);
-        p->R = R, p->Lk = Lk;
+        p->R = R, p->Lk = Lk, p->moduli = full;
         std::vector<T> down_rs_img, rs_img;
         if (R > 0)
         {
@@ -1315,8 +1403,34 @@ namespace gpuntt
         p_->switch_digits(a, device_key, device_out, count, components, output_ntt, scratch_device, stream);
     }
 
+    template <typename T>
+    void KeySwitchPlan<T>::mod_down_add(const T* device_x, const T* device_addend, T* device_out, int stacks,
+                                        stream_t stream) const
+    {
+        p_->mod_down_add(device_x, device_addend, device_out, stacks, stream);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::relinearize(const T* device_c01, const T* device_c2, const T* device_key, T* device_out,
+                                       int count, bool input_ntt, bool output_ntt, void* scratch_device,
+                                       stream_t stream) const
+    {
+        p_->relinearize(device_c01, device_c2, device_key, device_out, count, input_ntt, output_ntt, scratch_device,
+                        stream);
+    }
+    template <typename T> Modulus<T> KeySwitchPlan<T>::modulus(int m) const
+    {
+        if (m < 0 || m >= p_->M)
+            throw std::invalid_argument("Invalid modulus index!");
+        return p_->moduli[m];
+    }
+    template <typename T> ReductionPolynomial KeySwitchPlan<T>::reduction_poly() const
+    {
+        return p_->negacyclic ? ReductionPolynomial::X_N_plus : ReductionPolynomial::X_N_minus;
+    }
+
     template <typename T> int KeySwitchPlan<T>::q_count() const { return p_->L; }
     template <typename T> int KeySwitchPlan<T>::p_count() const { return p_->K; }
+    template <typename T> int KeySwitchPlan<T>::key_mod_count() const { return p_->KM; }
     template <typename T> int KeySwitchPlan<T>::alpha() const { return p_->alpha; }
     template <typename T> int KeySwitchPlan<T>::digits() const { return p_->D; }
     template <typename T> int KeySwitchPlan<T>::n_power() const { return p_->n; }

@@ -1,4 +1,5 @@
-// relinearize.hip -- the two kernels of KeySwitchPlan<T>::multiply_relinearize (include/gpuntt/rns/key_switch.cuh): the
+// relinearize.hip -- the kernels of KeySwitchPlan<T>::multiply_relinearize and ::relinearize
+// (include/gpuntt/rns/key_switch.cuh).  multiply_relinearize: the
 // product of two ciphertexts x = (x0, x1), y = (y0, y1) with the top component x1 y1 switched back under the
 // relinearization key, in ONE key switch.
 //
@@ -17,6 +18,10 @@
 // x0, x1; then three exact macs: x0' y0 into c = 0, x0' y1 and x1' y0 into c = 1.  mac is exact for any two words, so y is
 // not reduced.  Bound: the accumulator is exact up to its 32-bit carry count, one carry at most per term, and the fold's
 // product with the carry word is an exact Shoup product for any word -- D + 2 terms (D <= 64) need no new bound.
+//
+// inner_product_seeded (KeySwitchPlan::relinearize with input_ntt): the same inner product for a three-component ciphertext
+// whose low components c01 = T[2][count][L][N] already exist.  Its seed (IpSeedLow) is ONE exact mac per word, (P mod q_m)
+// times the word as it stands: the accumulator is exact for any two words, so c01 is not reduced first.  D + 1 terms.
 //
 // tensor_top is the same arithmetic for one term: one mac into a zero accumulator, IpFold::sum, IpFold::reduce.
 //
@@ -98,6 +103,64 @@ namespace gpuntt
             ip_digit_loop<T, V, 2, RB>(a, key, acc, consts, ra.limbs, D, count, M, KM, n_power, tiles, seed);
         }
 
+        // How inner_product_seeded seeds its accumulators: (P mod q_m) c01[c] for m < L, zero for the special limbs.
+        // c01: T[2][count][L][N] in NTT form, any word: mac is exact for any two words, so nothing is reduced first -- ONE
+        // mac per seed word.  An input past the end of the last block re-reads the block's last one, as the digit loop does
+        template <typename T> struct IpSeedLow
+        {
+            const T* c01;
+            T pq; // P mod q_m
+            int L, count, n_power;
+            bool on; // m < L
+            template <int RB, int C, int V>
+            __device__ __forceinline__ void operator()(IpAcc<T> (&acc)[RB][C][V], const IpPlace& p, const T*) const
+            {
+                static_assert(C == 2, "a three-component ciphertext has two components after the switch");
+                using Vec = IpVec<T, V>;
+#pragma unroll
+                for (int r = 0; r < RB; r++)
+#pragma unroll
+                    for (int c = 0; c < C; c++)
+#pragma unroll
+                        for (int v = 0; v < V; v++)
+                            acc[r][c][v] = IpAcc<T>{T(0), T(0), 0u};
+                if (!on)
+                    return;
+                const unsigned long long in_stack = static_cast<unsigned long long>(L) << n_power; // one input's limbs
+                const unsigned long long in_comp = static_cast<unsigned long long>(count) * in_stack;
+                const unsigned long long first =
+                    static_cast<unsigned long long>(p.r0) * in_stack + (static_cast<unsigned long long>(p.m) << n_power) +
+                    p.col;
+#pragma unroll
+                for (int r = 0; r < RB; r++)
+                {
+                    const unsigned long long at = first + static_cast<unsigned long long>(ip_min(r, p.nr - 1)) * in_stack;
+#pragma unroll
+                    for (int c = 0; c < C; c++)
+                    {
+                        const Vec s = *reinterpret_cast<const Vec*>(c01 + c * in_comp + at);
+#pragma unroll
+                        for (int v = 0; v < V; v++)
+                            acc[r][c][v].mac(pq, s.x[v]);
+                    }
+                }
+            }
+        };
+
+        // inner_product with the low components of a three-component ciphertext as the seed: KeySwitchPlan::relinearize
+        // with input_ntt.  grid: x = rblock * tiles + tile, y = m < M; the mapping of inner_product
+        template <typename T, int V, int RB>
+        __global__ __launch_bounds__(IP_NT) void inner_product_seeded(const T* __restrict__ a, const T* __restrict__ key,
+                                                                      T* __restrict__ acc, const T* __restrict__ consts,
+                                                                      const T* c01, RelinArgs<T> ra, int D, int count,
+                                                                      int L, int M, int KM, int n_power, unsigned tiles)
+        {
+            const unsigned m = blockIdx.y;
+            const bool on = m < static_cast<unsigned>(L);
+            const IpSeedLow<T> seed{c01, ra.p_mod_q[m], L, count, n_power, on};
+            ip_digit_loop<T, V, 2, RB>(a, key, acc, consts, ra.limbs, D, count, M, KM, n_power, tiles, seed);
+        }
+
         // grid: x = r * tiles + tile, y = m < L; x1, y1, d2: T[count][L][N]
         template <typename T, int V>
         __global__ __launch_bounds__(IP_NT) void tensor_top(const T* x1, const T* y1, T* __restrict__ d2,
@@ -156,6 +219,33 @@ namespace gpuntt
                 GPUNTT_HIP_CHECK(hipGetLastError());
             }
 
+            template <typename T, int V, int RB>
+            void relin_seeded_as(const T* a, const T* key, T* acc, const T* consts, const T* c01,
+                                 const kern::RelinArgs<T>& args, int D, int count, int L, int M, int KM, int n_power,
+                                 bool enqueue, hipStream_t stream)
+            {
+                const RelinGrid g = relin_grid(n_power, V, (static_cast<unsigned long long>(count) + RB - 1) / RB);
+                if (!enqueue)
+                    return;
+                GPUNTT_LAUNCH((kern::inner_product_seeded<T, V, RB>), dim3(g.blocks, static_cast<unsigned>(M)), dim3(g.nt),
+                              0, stream, a, key, acc, consts, c01, args, D, count, L, M, KM, n_power, g.tiles);
+                GPUNTT_HIP_CHECK(hipGetLastError());
+            }
+
+            // the blocks of relin_inner_v below
+            template <typename T, int V>
+            void relin_seeded_v(const T* a, const T* key, T* acc, const T* consts, const T* c01,
+                                const kern::RelinArgs<T>& args, int D, int count, int L, int M, int KM, int n_power,
+                                bool enqueue, hipStream_t stream)
+            {
+                if (count >= 4)
+                    relin_seeded_as<T, V, 4>(a, key, acc, consts, c01, args, D, count, L, M, KM, n_power, enqueue, stream);
+                else if (count >= 2)
+                    relin_seeded_as<T, V, 2>(a, key, acc, consts, c01, args, D, count, L, M, KM, n_power, enqueue, stream);
+                else
+                    relin_seeded_as<T, V, 1>(a, key, acc, consts, c01, args, D, count, L, M, KM, n_power, enqueue, stream);
+            }
+
             // a block of 4 inputs where count has them, of 2 for count = 2 or 3 (a block past the end of count multiplies
             // for nothing), one input per lane for count = 1: inner_product's launch_c for C = 2
             template <typename T, int V>
@@ -196,6 +286,24 @@ namespace gpuntt
                 relin_inner_v<T, 1>(a, key, acc, consts, x, y, args, D, count, L, M, KM, n_power, enqueue, stream);
         }
 
+        template <typename T>
+        void relin_seeded_launch(const T* a, const T* key, T* acc, const T* consts, const T* c01,
+                                 const kern::RelinArgs<T>& args, int D, int count, int L, int M, int KM, int n_power,
+                                 bool enqueue, hipStream_t stream)
+        {
+            constexpr int VW = 16 / sizeof(T);
+            if (relin_wide<T>(n_power, {a, key, acc, c01}))
+                relin_seeded_v<T, VW>(a, key, acc, consts, c01, args, D, count, L, M, KM, n_power, enqueue, stream);
+            else
+                relin_seeded_v<T, 1>(a, key, acc, consts, c01, args, D, count, L, M, KM, n_power, enqueue, stream);
+        }
+
+        template void relin_seeded_launch<Data32>(const Data32*, const Data32*, Data32*, const Data32*, const Data32*,
+                                                  const kern::RelinArgs<Data32>&, int, int, int, int, int, int, bool,
+                                                  hipStream_t);
+        template void relin_seeded_launch<Data64>(const Data64*, const Data64*, Data64*, const Data64*, const Data64*,
+                                                  const kern::RelinArgs<Data64>&, int, int, int, int, int, int, bool,
+                                                  hipStream_t);
         template void relin_top_launch<Data32>(const Data32*, const Data32*, Data32*, const Data32*, int, int, int, int, bool,
                                                hipStream_t);
         template void relin_top_launch<Data64>(const Data64*, const Data64*, Data64*, const Data64*, int, int, int, int, bool,

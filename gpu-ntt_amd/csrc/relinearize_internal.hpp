@@ -75,5 +75,12 @@ namespace gpuntt
         void relin_inner_launch(const T* a, const T* key, T* acc, const T* consts, const T* x, const T* y,
                                 const kern::RelinArgs<T>& args, int D, int count, int L, int M, int KM, int n_power,
                                 bool enqueue, hipStream_t stream);
+
+        // inner_product_seeded: a, key, acc as above; c01: T[2][count][L][N] in NTT form, any word.  One launch.
+        // enqueue false: only the checks.  Throws std::invalid_argument beyond the grid limits
+        template <typename T>
+        void relin_seeded_launch(const T* a, const T* key, T* acc, const T* consts, const T* c01,
+                                 const kern::RelinArgs<T>& args, int D, int count, int L, int M, int KM, int n_power,
+                                 bool enqueue, hipStream_t stream);
     } // namespace host
 } // namespace gpuntt

@@ -37,7 +37,8 @@
 //     plan call writes; y may be exactly x (a squaring).  In coefficient form (input_ntt false) every word may hold any
 //     value: extend reads it modulo q_m.  In NTT form the first step is a transform, which is defined on residues: the
 //     words are canonical, as GPU_INTT takes them.  out = T[3][count][L][N]: out[2] is directly the c_in of
-//     KeySwitchPlan::apply for relinearization (components = 2; add its two outputs to out[0], out[1] modulo q_m).
+//     KeySwitchPlan::apply for relinearization (components = 2; add its two outputs to out[0], out[1] modulo q_m) --
+//     multiply_relinearize below does all of that in one call, KeySwitchPlan::relinearize the second half.
 //     DEFINITION, word for word:
 //       1. [input_ntt: GPU_INTT over the q-base, 2 * count * L polynomials per operand]
 //       2. extend over the 2 * count stacks of each operand
@@ -52,6 +53,23 @@
 //     both operands, ONE bfv_tensor, ONE full-base INTT, ONE bfv_scale_round, [ONE q-base NTT].  No step's launch count
 //     grows with count.  multiply allocates nothing and never synchronises: one stream, capturable into a hipGraph as it
 //     is.  count = 0 launches nothing.
+//   multiply_relinearize(x, y, key_switch, key, out, count, input_ntt, output_ntt, scratch, key_switch_scratch):  the
+//     product, relinearized: BFV ct x ct in one call.  key_switch is a KeySwitchPlan<T> over the same q-base (its special
+//     base, digits and key layout are its own), key the relinearization key it reads (s^2 -> s), out = T[2][count][L][N].
+//     DEFINITION, word for word:
+//       m = multiply(x, y, count, input_ntt, output_ntt = false)
+//       out = key_switch.relinearize(m[0..1], m[2], key, count, input_ntt = false, output_ntt)
+//     What runs: steps 1 to 5 of multiply; bfv_scale_round over stacks 0 .. 2 count - 1 INTO out; bfv_scale_round over
+//     stacks 2 count .. 3 count - 1 into the scratch's coefficient region (dead since bfv_extend; T[count][L][N] fits its
+//     T[2][count][L][N]); relinearize's coefficient path with mod_down_add in place on out.  No T[3][count][L][N]
+//     temporary, no add pass, no transform of the low components on their own.  scratch_bytes(count) is unchanged;
+//     key_switch_scratch is key_switch.scratch_bytes(count, 2) bytes, 256-byte aligned.  out may be exactly x or exactly
+//     y, as for multiply; the two scratches must not overlap each other, out, an operand or the key.  Allocates nothing,
+//     never synchronises, capturable as it is; count = 0 launches nothing.
+//     std::invalid_argument("The key-switching plan does not match!"), before anything is launched: a q-modulus differs in
+//     value, q_count, n_power or the reduction polynomial differs, or one of the two plans has no transforms.  Then
+//     multiply's refusals, a null key or key_switch_scratch, a misaligned key_switch_scratch, and a count beyond
+//     relinearize's limits
 //   scratch: scratch_bytes(count) bytes owned by the CALLER, 256-byte aligned: the operands in the full base
 //     T[4][count][M][N] (x0, x1, y0, y1 -- bfv_tensor writes d0, d1, d2 over the first three, each word by the lane that
 //     read it) and T[2][count][L][N] for the coefficient form of one operand.
@@ -81,6 +99,7 @@
 #include "gpuntt/common/modular_arith.cuh"
 #include "gpuntt/common/nttparameters.cuh"
 #include "gpuntt/rns/base_conversion.cuh"
+#include "gpuntt/rns/key_switch.cuh"
 
 namespace gpuntt
 {
@@ -117,8 +136,14 @@ namespace gpuntt
         void multiply(const T* device_x, const T* device_y, T* device_out, int count, bool input_ntt, bool output_ntt,
                       void* scratch_device, stream_t stream) const;
 
+        void multiply_relinearize(const T* device_x, const T* device_y, const KeySwitchPlan<T>& key_switch,
+                                  const T* device_key, T* device_out, int count, bool input_ntt, bool output_ntt,
+                                  void* scratch_device, void* key_switch_scratch_device, stream_t stream) const;
+
         int q_count() const;
         int b_count() const;
+        Modulus<T> modulus(int m) const;            // modulus m < M of the full base, as the constructor took it
+        ReductionPolynomial reduction_poly() const; // as the constructor took it
         int n_power() const;
         T plain_modulus() const;
         bool has_transforms() const;

@@ -27,6 +27,13 @@
 //     ONE kernel launch for all stacks, the special limbs read in place.  out must NOT overlap x: stacks of x are M N
 //     words apart and those of out L N, so out[s] lies over limbs of earlier stacks that other workgroups may not have
 //     read yet -- in-place operation cannot be made safe without a second pass and is refused
+//   mod_down_add(x, addend, out, stacks):  mod_down with an addend.  x as for mod_down; addend = T[stacks][L][N], ANY word
+//     (read modulo q_j); out = T[stacks][L][N].  DEFINITION, word for word:
+//       out[s][j] = (mod_down(x)[s][j] + (addend[s][j] mod q_j)) mod q_j, canonical
+//     ONE launch (mod_down_add: mod_down's kernel with an addend epilogue behind a compile-time switch, the same output
+//     split); allocates nothing, never synchronises; stacks = 0 launches nothing.  addend may be exactly out: each word is
+//     read and then written by the same lane.  out must not overlap x (mod_down's rule); any other overlap of addend with
+//     out or x is refused.  Refusals: mod_down's, plus a null addend
 //   decompose(c_in, a, count, input_ntt, scratch):
 //       [input_ntt: INTT over the count * L polynomials of c_in (q-base) into scratch]  mod_up (centred)  forward NTT in
 //       place over the D * count * M polynomials of a
@@ -136,6 +143,37 @@
 //     anything is launched: any other overlap of out or the scratch with an operand or with each other, a null pointer, a
 //     scratch that is not 256-byte aligned, count < 0, a count beyond the grid and batch limits rotate_hoisted checks, a
 //     plan built without transforms
+//   relinearize(c01, c2, key, out, count, input_ntt, output_ntt, scratch):  the key switch of `count` THREE-component
+//     ciphertexts, whatever formed them -- a BFV product (rns/bfv_multiply.cuh), a hand-accumulated sum of tensors, a
+//     scheme with a step between the tensor and the key switch.  c01 = T[2][count][L][N], the two low components, any
+//     word, read modulo q_m; c2 = T[count][L][N], the top component: any word in coefficient form, residues in NTT form,
+//     as apply takes them.  A contiguous T[3][count][L][N] is c2 = c01 + 2 * count * L * N.  key, out = T[2][count][L][N]
+//     and the scratch (the existing scratch_bytes(count, 2), 256-byte aligned) are multiply_relinearize's.
+//     DEFINITION, word for word, through the calls that exist beside it:
+//       1. k = apply(c2, key, count, components = 2, input_ntt, output_ntt),
+//       2. out[c] = (k[c] + c01[c]) mod q_m, c01 reduced and -- when input_ntt != output_ntt -- brought to the output's
+//          form by the q-base transform first.
+//     What runs, no step's launch count growing with count, and c01 never transformed on its own:
+//       input_ntt true:   the plan's decompose steps on c2 (the q-base INTT into the scratch, mod_up, the full-base NTT);
+//                         inner_product_seeded: acc[c][r][m][j] = (sum_d a[d][r][m][j] * key[d][c][limb(m)][j]
+//                         + [m < L] (P mod q_m) * c01[c][r][m][j]) mod q_m, one exact mac per seed word, the K special
+//                         limbs load nothing of c01; finish over 2 * count stacks.
+//       input_ntt false:  mod_up (centred) straight from c2; the full-base NTT; the plan's inner_product; the full-base
+//                         INTT; mod_down_add with c01 as the addend; [output_ntt: the q-base NTT over 2 * count * L].
+//     Both equal the definition.  input_ntt true: folding c01 in as P * c01 before the ModDown is multiply_relinearize's
+//     argument above with d_c = c01[c] -- (c_j + P d - conv_j) P^-1 = d + (c_j - conv_j) P^-1 (mod q_j), canonical on both
+//     sides, and the same after the linear, canonical forward NTT; with output_ntt false the fold goes through the
+//     full-base INTT, which on the q-limbs is the q-base INTT of c01.  input_ntt false: mod_down_add adds the reduced
+//     coefficient-form c01 to the coefficient-form k, which is the definition for output_ntt false; for output_ntt true
+//     NTT(k + c) = NTT(k) + NTT(c) (mod q_m), and both sides are canonical, so they are the same word.
+//     With input_ntt and a c01 that holds the d_0, d_1 of multiply_relinearize's step 1, the call returns that call's
+//     words.  Allocates nothing, never synchronises: one stream, capturable as it is.  count = 0: nothing is launched.
+//     out may be exactly c01.  std::invalid_argument, before anything is launched: every other overlap among out, the
+//     scratch, c01, c2 and key; a null pointer; a scratch that is not 256-byte aligned; count < 0 or beyond the grid and
+//     int limits multiply_relinearize checks; a plan built without transforms.
+//     There is no relinearize_rescale: on the coefficient path P * c01 would have to be added to the DROPPED q-limbs
+//     before the conversion reads them (they are part of X, see "Rescaling"), which the epilogue of mod_down_add, after
+//     the division, cannot do -- a different change to the kernel
 //   multiply_relinearize_sum(x, y, terms, key, out, count, output_ntt, scratch):  sum_t x_t * y_t over `terms` pairs of
 //     two-component ciphertexts with ONE key switch and ONE ModDown ("lazy relinearization"): an encrypted dot product, a
 //     matrix-vector product, a convolution, the power-basis terms of a polynomial evaluation.  x, y = HOST arrays of
@@ -373,6 +411,7 @@ namespace gpuntt
 
         void mod_up(const T* device_in, T* device_a, int count, BaseConvMode mode, stream_t stream) const;
         void mod_down(const T* device_x, T* device_out, int stacks, stream_t stream) const;
+        void mod_down_add(const T* device_x, const T* device_addend, T* device_out, int stacks, stream_t stream) const;
         void decompose(const T* device_c_in, T* device_a, int count, bool input_ntt, void* scratch_device,
                        stream_t stream) const;
         void switch_digits(const T* device_a, const T* device_key, T* device_out, int count, int components,
@@ -392,6 +431,9 @@ namespace gpuntt
         void multiply_relinearize_sum(const T* const* device_x_host, const T* const* device_y_host, int terms,
                                       const T* device_key, T* device_out, int count, bool output_ntt,
                                       void* scratch_device, stream_t stream) const;
+
+        void relinearize(const T* device_c01, const T* device_c2, const T* device_key, T* device_out, int count,
+                         bool input_ntt, bool output_ntt, void* scratch_device, stream_t stream) const;
 
         // rescaling: a plan built with rescale_limbs = R > 0; every one of them throws on a plan with R = 0
         void mod_down_rescale(const T* device_x, T* device_out, int stacks, stream_t stream) const;
@@ -424,10 +466,13 @@ namespace gpuntt
         int q_count() const;
         int rescale_limbs() const; // R
         int p_count() const;
+        int key_mod_count() const;
         int alpha() const;
         int digits() const;
         int n_power() const;
         bool has_transforms() const;
+        Modulus<T> modulus(int m) const;            // modulus m < M of the full base, as the constructor took it
+        ReductionPolynomial reduction_poly() const; // as the constructor took it
         bool owns_workspace() const; // false: the plan lives in the caller's workspace and has allocated nothing
         size_t scratch_bytes(int count, int components) const;
         size_t hoisted_scratch_bytes(int count, int elements) const;

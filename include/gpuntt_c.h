@@ -422,6 +422,14 @@ extern "C"
                                          void* stream);
     int gpuntt_keyswitch_plan_mod_down_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* x, uint32_t* out, int stacks,
                                            void* stream);
+    /* mod_down with an addend (T[stacks][L][N], any word; it may be exactly out): key_switch.cuh, "mod_down_add" */
+    int gpuntt_keyswitch_plan_mod_down_add_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* x, const uint32_t* addend, uint32_t* out,
+                                               int stacks, void* stream);
+    /* the key switch of three-component ciphertexts: c01 = T[2][count][L][N], c2 = T[count][L][N]; key_switch.cuh,
+       "relinearize" */
+    int gpuntt_keyswitch_plan_relinearize_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* c01, const uint32_t* c2, const uint32_t* key,
+                                              uint32_t* out, int count, int input_ntt, int output_ntt, void* scratch,
+                                              void* stream);
     int gpuntt_keyswitch_plan_decompose_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* c_in, uint32_t* a, int count,
                                             int input_ntt, void* scratch, void* stream);
     int gpuntt_keyswitch_plan_switch_digits_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* a, const uint32_t* key,
@@ -471,6 +479,14 @@ extern "C"
                                          void* stream);
     int gpuntt_keyswitch_plan_mod_down_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* x, uint64_t* out, int stacks,
                                            void* stream);
+    /* mod_down with an addend (T[stacks][L][N], any word; it may be exactly out): key_switch.cuh, "mod_down_add" */
+    int gpuntt_keyswitch_plan_mod_down_add_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* x, const uint64_t* addend, uint64_t* out,
+                                               int stacks, void* stream);
+    /* the key switch of three-component ciphertexts: c01 = T[2][count][L][N], c2 = T[count][L][N]; key_switch.cuh,
+       "relinearize" */
+    int gpuntt_keyswitch_plan_relinearize_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* c01, const uint64_t* c2, const uint64_t* key,
+                                              uint64_t* out, int count, int input_ntt, int output_ntt, void* scratch,
+                                              void* stream);
     int gpuntt_keyswitch_plan_decompose_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* c_in, uint64_t* a, int count,
                                             int input_ntt, void* scratch, void* stream);
     int gpuntt_keyswitch_plan_switch_digits_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* a, const uint64_t* key,
@@ -675,8 +691,20 @@ extern "C"
                                      int count, int input_ntt, int output_ntt, void* scratch, void* stream);
     int gpuntt_bfv_plan_multiply_u64(const gpuntt_bfv_plan* plan, const uint64_t* x, const uint64_t* y, uint64_t* out,
                                      int count, int input_ntt, int output_ntt, void* scratch, void* stream);
+    /* BFV ct x ct, relinearized, in one call: out = T[2][count][L][N]; key_switch_scratch is the key-switching plan's
+       scratch_bytes(count, 2); bfv_multiply.cuh, "multiply_relinearize" */
+    int gpuntt_bfv_plan_multiply_relinearize_u32(const gpuntt_bfv_plan* plan, const uint32_t* x, const uint32_t* y,
+                                                 const gpuntt_keyswitch_plan* key_switch, const uint32_t* key, uint32_t* out,
+                                                 int count, int input_ntt, int output_ntt, void* scratch,
+                                                 void* key_switch_scratch, void* stream);
     int gpuntt_bfv_plan_owns_workspace_u32(const gpuntt_bfv_plan* plan); /* 1 / 0, negative on error */
     int gpuntt_bfv_plan_owns_workspace_u64(const gpuntt_bfv_plan* plan);
+    /* BFV ct x ct, relinearized, in one call: out = T[2][count][L][N]; key_switch_scratch is the key-switching plan's
+       scratch_bytes(count, 2); bfv_multiply.cuh, "multiply_relinearize" */
+    int gpuntt_bfv_plan_multiply_relinearize_u64(const gpuntt_bfv_plan* plan, const uint64_t* x, const uint64_t* y,
+                                                 const gpuntt_keyswitch_plan* key_switch, const uint64_t* key, uint64_t* out,
+                                                 int count, int input_ntt, int output_ntt, void* scratch,
+                                                 void* key_switch_scratch, void* stream);
     int gpuntt_bfv_plan_destroy_u32(gpuntt_bfv_plan* plan);
     int gpuntt_bfv_plan_destroy_u64(gpuntt_bfv_plan* plan);
     int gpuntt_bfv_constants_u32(const gpuntt_modulus32* q_moduli_host, int q_count, const gpuntt_modulus32* b_moduli_host,
