@@ -129,7 +129,8 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "keyswitch_plan_linear_transform_bsgs_rescale",
               "bfv_plan_workspace_bytes", "bfv_plan_scratch_bytes", "bfv_plan_create", "bfv_plan_extend",
               "bfv_plan_scale_round", "bfv_plan_multiply", "bfv_plan_multiply_relinearize", "bfv_plan_owns_workspace",
-              "bfv_plan_destroy",
+              "bfv_plan_destroy", "bfv_plan_max_terms", "bfv_plan_sum_scratch_bytes", "bfv_plan_multiply_sum",
+              "bfv_plan_multiply_relinearize_sum", "bfv_max_terms",
               "bfv_constants", "bfv_reference_extend", "bfv_reference_scale_round")
     for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option", "gpuntt_galois_element_u32",
                                 "gpuntt_automorphism_index_map"]
@@ -1530,6 +1531,18 @@ def bfv_constants(q_moduli, b_moduli, plain_modulus, n_power, bits=64):
     return out
 
 
+def bfv_max_terms(q_moduli, b_moduli, plain_modulus, n_power, bits=64):
+    """Host (no GPU): BfvMultiplyPlan<T>::max_terms of a plan of these bases, this t and this ring --
+    min(32, B // (2 t N Q)) -- with the checks of the constructor ("Auxiliary base too small!" where that is 0)."""
+    qs, qarr = _keyswitch_moduli(q_moduli, bits)
+    bs, barr = _keyswitch_moduli(b_moduli, bits)
+    out = ctypes.c_int()
+    fn = getattr(load_library(), "gpuntt_bfv_max_terms_u%d" % bits)
+    _check(fn(qarr, len(qs), barr, len(bs), _ct(bits)(int(plain_modulus) & ((1 << bits) - 1)), int(n_power),
+              ctypes.byref(out)))
+    return int(out.value)
+
+
 def bfv_reference_extend(q_moduli, b_moduli, x, full, n_power, stacks, bits=64):
     """Host (no GPU): BfvMultiplyPlan<T>::reference_extend on numpy arrays of the plan's word type -- x holds stacks x L
     x N words, full stacks x M x N (written and returned) -- after the argument checks of extend (ValueError).  None for
@@ -1689,6 +1702,79 @@ class BfvMultiplyPlan:
         fn = getattr(load_library(), "gpuntt_bfv_plan_multiply_relinearize_u%d" % self.bits)
         _check(fn(self._h, _ptr(x), _ptr(y), key_switch._h, _ptr(key), _ptr(out), int(count), int(bool(input_ntt)),
                   int(bool(output_ntt)), _ptr(scratch), _ptr(key_switch_scratch), _stream(stream)))
+
+    # ---- the summed product (bfv_multiply.cuh, "multiply_sum") ----
+    @property
+    def max_terms(self):
+        """BfvMultiplyPlan<T>::max_terms: min(32, B // (2 t N Q)), the most terms one multiply_sum call may add up"""
+        rc = getattr(load_library(), "gpuntt_bfv_plan_max_terms_u%d" % self.bits)(self._h)
+        if rc < 0:
+            _check(rc)
+        return int(rc)
+
+    def sum_scratch_bytes(self, count, operands):
+        """BfvMultiplyPlan<T>::sum_scratch_bytes: the scratch of multiply_sum for `operands` distinct operand tensors"""
+        out = ctypes.c_uint64()
+        _check(getattr(load_library(), "gpuntt_bfv_plan_sum_scratch_bytes_u%d" % self.bits)(
+            self.q_count, self.b_count, self.n_power, int(count), int(operands), ctypes.byref(out)))
+        return int(out.value)
+
+    def _sum_operands(self, xs, ys, out, comps, count, scratch):
+        """the checks multiply_sum and multiply_relinearize_sum share; returns (terms, x pointers, y pointers)"""
+        if xs is None or ys is None:
+            raise ValueError("null pointer argument")
+        xs, ys = list(xs), list(ys)
+        if len(xs) != len(ys):
+            raise ValueError("multiply_sum takes one y per x")
+        terms = len(xs)
+        if not 1 <= terms <= 32:
+            raise ValueError("Invalid terms!")
+        if out is None or scratch is None or any(t is None for t in xs + ys):
+            raise ValueError("null pointer argument")
+        cols = self._cols(count)
+        ct = cols * self.q_count * 2
+        self._check_buffers([(t, ct, "x[%d] (2 x count x L x N)" % i) for i, t in enumerate(xs)] +
+                            [(t, ct, "y[%d] (2 x count x L x N)" % i) for i, t in enumerate(ys)] +
+                            [(out, cols * self.q_count * comps, "out (%d x count x L x N)" % comps)])
+        _require_gpu(scratch)
+        distinct = len({t.data_ptr() for t in xs + ys})
+        if int(count) > 0 and scratch.numel() * scratch.element_size() < self.sum_scratch_bytes(count, distinct):
+            raise ValueError("scratch holds fewer than sum_scratch_bytes(count, %d) bytes: the call has %d distinct "
+                             "operands" % (distinct, distinct))
+        x_ptrs = (ctypes.c_void_p * terms)(*[t.data_ptr() for t in xs])
+        y_ptrs = (ctypes.c_void_p * terms)(*[t.data_ptr() for t in ys])
+        return terms, x_ptrs, y_ptrs
+
+    def multiply_sum(self, xs, ys, out, count, input_ntt=False, output_ntt=False, scratch=None, stream=None):
+        """sum_t xs[t] * ys[t] with ONE division by Q: xs, ys two lists of T device tensors, 1 <= T <= max_terms, each
+        T[2][count][L][N] with multiply's rules (ys[t] may be xs[t]; a tensor may appear in several terms and is extended
+        and transformed once) -> out T[3][count][L][N]; out may be exactly one operand.  scratch: at least
+        sum_scratch_bytes(count, U) bytes for the U distinct tensors, 256-byte aligned.  With one pair it equals multiply
+        word for word; with more it rounds once where T multiply calls round T times (bfv_multiply.cuh)."""
+        terms, x_ptrs, y_ptrs = self._sum_operands(xs, ys, out, 3, count, scratch)
+        fn = getattr(load_library(), "gpuntt_bfv_plan_multiply_sum_u%d" % self.bits)
+        _check(fn(self._h, x_ptrs, y_ptrs, terms, _ptr(out), int(count), int(bool(input_ntt)), int(bool(output_ntt)),
+                  _ptr(scratch), _stream(stream)))
+
+    def multiply_relinearize_sum(self, xs, ys, key_switch, key, out, count, input_ntt=False, output_ntt=False,
+                                 scratch=None, key_switch_scratch=None, stream=None):
+        """An encrypted BFV dot product in one call: multiply_sum(output_ntt=False), then key_switch.relinearize -> out
+        T[2][count][L][N], with ONE t/Q rounding, ONE key switch and ONE ModDown.  xs, ys, scratch as for multiply_sum;
+        key_switch, key, key_switch_scratch as for multiply_relinearize."""
+        if not isinstance(key_switch, KeySwitchPlan) or key_switch.bits != self.bits:
+            raise ValueError("key_switch is a KeySwitchPlan of the same word width")
+        if key is None or key_switch_scratch is None:
+            raise ValueError("null pointer argument")
+        terms, x_ptrs, y_ptrs = self._sum_operands(xs, ys, out, 2, count, scratch)
+        self._check_buffers([(key, key_switch._key_words(2) if self._cols(count) else 0,
+                              "key (D x 2 x key_mod_count x N)")])
+        _require_gpu(key_switch_scratch)
+        if int(count) > 0 and \
+                key_switch_scratch.numel() * key_switch_scratch.element_size() < key_switch.scratch_bytes(count, 2):
+            raise ValueError("key_switch_scratch holds fewer than key_switch.scratch_bytes(count, 2) bytes")
+        fn = getattr(load_library(), "gpuntt_bfv_plan_multiply_relinearize_sum_u%d" % self.bits)
+        _check(fn(self._h, x_ptrs, y_ptrs, terms, key_switch._h, _ptr(key), _ptr(out), int(count),
+                  int(bool(input_ntt)), int(bool(output_ntt)), _ptr(scratch), _ptr(key_switch_scratch), _stream(stream)))
 
     def close(self):
         if self._h:

@@ -25,6 +25,9 @@
 // bfv_tensor is tensor_top's arithmetic (relinearize.hip) for three terms: IpAcc::mac and IpFold of
 // inner_product_internal.hpp, the ONE copy of that arithmetic -- d1 is one exact two-term sum, folded once.  It may write
 // d over x: every word is written by the lane that read it, after its loads.
+//
+// multiply_sum / multiply_relinearize_sum: the host side is here (sum_check, sum_product: the distinct operands by pointer
+// equality, one slot of the operand region each); their kernel, bfv_tensor_sum, is in bfv_multiply_sum.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +37,7 @@
 #include <vector>
 
 #include "bfv_multiply_internal.hpp"
+#include "bfv_multiply_sum_internal.hpp"
 #include "gpuntt/ntt_merge/ntt.cuh"
 #include "gpuntt/rns/bfv_multiply.cuh"
 #include "launch.hpp"
@@ -262,6 +266,7 @@ namespace gpuntt
         struct BfvHost
         {
             int L = 0, K = 0, M = 0;
+            int max_terms = 1;                                 // min(BFV_MAX_TERMS, floor(B / (2 t N Q)))
             std::vector<std::uint64_t> mod;                    // [M] the full base
             host::BcHostConsts up, down;                       // {q} -> {b}, {b} -> {q}
             std::vector<std::uint64_t> tm, tmp;                // [M] t mod m_m and its Shoup companion
@@ -299,6 +304,15 @@ namespace gpuntt
                     big_mul(need, h.mod[i]);
                 if (big_less(B, need))
                     throw std::invalid_argument("Auxiliary base too small!");
+                // the largest terms <= BFV_MAX_TERMS with B >= 2 terms t N Q: what multiply_sum may add up
+                for (int terms = 2; terms <= BFV_MAX_TERMS; terms++)
+                {
+                    Big scaled = need;
+                    big_mul(scaled, static_cast<std::uint64_t>(terms));
+                    if (big_less(B, scaled))
+                        break;
+                    h.max_terms = terms;
+                }
             }
             for (int m = 0; m < h.M; m++)
             {
@@ -371,6 +385,22 @@ namespace gpuntt
             return s;
         }
 
+        // multiply_sum's scratch: the operand region grows to max(operands, 2) slots of T[2][count][M][N]; operands = 2
+        // is multiply's layout
+        template <typename T> BfvScratch bfv_sum_scratch(int L, int M, int n_power, int count, int operands)
+        {
+            if (count < 0)
+                throw std::invalid_argument("Invalid count!");
+            if (operands < 1 || operands > 2 * BFV_MAX_TERMS)
+                throw std::invalid_argument("Invalid operands!");
+            const size_t poly = (static_cast<size_t>(count) << n_power) * sizeof(T);
+            BfvScratch s{};
+            s.e = 0;
+            s.coeff = s.e + rns_align(poly * M * 2 * static_cast<size_t>(std::max(operands, 2)));
+            s.total = s.coeff + rns_align(poly * L * 2);
+            return s;
+        }
+
         // the argument checks of extend / scale_round (device or host arrays alike): `narrow` limbs per stack at a,
         // `wide` at b
         template <typename T>
@@ -412,7 +442,7 @@ namespace gpuntt
 
     template <typename T> struct BfvMultiplyPlan<T>::Impl
     {
-        int L = 0, K = 0, M = 0, n = 0;
+        int L = 0, K = 0, M = 0, n = 0, max_terms = 1;
         T t = 0;
         std::vector<Modulus<T>> moduli; // [M] the full base as the caller gave it: modulus(m)
         ReductionPolynomial poly = ReductionPolynomial::X_N_plus;
@@ -568,6 +598,152 @@ namespace gpuntt
             scale_round(e + 2 * cols * M, top, count, stream);
             ks.relinearize(out, top, key, out, count, false, output_ntt, ks_scratch, stream);
         }
+
+        // one multiply_sum call as the host sees it: the U distinct operand pointers in order of first appearance (x_0
+        // is slot 0) and the two slots of every term
+        struct SumCall
+        {
+            int U = 0;
+            const T* op[2 * BFV_MAX_TERMS];
+            kern::BfvSumArgs args;
+        };
+
+        // What multiply_sum and multiply_relinearize_sum share up to the first launch: every refusal of multiply_sum,
+        // with `comps` components at out.  Returns false when count is 0 and nothing is to be launched
+        bool sum_check(const T* const* xs, const T* const* ys, int terms, const T* out, int comps, int count,
+                       void* scratch, SumCall& call) const
+        {
+            if (!ntt_full_f)
+                throw std::invalid_argument("The plan was built without transform tables!");
+            if (terms < 1 || terms > BFV_MAX_TERMS)
+                throw std::invalid_argument("Invalid terms!");
+            if (terms > max_terms)
+                throw std::invalid_argument("Auxiliary base too small for these terms!");
+            if (xs == nullptr || ys == nullptr || out == nullptr || scratch == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            call.U = 0;
+            call.args = kern::BfvSumArgs{};
+            call.args.terms = terms;
+            auto slot_of = [&](const T* p) {
+                if (p == nullptr)
+                    throw std::invalid_argument("null pointer argument");
+                for (int s = 0; s < call.U; s++)
+                    if (call.op[s] == p)
+                        return static_cast<unsigned char>(s);
+                call.op[call.U] = p;
+                return static_cast<unsigned char>(call.U++);
+            };
+            for (int i = 0; i < terms; i++)
+            {
+                call.args.x_slot[i] = slot_of(xs[i]);
+                call.args.y_slot[i] = slot_of(ys[i]);
+            }
+            const BfvScratch s = bfv_sum_scratch<T>(L, M, n, count, call.U); // checks count
+            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
+                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            if (count == 0)
+                return false;
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T), out_bytes = cols * L * comps * sizeof(T);
+            for (int u = 0; u < call.U; u++)
+            {
+                const T* op = call.op[u];
+                if (rns_overlap(scratch, s.total, op, ct_bytes))
+                    throw std::invalid_argument("out or the scratch overlaps an operand!");
+                // out may be exactly one operand: the last read of every operand (bfv_extend, or the INTT before it)
+                // precedes bfv_scale_round's first write on the stream.  Any other overlap is refused
+                if (rns_overlap(out, out_bytes, op, ct_bytes) && op != out)
+                    throw std::invalid_argument("out or the scratch overlaps an operand!");
+            }
+            if (rns_overlap(out, out_bytes, scratch, s.total))
+                throw std::invalid_argument("The scratch overlaps out!");
+            // every limit before the first launch: the widest transform batch, 2 U count M (3 count M for U = 1), is an
+            // int; the grids as the launches check
+            const unsigned long long widest = static_cast<unsigned>(std::max(2 * call.U, 3));
+            if (widest * static_cast<unsigned>(count) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
+                throw std::invalid_argument("Invalid count!");
+            (void) column_tiles((3ull * static_cast<unsigned>(count)) << n, kern::BC_NT, "Invalid stacks!");
+            T* e = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.e);
+            host::bfv_tensor_sum_launch<T>(e, fold(), call.args, count, M, n, false, nullptr);
+            return true;
+        }
+
+        // steps 1 and 2 of multiply_sum and the one inverse transform: T[3][count][M][N] in coefficient form at the start
+        // of the scratch
+        T* sum_product(const SumCall& call, int count, bool input_ntt, void* scratch, hipStream_t stream) const
+        {
+            const BfvScratch s = bfv_sum_scratch<T>(L, M, n, count, call.U);
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            T* e = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.e);
+            T* coeff = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.coeff);
+            for (int u = 0; u < call.U; u++) // the coefficient region is reused in stream order
+            {
+                if (input_ntt)
+                    ntt_q_i->execute(call.op[u], coeff, 2 * count * L, stream);
+                extend(input_ntt ? coeff : call.op[u], e + cols * M * 2 * static_cast<unsigned>(u), 2 * count, stream);
+            }
+            ntt_full_f->execute(e, e, 2 * call.U * count * M, stream);
+            host::bfv_tensor_sum_launch<T>(e, fold(), call.args, count, M, n, true, stream);
+            ntt_full_i->execute(e, e, 3 * count * M, stream);
+            return e;
+        }
+
+        void multiply_sum(const T* const* xs, const T* const* ys, int terms, T* out, int count, bool input_ntt,
+                          bool output_ntt, void* scratch, hipStream_t stream) const
+        {
+            SumCall call;
+            if (!sum_check(xs, ys, terms, out, 3, count, scratch, call))
+                return;
+            const T* e = sum_product(call, count, input_ntt, scratch, stream);
+            scale_round(e, out, 3 * count, stream);
+            if (output_ntt)
+                ntt_q_f->execute(out, out, 3 * count * L, stream);
+        }
+
+        void multiply_relinearize_sum(const T* const* xs, const T* const* ys, int terms, const KeySwitchPlan<T>& ks,
+                                      const T* key, T* out, int count, bool input_ntt, bool output_ntt, void* scratch,
+                                      void* ks_scratch, hipStream_t stream) const
+        {
+            bool match = ntt_full_f && ks.has_transforms() && ks.q_count() == L && ks.n_power() == n &&
+                         ks.reduction_poly() == poly;
+            for (int m = 0; match && m < L; m++)
+                match = ks.modulus(m).value == moduli[m].value;
+            if (!match)
+                throw std::invalid_argument("The key-switching plan does not match!");
+            if (key == nullptr || ks_scratch == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            const size_t ks_bytes = ks.scratch_bytes(count, 2); // checks count
+            if (reinterpret_cast<uintptr_t>(ks_scratch) % 256 != 0)
+                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            SumCall call;
+            if (!sum_check(xs, ys, terms, out, 2, count, scratch, call))
+                return;
+            const BfvScratch s = bfv_sum_scratch<T>(L, M, n, count, call.U);
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T);
+            const std::uint64_t key_bytes =
+                ((static_cast<std::uint64_t>(ks.digits()) * 2 * ks.key_mod_count()) << n) * sizeof(T);
+            bool bad = rns_overlap(ks_scratch, ks_bytes, key, key_bytes) || rns_overlap(scratch, s.total, key, key_bytes) ||
+                       rns_overlap(out, ct_bytes, key, key_bytes);
+            for (int u = 0; u < call.U; u++)
+                bad = bad || rns_overlap(ks_scratch, ks_bytes, call.op[u], ct_bytes) ||
+                      rns_overlap(call.op[u], ct_bytes, key, key_bytes);
+            if (bad)
+                throw std::invalid_argument("out or the scratch overlaps an operand!");
+            if (rns_overlap(ks_scratch, ks_bytes, out, ct_bytes) || rns_overlap(ks_scratch, ks_bytes, scratch, s.total))
+                throw std::invalid_argument("The scratch overlaps out!");
+            // the limits of relinearize's coefficient path, as multiply_relinearize checks them
+            const unsigned long long ks_m = static_cast<unsigned>(L + ks.p_count());
+            if (static_cast<unsigned long long>(ks.digits()) * static_cast<unsigned>(count) * ks_m > 0x7FFFFFFFull ||
+                2ull * static_cast<unsigned>(count) * ((1ull << n) > 256ull ? (1ull << n) : 256ull) > 0xFFFFFFFFull)
+                throw std::invalid_argument("Invalid count!");
+            const T* e = sum_product(call, count, input_ntt, scratch, stream);
+            // as multiply_relinearize: the low components straight into out, the top one into the coeff region
+            T* top = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.coeff);
+            scale_round(e, out, 2 * count, stream);
+            scale_round(e + 2 * cols * M, top, count, stream);
+            ks.relinearize(out, top, key, out, count, false, output_ntt, ks_scratch, stream);
+        }
     };
 
     template <typename T> size_t BfvMultiplyPlan<T>::workspace_bytes(int q_count, int b_count, int n_power)
@@ -599,7 +775,7 @@ namespace gpuntt
             throw std::invalid_argument("null pointer argument");
         std::unique_ptr<Impl> p(new Impl);
         p->L = h.L, p->K = h.K, p->M = h.M, p->n = n_power, p->t = plain_modulus, p->lay = lay;
-        p->poly = reduction_poly;
+        p->poly = reduction_poly, p->max_terms = h.max_terms;
 
         // the run of constants: the two images, the plan's own arrays, the fold image -- one host buffer, one copy
         const int L = h.L, KP = bc_padded(h.K);
@@ -702,6 +878,43 @@ namespace gpuntt
     {
         p_->multiply_relinearize(device_x, device_y, key_switch, device_key, device_out, count, input_ntt, output_ntt,
                                  scratch_device, key_switch_scratch_device, stream);
+    }
+    template <typename T>
+    void BfvMultiplyPlan<T>::multiply_sum(const T* const* device_x_host, const T* const* device_y_host, int terms,
+                                          T* device_out, int count, bool input_ntt, bool output_ntt, void* scratch_device,
+                                          stream_t stream) const
+    {
+        p_->multiply_sum(device_x_host, device_y_host, terms, device_out, count, input_ntt, output_ntt, scratch_device,
+                         stream);
+    }
+    template <typename T>
+    void BfvMultiplyPlan<T>::multiply_relinearize_sum(const T* const* device_x_host, const T* const* device_y_host,
+                                                      int terms, const KeySwitchPlan<T>& key_switch, const T* device_key,
+                                                      T* device_out, int count, bool input_ntt, bool output_ntt,
+                                                      void* scratch_device, void* key_switch_scratch_device,
+                                                      stream_t stream) const
+    {
+        p_->multiply_relinearize_sum(device_x_host, device_y_host, terms, key_switch, device_key, device_out, count,
+                                     input_ntt, output_ntt, scratch_device, key_switch_scratch_device, stream);
+    }
+    template <typename T> int BfvMultiplyPlan<T>::max_terms() const { return p_->max_terms; }
+    template <typename T>
+    int BfvMultiplyPlan<T>::max_terms(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* b_moduli_host,
+                                      int b_count, T plain_modulus, int n_power)
+    {
+        rns_check_n_power(n_power);
+        return bfv_derive<T>(q_moduli_host, q_count, b_moduli_host, b_count, plain_modulus, n_power).max_terms;
+    }
+    template <typename T>
+    size_t BfvMultiplyPlan<T>::sum_scratch_bytes(int q_count, int b_count, int n_power, int count, int operands)
+    {
+        bfv_check_counts(q_count, b_count);
+        rns_check_n_power(n_power);
+        return bfv_sum_scratch<T>(q_count, q_count + b_count, n_power, count, operands).total;
+    }
+    template <typename T> size_t BfvMultiplyPlan<T>::sum_scratch_bytes(int count, int operands) const
+    {
+        return bfv_sum_scratch<T>(p_->L, p_->M, p_->n, count, operands).total;
     }
     template <typename T> Modulus<T> BfvMultiplyPlan<T>::modulus(int m) const
     {

@@ -1307,6 +1307,54 @@ extern "C"
                 output_ntt != 0, scratch, key_switch_scratch, static_cast<hipStream_t>(stream));  \
         });                                                                                       \
     }                                                                                             \
+    int gpuntt_bfv_plan_max_terms_##S(const gpuntt_bfv_plan* plan)                                \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return reinterpret_cast<const BfvMultiplyPlan<T>*>(plan)->max_terms();                    \
+    }                                                                                             \
+    int gpuntt_bfv_max_terms_##S(const CM* q_moduli_host, int q_count, const CM* b_moduli_host, int b_count,      \
+                                 T plain_modulus, int n_power, int* terms_host)                   \
+    {                                                                                             \
+        GPUNTT_NEED(terms_host)                                                                   \
+        return guarded([&] {                                                                      \
+            const auto qs = to_mods<T>(q_moduli_host, q_count, "Invalid q_count!");                \
+            const auto bs = to_mods<T>(b_moduli_host, b_count, "Invalid b_count!");                \
+            *terms_host = BfvMultiplyPlan<T>::max_terms(qs.data(), q_count, bs.data(), b_count, plain_modulus,    \
+                                                        n_power);                                 \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_plan_sum_scratch_bytes_##S(int q_count, int b_count, int n_power, int count, int operands,     \
+                                              uint64_t* bytes_host)                               \
+    {                                                                                             \
+        GPUNTT_NEED(bytes_host)                                                                   \
+        return guarded([&] {                                                                      \
+            *bytes_host = BfvMultiplyPlan<T>::sum_scratch_bytes(q_count, b_count, n_power, count, operands);      \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_plan_multiply_sum_##S(const gpuntt_bfv_plan* plan, const T* const* x_host,     \
+                                         const T* const* y_host, int terms, T* out, int count, int input_ntt,     \
+                                         int output_ntt, void* scratch, void* stream)             \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const BfvMultiplyPlan<T>*>(plan)->multiply_sum(                      \
+                x_host, y_host, terms, out, count, input_ntt != 0, output_ntt != 0, scratch,      \
+                static_cast<hipStream_t>(stream));                                                \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_plan_multiply_relinearize_sum_##S(                                             \
+        const gpuntt_bfv_plan* plan, const T* const* x_host, const T* const* y_host, int terms,   \
+        const gpuntt_keyswitch_plan* key_switch, const T* key, T* out, int count, int input_ntt, int output_ntt,  \
+        void* scratch, void* key_switch_scratch, void* stream)                                    \
+    {                                                                                             \
+        GPUNTT_NEED(plan, key_switch)                                                             \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const BfvMultiplyPlan<T>*>(plan)->multiply_relinearize_sum(          \
+                x_host, y_host, terms, *reinterpret_cast<const KeySwitchPlan<T>*>(key_switch), key, out, count,   \
+                input_ntt != 0, output_ntt != 0, scratch, key_switch_scratch,                     \
+                static_cast<hipStream_t>(stream));                                                \
+        });                                                                                       \
+    }                                                                                             \
     int gpuntt_bfv_plan_owns_workspace_##S(const gpuntt_bfv_plan* plan)                           \
     {                                                                                             \
         GPUNTT_NEED(plan)                                                                         \

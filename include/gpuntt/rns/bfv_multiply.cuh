@@ -70,6 +70,60 @@
 //     value, q_count, n_power or the reduction polynomial differs, or one of the two plans has no transforms.  Then
 //     multiply's refusals, a null key or key_switch_scratch, a misaligned key_switch_scratch, and a count beyond
 //     relinearize's limits
+//   multiply_sum(x, y, terms, out, count, input_ntt, output_ntt, scratch):  the sum of `terms` products with ONE division
+//     by Q: round(t * sum_t (x~_t (x) y~_t) / Q).  The tensor is bilinear and the division comes after it, so the sum is
+//     taken in the full base, in NTT form, in exact accumulators, and every later step of multiply runs once whatever
+//     `terms` is.  x, y: HOST arrays of `terms` device pointers (as KeySwitchPlan::multiply_relinearize_sum takes them),
+//     each a batch T[2][count][L][N] with multiply's rules for the words; y[t] may be x[t], and the same pointer may
+//     appear in any number of terms on either side.  out = T[3][count][L][N].  1 <= terms <= BFV_MAX_TERMS
+//     ("Invalid terms!") and terms <= max_terms() ("Auxiliary base too small for these terms!"), both before any launch.
+//     DEFINITION, word for word, through multiply's steps:
+//       1. steps 1 to 3 for every DISTINCT operand pointer
+//       2. step 4 summed: per limb m < M the canonical residues d0 = (sum_t x0_t y0_t) mod m_m,
+//          d1 = (sum_t x0_t y1_t + x1_t y0_t) mod m_m, d2 = (sum_t x1_t y1_t) mod m_m -- each what
+//          InnerProductPlan::multiply_accumulate gives with D = terms for d0 and d2, D = 2 * terms for d1, and C = 1
+//          (BFV_MAX_TERMS keeps 2 * terms inside INNERPROD_MAX_DIGITS)
+//       3. steps 5 to 7 unchanged: ONE full-base GPU_INTT over 3 * count * M polynomials, scale_round over 3 * count
+//          stacks, [the q-base GPU_NTT]
+//     With terms = 1 these are the words of multiply.
+//     Size.  Every extended operand obeys |x~| <= Q (1/2 + eps), so |sum_t d_c| <= terms * 2 N Q^2 (1/2 + eps)^2 and the
+//     argument above needs B >= 2 * terms * t N Q and nothing else.  max_terms() = min(BFV_MAX_TERMS,
+//     floor(B / (2 t N Q))) >= 1 is fixed at construction in exact integers; the constructor's check is its terms = 1 case.
+//     Rounding.  With more terms the result is NOT word for word the sum of `terms` multiply calls: this call rounds
+//     S = t * sum D / Q once, they round `terms` times.  |round(S) - S| <= 1/2 and |sum_t round(a_t) - S| <= terms / 2, so
+//     outside the conversion bands the centred difference per coefficient is at most (terms + 1) / 2; every band hit
+//     (mod_down's documented +- 1) adds at most 1 per rounding, so it is unconditionally at most
+//     (terms + 1) / 2 + terms + 1.
+//     What runs: the DISTINCT operand pointers are collected on the host by pointer equality, U <= 2 * terms of them, so a
+//     squaring or a vector shared by several terms is extended and transformed once.  Per distinct operand [the q-base
+//     INTT and] bfv_extend; ONE full-base NTT over 2 * U * count * M polynomials; ONE bfv_tensor_sum; ONE full-base INTT
+//     over 3 * count * M; ONE bfv_scale_round; [ONE q-base NTT].  Apart from the per-operand step no launch count grows
+//     with terms or count.  Allocates nothing, never synchronises, one stream, capturable as it is; count = 0 launches
+//     nothing.
+//     scratch: sum_scratch_bytes(count, operands) bytes with operands >= U (the call lays it out for exactly U and
+//     uses the first sum_scratch_bytes(count, U) bytes; a wrapper that knows the size of the buffer -- the Python one --
+//     refuses a smaller one; operands outside [1, 2 * BFV_MAX_TERMS]: "Invalid operands!"), 256-byte aligned:
+//     T[max(operands, 2)][2][count][M][N] for the extended
+//     operands, contiguous (bfv_tensor_sum writes d0, d1, d2 over its first three planes, each word by the lane that read
+//     it), and the T[2][count][L][N] coefficient region of multiply, reused operand by operand in stream order.  It
+//     grows linearly with the distinct operands: a caller who cannot afford it splits the sum and adds the parts, at
+//     one rounding per part.
+//     Refusals: multiply's, applied to every operand pointer -- a null pointer (or a null array), overlap with out other
+//     than being exactly out, overlap with the scratch, a misaligned scratch, and the count limits with the widest
+//     transform batch 2 * U * count * M as an int
+//   multiply_relinearize_sum(x, y, terms, key_switch, key, out, count, input_ntt, output_ntt, scratch,
+//     key_switch_scratch):  the summed product, relinearized: an encrypted BFV dot product with ONE t/Q rounding, ONE key
+//     switch and ONE ModDown.  out = T[2][count][L][N].
+//     DEFINITION, word for word:
+//       m = multiply_sum(x, y, terms, count, input_ntt, output_ntt = false)
+//       out = key_switch.relinearize(m[0..1], m[2], key, count, input_ntt = false, output_ntt)
+//     exactly as multiply_relinearize is defined from multiply, and run in the same way: bfv_scale_round over the first
+//     2 * count stacks INTO out, the top component into the coefficient region (dead by then), mod_down_add in place.
+//     With terms = 1 these are the words of multiply_relinearize; with more terms the rounding bounds above hold for
+//     m.  They do not carry over to out word by word: a top component that differs by one is decomposed into other
+//     digits, and the switched words differ by a multiple of the key.  What is close is the decryption, where this call
+//     carries one t/Q rounding and one ModDown rounding and the separate calls `terms` of each.
+//     Refusals: multiply_relinearize's, applied to every operand pointer
 //   scratch: scratch_bytes(count) bytes owned by the CALLER, 256-byte aligned: the operands in the full base
 //     T[4][count][M][N] (x0, x1, y0, y1 -- bfv_tensor writes d0, d1, d2 over the first three, each word by the lane that
 //     read it) and T[2][count][L][N] for the coefficient form of one operand.
@@ -103,6 +157,9 @@
 
 namespace gpuntt
 {
+    // terms of one multiply_sum call at most: the cross term is one exact sum of 2 * terms products
+    constexpr int BFV_MAX_TERMS = 32;
+
     // The plan's constants as the host derived them (BfvMultiplyPlan::constants, gpuntt_bfv_constants_*): every pointer
     // is a caller array of the stated length.
     template <typename T> struct BfvConstants
@@ -140,6 +197,17 @@ namespace gpuntt
                                   const T* device_key, T* device_out, int count, bool input_ntt, bool output_ntt,
                                   void* scratch_device, void* key_switch_scratch_device, stream_t stream) const;
 
+        // sum_t x[t] * y[t] with ONE division by Q; x, y: host arrays of `terms` device pointers ("multiply_sum" above)
+        void multiply_sum(const T* const* device_x_host, const T* const* device_y_host, int terms, T* device_out,
+                          int count, bool input_ntt, bool output_ntt, void* scratch_device, stream_t stream) const;
+        void multiply_relinearize_sum(const T* const* device_x_host, const T* const* device_y_host, int terms,
+                                      const KeySwitchPlan<T>& key_switch, const T* device_key, T* device_out, int count,
+                                      bool input_ntt, bool output_ntt, void* scratch_device,
+                                      void* key_switch_scratch_device, stream_t stream) const;
+        int max_terms() const; // min(BFV_MAX_TERMS, floor(B / (2 t N Q))), fixed at construction; >= 1
+        static size_t sum_scratch_bytes(int q_count, int b_count, int n_power, int count, int operands);
+        size_t sum_scratch_bytes(int count, int operands) const;
+
         int q_count() const;
         int b_count() const;
         Modulus<T> modulus(int m) const;            // modulus m < M of the full base, as the constructor took it
@@ -153,6 +221,10 @@ namespace gpuntt
         // host only (no GPU): the constants of these bases and this t, with the checks of the constructor
         static void constants(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* b_moduli_host, int b_count,
                               T plain_modulus, int n_power, const BfvConstants<T>& out);
+        // host only (no GPU): what max_terms() of a plan of these bases, this t and this ring returns, with the checks of the
+        // constructor
+        static int max_terms(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* b_moduli_host, int b_count,
+                             T plain_modulus, int n_power);
         // host only (no GPU): extend / scale_round on HOST arrays, with unsigned __int128 and %, after the same argument
         // checks.  What tests and examples compare the kernels with; never a GPU fall-back
         static void reference_extend(const Modulus<T>* q_moduli_host, int q_count, const Modulus<T>* b_moduli_host,

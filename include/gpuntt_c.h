@@ -705,6 +705,41 @@ extern "C"
                                                  const gpuntt_keyswitch_plan* key_switch, const uint64_t* key, uint64_t* out,
                                                  int count, int input_ntt, int output_ntt, void* scratch,
                                                  void* key_switch_scratch, void* stream);
+    /* sum_t x_t * y_t over `terms` pairs with ONE division by Q (bfv_multiply.cuh, "multiply_sum"): x_host, y_host are
+       HOST arrays of `terms` device pointers, each T[2][count][L][N]; y[t] may be x[t] and a pointer may appear in several
+       terms -- every distinct pointer is extended and transformed once.  1 <= terms <= 32 and terms <= max_terms
+       (min(32, floor(B / (2 t N Q))); returned by gpuntt_bfv_plan_max_terms_*, negative on error).  The scratch is
+       gpuntt_bfv_plan_sum_scratch_bytes_*(.., count, operands) bytes for operands >= the number of distinct pointers,
+       256-byte aligned.  multiply_sum: out = T[3][count][L][N]; multiply_relinearize_sum: out = T[2][count][L][N], with
+       ONE key switch and ONE ModDown.  With terms = 1 they return the words of multiply / multiply_relinearize; with
+       more terms they round once where `terms` separate calls round `terms` times */
+    int gpuntt_bfv_plan_max_terms_u32(const gpuntt_bfv_plan* plan);
+    int gpuntt_bfv_plan_max_terms_u64(const gpuntt_bfv_plan* plan);
+    /* host only (no GPU): what gpuntt_bfv_plan_max_terms_* of a plan of these bases returns, with the checks of create */
+    int gpuntt_bfv_max_terms_u32(const gpuntt_modulus32* q_moduli_host, int q_count, const gpuntt_modulus32* b_moduli_host,
+                                 int b_count, uint32_t plain_modulus, int n_power, int* terms_host);
+    int gpuntt_bfv_max_terms_u64(const gpuntt_modulus64* q_moduli_host, int q_count, const gpuntt_modulus64* b_moduli_host,
+                                 int b_count, uint64_t plain_modulus, int n_power, int* terms_host);
+    int gpuntt_bfv_plan_sum_scratch_bytes_u32(int q_count, int b_count, int n_power, int count, int operands,
+                                              uint64_t* bytes_host);
+    int gpuntt_bfv_plan_sum_scratch_bytes_u64(int q_count, int b_count, int n_power, int count, int operands,
+                                              uint64_t* bytes_host);
+    int gpuntt_bfv_plan_multiply_sum_u32(const gpuntt_bfv_plan* plan, const uint32_t* const* x_host,
+                                         const uint32_t* const* y_host, int terms, uint32_t* out, int count, int input_ntt,
+                                         int output_ntt, void* scratch, void* stream);
+    int gpuntt_bfv_plan_multiply_sum_u64(const gpuntt_bfv_plan* plan, const uint64_t* const* x_host,
+                                         const uint64_t* const* y_host, int terms, uint64_t* out, int count, int input_ntt,
+                                         int output_ntt, void* scratch, void* stream);
+    int gpuntt_bfv_plan_multiply_relinearize_sum_u32(const gpuntt_bfv_plan* plan, const uint32_t* const* x_host,
+                                                     const uint32_t* const* y_host, int terms,
+                                                     const gpuntt_keyswitch_plan* key_switch, const uint32_t* key,
+                                                     uint32_t* out, int count, int input_ntt, int output_ntt,
+                                                     void* scratch, void* key_switch_scratch, void* stream);
+    int gpuntt_bfv_plan_multiply_relinearize_sum_u64(const gpuntt_bfv_plan* plan, const uint64_t* const* x_host,
+                                                     const uint64_t* const* y_host, int terms,
+                                                     const gpuntt_keyswitch_plan* key_switch, const uint64_t* key,
+                                                     uint64_t* out, int count, int input_ntt, int output_ntt,
+                                                     void* scratch, void* key_switch_scratch, void* stream);
     int gpuntt_bfv_plan_destroy_u32(gpuntt_bfv_plan* plan);
     int gpuntt_bfv_plan_destroy_u64(gpuntt_bfv_plan* plan);
     int gpuntt_bfv_constants_u32(const gpuntt_modulus32* q_moduli_host, int q_count, const gpuntt_modulus32* b_moduli_host,
