@@ -131,9 +131,13 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "bfv_plan_scale_round", "bfv_plan_multiply", "bfv_plan_multiply_relinearize", "bfv_plan_owns_workspace",
               "bfv_plan_destroy", "bfv_plan_max_terms", "bfv_plan_sum_scratch_bytes", "bfv_plan_multiply_sum",
               "bfv_plan_multiply_relinearize_sum", "bfv_max_terms",
-              "bfv_constants", "bfv_reference_extend", "bfv_reference_scale_round")
+              "bfv_constants", "bfv_reference_extend", "bfv_reference_scale_round",
+              "sample_uniform", "sample_reference_uniform", "keyswitch_plan_lift_small",
+              "keyswitch_plan_keygen_scratch_bytes", "keyswitch_plan_encrypt_scratch_bytes",
+              "keyswitch_plan_generate_keys", "keyswitch_plan_encrypt_symmetric")
     for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option", "gpuntt_galois_element_u32",
-                                "gpuntt_automorphism_index_map"]
+                                "gpuntt_automorphism_index_map", "gpuntt_philox4x32_10", "gpuntt_sample_small",
+                                "gpuntt_sample_reference_small"]
 
 # GPUNTT_* environment variables of the A/B scripts and tests -> library options.  The C++ library reads no
 # environment variable; this harness forwards them once, when it loads the library.
@@ -1500,6 +1504,86 @@ class KeySwitchPlan:
         self.linear_transform_bsgs(a, c0, c1, baby_keys, baby_elements, giant_keys, giant_elements, weights, out, count,
                                    output_ntt, scratch, stream, _rescale=True)
 
+    # key material (key_switch.cuh, "Key material")
+    @staticmethod
+    def _check_small(t, words, name):
+        _require_gpu(t)
+        if t.element_size() != 4 or t.dtype.is_floating_point:
+            raise ValueError("%s takes 32-bit signed integer tensors" % name)
+        if words > 0 and t.numel() < words:
+            raise ValueError("%s needs %d words; got %d" % (name, words, t.numel()))
+
+    def _check_aligned_scratch(self, scratch, need, name):
+        _require_gpu(scratch)
+        if scratch.numel() * scratch.element_size() < need:
+            raise ValueError("scratch holds fewer than %s bytes" % name)
+
+    def lift_small(self, small, out, polys, full_base=True, to_ntt=True, stream=None):
+        """small int32[polys][N] (any values) -> out T[polys][M or L][N]: the canonical residue of every signed value under
+        every modulus of the full base (full_base) or the q-base; with to_ntt the plan's forward transform over that base
+        follows in place.  One launch plus the transform's own."""
+        if small is None or out is None:
+            raise ValueError("null pointer argument")
+        cols = self._cols(polys)
+        self._check_small(small, cols, "small (polys x N)")
+        self._check_buffers(((out, cols * (self.mod_count if full_base else self.q_count), "out (polys x B x N)"),))
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_lift_small_u%d" % self.bits)
+        _check(fn(self._h, _ptr(small), _ptr(out), int(polys), int(bool(full_base)), int(bool(to_ntt)),
+                  _stream(stream)))
+
+    def keygen_scratch_bytes(self, keys):
+        out = ctypes.c_uint64()
+        _check(getattr(load_library(), "gpuntt_keyswitch_plan_keygen_scratch_bytes_u%d" % self.bits)(
+            self._h, int(keys), ctypes.byref(out)))
+        return int(out.value)
+
+    def encrypt_scratch_bytes(self, count):
+        out = ctypes.c_uint64()
+        _check(getattr(load_library(), "gpuntt_keyswitch_plan_encrypt_scratch_bytes_u%d" % self.bits)(
+            self._h, int(count), ctypes.byref(out)))
+        return int(out.value)
+
+    def generate_keys(self, s, s_from, errors, keys, scratch, stream=None):
+        """len(keys) <= 64 switching keys to the secret s in one call: s T[M][N] and s_from T[len(keys)][M][N] in NTT form
+        over the full base (lift_small gives them), errors int32[len(keys)][D][N], keys a list of device tensors, each
+        T[D][2][M][N] with component 1 = a on entry (sample_uniform fills it in place); component 0 =
+        E - a s + P g_d s_from is written, a is left untouched.  scratch: at least keygen_scratch_bytes(len(keys)) bytes,
+        256-byte aligned.  Word for word the header's definition (key_switch.cuh)."""
+        keys = list(keys)
+        G = len(keys)
+        if not 0 <= G <= 64:
+            raise ValueError("Invalid keys!")
+        if s is None or s_from is None or errors is None or scratch is None or any(k is None for k in keys):
+            raise ValueError("null pointer argument")
+        stack = self.mod_count << self.n_power
+        self._check_buffers([(s, stack, "s (M x N)"), (s_from, stack * G, "s_from (keys x M x N)")] +
+                            [(k, 2 * self.digits * stack, "key (D x 2 x M x N)") for k in keys])
+        self._check_small(errors, (G * self.digits) << self.n_power, "errors (keys x D x N)")
+        self._check_aligned_scratch(scratch, self.keygen_scratch_bytes(G), "keygen_scratch_bytes(keys)")
+        key_ptrs = (ctypes.c_void_p * max(1, G))(*[k.data_ptr() for k in keys])
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_generate_keys_u%d" % self.bits)
+        _check(fn(self._h, _ptr(s), _ptr(s_from), _ptr(errors), key_ptrs, G, _ptr(scratch), _stream(stream)))
+
+    def encrypt_symmetric(self, s, errors, message, out, count, scratch, stream=None):
+        """`count` symmetric encryptions under s T[M][N] (NTT form; the first L limbs are read): out T[2][count][L][N] with
+        out[1] = a on entry (left untouched), errors int32[count][N], message T[count][L][N] in NTT form or None (an
+        encryption of zero: a public key); out[0] = E - a s + message is written.  scratch: at least
+        encrypt_scratch_bytes(count) bytes, 256-byte aligned."""
+        if s is None or errors is None or out is None or scratch is None:
+            raise ValueError("null pointer argument")
+        cols = self._cols(count)
+        sized = [(s, self.q_count << self.n_power, "s (L x N at least)"),
+                 (out, 2 * cols * self.q_count, "out (2 x count x L x N)")]
+        if message is not None:
+            sized.append((message, cols * self.q_count, "message (count x L x N)"))
+        self._check_buffers(sized)
+        self._check_small(errors, cols, "errors (count x N)")
+        if int(count) >= 0:
+            self._check_aligned_scratch(scratch, self.encrypt_scratch_bytes(count), "encrypt_scratch_bytes(count)")
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_encrypt_symmetric_u%d" % self.bits)
+        _check(fn(self._h, _ptr(s), _ptr(errors), _ptr(message), _ptr(out), int(count), _ptr(scratch),
+                  _stream(stream)))
+
     def close(self):
         if self._h:
             getattr(load_library(), "gpuntt_keyswitch_plan_destroy_u%d" % self.bits)(self._h)
@@ -1510,6 +1594,90 @@ class KeySwitchPlan:
             self.close()
         except Exception:
             pass
+
+
+# ------------------------------------------------------------------------- samplers (rns/sampling.cuh)
+TERNARY, CBD21 = 0, 1
+SAMPLE_MAX_CANDIDATES = 32
+
+
+def philox4x32_10(ctr, key):
+    """Host (no GPU): the standard Philox4x32-10 block of the 4 counter words and 2 key words, as 4 ints"""
+    c = (ctypes.c_uint32 * 4)(*[int(v) & 0xFFFFFFFF for v in ctr])
+    k = (ctypes.c_uint32 * 2)(*[int(v) & 0xFFFFFFFF for v in key])
+    out = (ctypes.c_uint32 * 4)()
+    _check(load_library().gpuntt_philox4x32_10(c, k, out))
+    return [int(v) for v in out]
+
+
+def _sample_args(moduli, n_power, stacks, stack_stride_words, bits):
+    vals = [int(getattr(m, "value", m)) for m in moduli]
+    if not 1 <= len(vals) <= 256:
+        raise ValueError("Invalid mod_count!")
+    if any(not 0 < v < (1 << bits) for v in vals):
+        raise ValueError("Invalid modulus!")
+    dense = len(vals) << int(n_power)
+    stride = dense if stack_stride_words is None else int(stack_stride_words)
+    if stride < dense:
+        raise ValueError("Invalid stack stride!")
+    words = (int(stacks) - 1) * stride + dense if int(stacks) > 0 else 0
+    return (_ct(bits) * len(vals))(*vals), len(vals), stride, words
+
+
+def sample_uniform(out, moduli, n_power, stacks, seed, stream_id=0, stack_stride_words=None, stream=None):
+    """Fill out T[stacks][len(moduli)][N] (stack s at s x stack_stride_words, default dense) with uniform residues:
+    a pure function of (seed, stream_id, word index), restated in tests/sampling_exact.py.  NOT a cryptographic
+    generator (sampling.cuh).  One launch; 16-byte stores where out and the stride allow."""
+    if out is None:
+        raise ValueError("null pointer argument")
+    _require_gpu(out)
+    bits = out.element_size() * 8
+    if bits not in (32, 64) or out.dtype.is_floating_point:
+        raise ValueError("sample_uniform fills 32- or 64-bit integer tensors")
+    arr, count, stride, words = _sample_args(moduli, n_power, stacks, stack_stride_words, bits)
+    if out.numel() < words:
+        raise ValueError("out needs %d words; got %d" % (words, out.numel()))
+    fn = getattr(load_library(), "gpuntt_sample_uniform_u%d" % bits)
+    _check(fn(_ptr(out), arr, count, int(n_power), int(stacks), ctypes.c_uint64(stride),
+              ctypes.c_uint64(int(seed) & (2**64 - 1)), ctypes.c_uint32(int(stream_id) & 0xFFFFFFFF), _stream(stream)))
+
+
+def sample_small(out, polys, n_power, distribution, seed, stream_id=0, stream=None):
+    """Fill out int32[polys][N] with TERNARY (uniform on -1, 0, 1) or CBD21 (centred binomial, variance 10.5) values, a
+    pure function of (seed, stream_id, word index).  One launch."""
+    if out is None:
+        raise ValueError("null pointer argument")
+    _require_gpu(out)
+    if out.element_size() != 4 or out.dtype.is_floating_point:
+        raise ValueError("sample_small fills 32-bit signed integer tensors")
+    if int(polys) > 0 and out.numel() < int(polys) << int(n_power):
+        raise ValueError("out needs %d words; got %d" % (int(polys) << int(n_power), out.numel()))
+    _check(load_library().gpuntt_sample_small(
+        _ptr(out), int(polys), int(n_power), int(distribution), ctypes.c_uint64(int(seed) & (2**64 - 1)),
+        ctypes.c_uint32(int(stream_id) & 0xFFFFFFFF), _stream(stream)))
+
+
+def sample_reference_uniform(moduli, n_power, stacks, seed, stream_id=0, stack_stride_words=None, bits=64,
+                             max_candidates=SAMPLE_MAX_CANDIDATES, fill=0):
+    """Host (no GPU): sample_uniform's words as a numpy array of (stacks - 1) x stride + len(moduli) x N words, the gaps
+    between strided stacks left at `fill`; max_candidates < 32 reaches the `r mod q` tail"""
+    arr, count, stride, words = _sample_args(moduli, n_power, stacks, stack_stride_words, bits)
+    out = np.full(max(1, words), fill, dtype=np_dtype(bits))
+    fn = getattr(load_library(), "gpuntt_sample_reference_uniform_u%d" % bits)
+    _check(fn(out.ctypes.data_as(ctypes.c_void_p), arr, count, int(n_power), int(stacks), ctypes.c_uint64(stride),
+              ctypes.c_uint64(int(seed) & (2**64 - 1)), ctypes.c_uint32(int(stream_id) & 0xFFFFFFFF),
+              int(max_candidates)))
+    return out[:words]
+
+
+def sample_reference_small(polys, n_power, distribution, seed, stream_id=0):
+    """Host (no GPU): sample_small's words as a numpy int32 array of polys x N"""
+    words = int(polys) << int(n_power) if int(polys) > 0 else 0
+    out = np.zeros(max(1, words), dtype=np.int32)
+    _check(load_library().gpuntt_sample_reference_small(
+        out.ctypes.data_as(ctypes.c_void_p), int(polys), int(n_power), int(distribution),
+        ctypes.c_uint64(int(seed) & (2**64 - 1)), ctypes.c_uint32(int(stream_id) & 0xFFFFFFFF)))
+    return out[:words]
 
 
 def bfv_constants(q_moduli, b_moduli, plain_modulus, n_power, bits=64):

@@ -14,6 +14,7 @@
 #include "gpuntt/rns/bfv_multiply.cuh"
 #include "gpuntt/rns/inner_product.cuh"
 #include "gpuntt/rns/key_switch.cuh"
+#include "gpuntt/rns/sampling.cuh"
 #include "gpuntt_c.h"
 #include "hoisted_rotation_internal.hpp"
 #include "test_hooks.h"
@@ -549,6 +550,29 @@ extern "C"
         return 0;
     }
 
+    int gpuntt_philox4x32_10(const uint32_t* ctr4_host, const uint32_t* key2_host, uint32_t* out4_host)
+    {
+        GPUNTT_NEED(ctr4_host, key2_host, out4_host)
+        return guarded([&] { reference_philox(ctr4_host, key2_host, out4_host); });
+    }
+    int gpuntt_sample_small(int32_t* out, int polys, int n_power, int distribution, uint64_t seed, uint32_t stream_id,
+                            void* stream)
+    {
+        GPUNTT_NEED(out)
+        return guarded([&] {
+            sample_small(out, polys, n_power, static_cast<SmallDistribution>(distribution), seed, stream_id,
+                         static_cast<hipStream_t>(stream));
+        });
+    }
+    int gpuntt_sample_reference_small(int32_t* out_host, int polys, int n_power, int distribution, uint64_t seed,
+                                      uint32_t stream_id)
+    {
+        GPUNTT_NEED(out_host)
+        return guarded([&] {
+            reference_sample_small(out_host, polys, n_power, static_cast<SmallDistribution>(distribution), seed,
+                                   stream_id);
+        });
+    }
     int gpuntt_galois_element_u32(int steps, int n_power, int conjugation, uint32_t* elt_host)
     {
         GPUNTT_NEED(elt_host)
@@ -1056,6 +1080,70 @@ extern "C"
     {                                                                                             \
         GPUNTT_NEED(plan)                                                                         \
         return reinterpret_cast<const KeySwitchPlan<T>*>(plan)->owns_workspace() ? 1 : 0;         \
+    }                                                                                             \
+    int gpuntt_sample_uniform_##S(T* out, const T* moduli_host, int mod_count, int n_power, int stacks,\
+                                  uint64_t stack_stride_words, uint64_t seed, uint32_t stream_id, void* stream)\
+    {                                                                                             \
+        GPUNTT_NEED(out, moduli_host)                                                             \
+        return guarded([&] {                                                                      \
+            sample_uniform<T>(out, moduli_host, mod_count, n_power, stacks, stack_stride_words, seed, stream_id,\
+                              static_cast<hipStream_t>(stream));                                  \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_sample_reference_uniform_##S(T* out_host, const T* moduli_host, int mod_count, int n_power,\
+                                            int stacks, uint64_t stack_stride_words, uint64_t seed,\
+                                            uint32_t stream_id, int max_candidates)               \
+    {                                                                                             \
+        GPUNTT_NEED(out_host, moduli_host)                                                        \
+        return guarded([&] {                                                                      \
+            reference_sample_uniform<T>(out_host, moduli_host, mod_count, n_power, stacks, stack_stride_words,\
+                                        seed, stream_id, max_candidates);                         \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_lift_small_##S(const gpuntt_keyswitch_plan* plan, const int32_t* small, T* out,\
+                                             int polys, int full_base, int to_ntt, void* stream)  \
+    {                                                                                             \
+        GPUNTT_NEED(plan, small, out)                                                             \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->lift_small(                          \
+                small, out, polys, full_base != 0, to_ntt != 0, static_cast<hipStream_t>(stream));\
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_keygen_scratch_bytes_##S(const gpuntt_keyswitch_plan* plan, int keys,\
+                                                       uint64_t* bytes_host)                      \
+    {                                                                                             \
+        GPUNTT_NEED(plan, bytes_host)                                                             \
+        return guarded([&] {                                                                      \
+            *bytes_host = reinterpret_cast<const KeySwitchPlan<T>*>(plan)->keygen_scratch_bytes(keys);\
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_encrypt_scratch_bytes_##S(const gpuntt_keyswitch_plan* plan, int count,\
+                                                        uint64_t* bytes_host)                     \
+    {                                                                                             \
+        GPUNTT_NEED(plan, bytes_host)                                                             \
+        return guarded([&] {                                                                      \
+            *bytes_host = reinterpret_cast<const KeySwitchPlan<T>*>(plan)->encrypt_scratch_bytes(count);\
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_generate_keys_##S(const gpuntt_keyswitch_plan* plan, const T* s, const T* s_from,\
+                                                const int32_t* errors, T* const* keys_host, int keys,\
+                                                void* scratch, void* stream)                      \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->generate_keys(                       \
+                s, s_from, errors, keys_host, keys, scratch, static_cast<hipStream_t>(stream));   \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_encrypt_symmetric_##S(const gpuntt_keyswitch_plan* plan, const T* s,\
+                                                    const int32_t* errors, const T* message, T* out, int count,\
+                                                    void* scratch, void* stream)                  \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->encrypt_symmetric(                   \
+                s, errors, message, out, count, scratch, static_cast<hipStream_t>(stream));       \
+        });                                                                                       \
     }                                                                                             \
     int gpuntt_keyswitch_plan_destroy_##S(gpuntt_keyswitch_plan* plan)                            \
     {                                                                                             \

@@ -48,6 +48,11 @@
 // form mod_up, the transforms and the plain inner product, then mod_down_add -- mod_down's kernel with an addend epilogue
 // (base_conversion_internal.hpp) -- so c01 is never transformed on its own.
 //
+// Key material.  lift_small, generate_keys and encrypt_symmetric make what every call above reads:
+// lift_small of keygen.hip takes signed errors into the base, the plan's forward transform follows, and keygen_combine
+// (one launch over all keys and digits) forms E - a s + P g_d s_from with the exact accumulator.  encrypt_symmetric is the
+// same kernel over the q-base with the message in the gadget term's place.
+//
 // Rescaling (a plan built with rescale_limbs = R > 0).  mod_down_rescale is mod_down's launch with a second
 // constants image, {q_{L-R} .. q_{L-1}, p_0 .. p_{K-1}} -> {q_0 .. q_{L-R-1}}: the R dropped q-limbs and the K special
 // limbs are one contiguous run of the full-base stack, (L - R) N words behind its start, so the strided kernel reads them
@@ -68,6 +73,7 @@
 #include "gpuntt/ntt_merge/ntt.cuh"
 #include "gpuntt/rns/key_switch.cuh"
 #include "hoisted_rotation_internal.hpp"
+#include "keygen_internal.hpp"
 #include "launch.hpp"
 #include "relinearize_internal.hpp"
 #include "relinearize_sum_internal.hpp"
@@ -1085,7 +1091,174 @@ namespace gpuntt
             host::relin_seeded_launch<T>(a, key, acc, consts, c01, args, D, count, L, M, KM, n, true, stream);
             finish(acc, out, 2 * count, output_ntt, false, stream);
         }
+
+        // Key material (keygen.hip)
+
+        // small: int32[polys][N] -> out: T[polys][B][N], B = M (full_base) or L
+        void lift_small(const std::int32_t* small, T* out, int polys, bool full_base, bool to_ntt, hipStream_t stream) const
+        {
+            if (to_ntt)
+                need_transforms();
+            if (polys < 0)
+                throw std::invalid_argument("Invalid polys!");
+            if (small == nullptr || out == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            const int B = full_base ? M : L;
+            if (static_cast<unsigned long long>(polys) * static_cast<unsigned>(B) > 0x7FFFFFFFull) // the transforms' batch
+                throw std::invalid_argument("Invalid polys!");
+            if (polys == 0)
+                return;
+            const std::uint64_t cols = static_cast<std::uint64_t>(polys) << n;
+            if (rns_overlap(small, cols * sizeof(std::int32_t), out, cols * B * sizeof(T)))
+                throw std::invalid_argument("The lift's input and output overlap!");
+            const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
+            host::keygen_lift_launch<T>(small, out, consts, polys, B, M, n, false, stream);
+            host::keygen_lift_launch<T>(small, out, consts, polys, B, M, n, true, stream);
+            if (to_ntt)
+                (full_base ? ntt_full_f : ntt_q_f)->execute(out, out, polys * B, stream);
+        }
+
+        size_t keygen_scratch(int keys) const // E: T[keys][D][M][N]
+        {
+            if (keys < 0 || keys > KEYGEN_MAX_KEYS)
+                throw std::invalid_argument("Invalid keys!");
+            return rns_align(((static_cast<size_t>(keys) * D * M) << n) * sizeof(T));
+        }
+        size_t encrypt_scratch(int count) const // E: T[count][L][N]
+        {
+            if (count < 0)
+                throw std::invalid_argument("Invalid count!");
+            return rns_align(((static_cast<size_t>(count) * L) << n) * sizeof(T));
+        }
+
+        // s: T[M][N], s_from: T[keys][M][N], errors: int32[keys][D][N], key_ptrs: a host array of `keys` device
+        // pointers to T[D][2][M][N]; the scratch: keygen_scratch(keys)
+        void generate_keys(const T* s, const T* s_from, const std::int32_t* errors, T* const* key_ptrs, int keys,
+                           void* scratch, hipStream_t stream) const
+        {
+            need_transforms();
+            const size_t e_bytes = keygen_scratch(keys); // checks keys
+            if (KM != M)
+                throw std::invalid_argument("Keys are generated by the plan of the level they are laid out for!");
+            for (int m = 0; m < M; m++)
+                if (limbs[m] != m)
+                    throw std::invalid_argument("Keys are generated by the plan of the level they are laid out for!");
+            if (s == nullptr || s_from == nullptr || errors == nullptr || key_ptrs == nullptr || scratch == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            for (int g = 0; g < keys; g++)
+                if (key_ptrs[g] == nullptr)
+                    throw std::invalid_argument("null pointer argument");
+            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
+                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            if (keys == 0)
+                return;
+            const std::uint64_t stack = (static_cast<std::uint64_t>(M) << n) * sizeof(T);
+            const std::uint64_t key_bytes = stack * 2 * D, from_bytes = stack * keys;
+            const std::uint64_t err_bytes = ((static_cast<std::uint64_t>(keys) * D) << n) * sizeof(std::int32_t);
+            const std::pair<const void*, std::uint64_t> inputs[] = {{s, stack}, {s_from, from_bytes}, {errors, err_bytes}};
+            for (const auto& op : inputs)
+            {
+                if (rns_overlap(scratch, e_bytes, op.first, op.second))
+                    throw std::invalid_argument("The scratch overlaps an operand!");
+                for (int g = 0; g < keys; g++)
+                    if (rns_overlap(key_ptrs[g], key_bytes, op.first, op.second))
+                        throw std::invalid_argument("A key overlaps an operand!");
+            }
+            for (int g = 0; g < keys; g++)
+            {
+                if (rns_overlap(key_ptrs[g], key_bytes, scratch, e_bytes))
+                    throw std::invalid_argument("The scratch overlaps a key!");
+                for (int o = g + 1; o < keys; o++)
+                    if (rns_overlap(key_ptrs[g], key_bytes, key_ptrs[o], key_bytes))
+                        throw std::invalid_argument("Two keys overlap!");
+            }
+            kern::KeygenArgs<T> args{};
+            for (int g = 0; g < keys; g++)
+                args.group[g] = key_ptrs[g];
+            for (int j = 0; j < L; j++)
+                args.mult[j] = p_mod_q[j];
+            const unsigned long long poly = 1ull << n;
+            const kern::KeygenShape shape{2 * M * poly, M * poly, M * poly, 0, D, M, L, alpha};
+            T* e = static_cast<T*>(scratch);
+            const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
+            // the grid limits of both kernels, before the first launch
+            host::keygen_lift_launch<T>(errors, e, consts, keys * D, M, M, n, false, stream);
+            host::keygen_combine_launch<T>(e, s, s_from, args, shape, keys, consts, M, n, false, stream);
+            host::keygen_lift_launch<T>(errors, e, consts, keys * D, M, M, n, true, stream);
+            ntt_full_f->execute(e, e, keys * D * M, stream);
+            host::keygen_combine_launch<T>(e, s, s_from, args, shape, keys, consts, M, n, true, stream);
+        }
+
+        // s: T[M][N] (the first L limbs are read), errors: int32[count][N], message: T[count][L][N] or nullptr,
+        // out: T[2][count][L][N] with out[1] = a; the scratch: encrypt_scratch(count)
+        void encrypt_symmetric(const T* s, const std::int32_t* errors, const T* message, T* out, int count, void* scratch,
+                               hipStream_t stream) const
+        {
+            need_transforms();
+            const size_t e_bytes = encrypt_scratch(count); // checks count
+            if (s == nullptr || errors == nullptr || out == nullptr || scratch == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
+                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            if (static_cast<unsigned long long>(count) * static_cast<unsigned>(L) > 0x7FFFFFFFull)
+                throw std::invalid_argument("Invalid count!");
+            if (count == 0)
+                return;
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T), msg_bytes = cols * L * sizeof(T);
+            const std::pair<const void*, std::uint64_t> inputs[] = {
+                {s, (static_cast<std::uint64_t>(L) << n) * sizeof(T)}, {errors, cols * sizeof(std::int32_t)},
+                {message, message != nullptr ? msg_bytes : 0}};
+            for (const auto& op : inputs)
+                if (op.first != nullptr &&
+                    (rns_overlap(scratch, e_bytes, op.first, op.second) || rns_overlap(out, ct_bytes, op.first, op.second)))
+                    throw std::invalid_argument("out or the scratch overlaps an operand!");
+            if (rns_overlap(out, ct_bytes, scratch, e_bytes))
+                throw std::invalid_argument("The scratch overlaps out!");
+            kern::KeygenArgs<T> args{};
+            args.group[0] = out;
+            for (int j = 0; j < L; j++)
+                args.mult[j] = T(1);
+            const unsigned long long poly = 1ull << n;
+            const kern::KeygenShape shape{L * poly, cols * L, 0, L * poly, count, L, L, 0};
+            T* e = static_cast<T*>(scratch);
+            const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
+            host::keygen_lift_launch<T>(errors, e, consts, count, L, M, n, false, stream);
+            host::keygen_combine_launch<T>(e, s, message, args, shape, 1, consts, M, n, false, stream);
+            host::keygen_lift_launch<T>(errors, e, consts, count, L, M, n, true, stream);
+            ntt_q_f->execute(e, e, count * L, stream);
+            host::keygen_combine_launch<T>(e, s, message, args, shape, 1, consts, M, n, true, stream);
+        }
     };
+
+    template <typename T>
+    void KeySwitchPlan<T>::lift_small(const std::int32_t* device_small, T* device_out, int polys, bool full_base,
+                                      bool to_ntt, stream_t stream) const
+    {
+        p_->lift_small(device_small, device_out, polys, full_base, to_ntt, stream);
+    }
+    template <typename T> size_t KeySwitchPlan<T>::keygen_scratch_bytes(int keys) const
+    {
+        return p_->keygen_scratch(keys);
+    }
+    template <typename T> size_t KeySwitchPlan<T>::encrypt_scratch_bytes(int count) const
+    {
+        return p_->encrypt_scratch(count);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::generate_keys(const T* device_s_ntt, const T* device_s_from_ntt,
+                                         const std::int32_t* device_errors, T* const* device_keys_host, int keys,
+                                         void* scratch_device, stream_t stream) const
+    {
+        p_->generate_keys(device_s_ntt, device_s_from_ntt, device_errors, device_keys_host, keys, scratch_device, stream);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::encrypt_symmetric(const T* device_s_ntt, const std::int32_t* device_errors,
+                                             const T* device_message_ntt, T* device_out, int count, void* scratch_device,
+                                             stream_t stream) const
+    {
+        p_->encrypt_symmetric(device_s_ntt, device_errors, device_message_ntt, device_out, count, scratch_device, stream);
+    }
 
     template <typename T> int KeySwitchPlan<T>::digits(int q_count, int alpha)
     {

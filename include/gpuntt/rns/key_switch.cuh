@@ -324,6 +324,45 @@
 //     stream once each: up to eight host waits per plan, none afterwards.  With R = 0 workspace_bytes, the waits and every
 //     launch are those of a plan built without the argument
 //
+// Key material.  THE KEY CONVENTION, stated once: a switching key from the secret s_from to the secret s is
+//   key = T[D][2][M][N] in NTT form over the full base,  key[d] = (-a_d s + e_d + P g_d s_from,  a_d),
+//   g_d = (Q / Q_d) [(Q / Q_d)^-1 mod Q_d]  -- so P g_d is (P mod q_m) on the limbs m of digit d and 0 on every other
+//   limb, the special limbs included --, a_d uniform, e_d small.  A relinearization key has s_from = s^2 (a pointwise
+//   product in NTT form), the key of the automorphism k has s_from = sigma_k(s) (GPU_Automorphism_NTT).  A ciphertext is
+//   (c0, c1) with c0 + c1 s = m + e.  The three calls below make such keys and ciphertexts on the device; their
+//   randomness comes in as buffers (rns/sampling.cuh fills them for tests and benchmarks; a production caller uses its
+//   own generator).
+//   lift_small(small, out, polys, full_base, to_ntt):  small = int32[polys][N], any value; out = T[polys][B][N] with
+//     B = M (full_base) or L.  out[p][m][j] = the canonical residue of the signed value small[p][j] modulo modulus m;
+//     with to_ntt the plan's forward transform over that base follows in place (polys * B polynomials).  This is how a
+//     caller obtains s in the form the calls below read.  ONE launch (lift_small) plus the transform's own; no scratch;
+//     allocates nothing, never synchronises; polys = 0 launches nothing.  std::invalid_argument: polys < 0 or
+//     polys * B beyond an int, a null pointer, small overlapping out, to_ntt on a plan without transforms
+//   generate_keys(s_ntt, s_from_ntt, errors, keys_host, keys, scratch):  0 <= keys <= KEYGEN_MAX_KEYS = 64.
+//     s_ntt = T[M][N], the target secret over the full base in NTT form, any word, read modulo modulus m;
+//     s_from_ntt = T[keys][M][N], the source secrets, likewise; errors = int32[keys][D][N]; keys_host = a HOST array of
+//     `keys` device pointers, each T[D][2][M][N]: component 1 holds a on entry (any word) and is left untouched,
+//     component 0 is written.  DEFINITION, word for word, with E = the full-base GPU_NTT of lift_small(errors):
+//       key[g][d][0][m][j] = (E[g][d][m][j] - a[g][d][m][j] s[m][j] + [m in S_d] (P mod q_m) s_from[g][m][j]) mod m_m,
+//     canonical; the gadget term is absent on every limb outside digit d and on the special limbs.
+//     What runs: lift_small into the scratch T[keys][D][M][N], ONE full-base NTT over keys * D * M polynomials, ONE
+//     launch of keygen_combine over all keys (the key pointers travel in the kernel argument, as rotate_hoisted's do).
+//     Allocates nothing, never synchronises, capturable as it is; keys = 0 launches nothing.  The scratch is
+//     keygen_scratch_bytes(keys) bytes, 256-byte aligned.  std::invalid_argument, before anything is launched: keys
+//     outside [0, 64]; a null pointer or a null entry; an overlap among the scratch, the keys, the secrets and the
+//     errors; a misaligned scratch; a plan without transforms; a plan whose key_mod_count != M or whose key_limbs is not
+//     the identity -- keys are generated by the plan of the level they are laid out for, lower-level plans read them
+//     through key_limbs
+//   encrypt_symmetric(s_ntt, errors, message_ntt, out, count, scratch):  out = T[2][count][L][N] with out[1] = a on
+//     entry (any word), untouched; errors = int32[count][N]; message_ntt = T[count][L][N] in NTT form over the q-base
+//     (any word) or nullptr -- an encryption of zero, which is also how a public key is made.  Only the first L limbs of
+//     s_ntt are read.  DEFINITION, with E = the q-base GPU_NTT of lift_small(errors):
+//       out[0][r][m][j] = (E[r][m][j] - a[r][m][j] s[m][j] + message[r][m][j]) mod q_m, canonical.
+//     The same kernel over the first L limbs, one row per ciphertext, the message in the gadget term's place with
+//     multiplier 1.  The scratch is encrypt_scratch_bytes(count) bytes (T[count][L][N]), 256-byte aligned; refusals as
+//     for generate_keys (count < 0 in the place of keys).  Not here: public-key encryption, coefficient-form output,
+//     fixed-Hamming-weight secrets, BGV error scaling, a sampler fused into the combine kernel
+//
 //   * ranges: 1 <= L, 1 <= K, M = L + K <= 64, alpha >= 1, 1 <= components <= 4, count >= 0 and stacks >= 0 (0: nothing
 //     happens), n_power in [1, 28], M <= key_mod_count <= 256.  A plan is built for ONE level (one L) and one ring; a
 //     caller at a lower level builds another plan and points it at the full-level key through key_mod_count /
@@ -362,6 +401,7 @@ namespace gpuntt
     constexpr int KEYSWITCH_MAX_TERMS = 32; // multiply_relinearize_sum: pairs of ciphertexts per call
     constexpr int KEYSWITCH_MAX_DIAGONALS = 256; // linear_transform_bsgs: n1 * n2, the weight pointers of one call
     constexpr int KEYSWITCH_MAX_STEPS = 64;      // linear_transform_bsgs: n1 and n2 each
+    constexpr int KEYGEN_MAX_KEYS = 64;          // generate_keys: switching keys per call
 
     // The plan's constants as the host derived them (KeySwitchPlan::constants, gpuntt_keyswitch_constants_*): every
     // pointer is a caller array of the stated length.  d(i) = i / alpha is the digit of q-limb i.
@@ -462,6 +502,16 @@ namespace gpuntt
                                            int n2, const T* const* weights_host, T* device_out, int count,
                                            bool output_ntt, void* scratch_device, stream_t stream) const;
         size_t bsgs_scratch_bytes(int count, int n1, int n2) const;
+
+        // key material ("Key material" above)
+        void lift_small(const std::int32_t* device_small, T* device_out, int polys, bool full_base, bool to_ntt,
+                        stream_t stream) const;
+        size_t keygen_scratch_bytes(int keys) const;   // T[keys][D][M][N]
+        size_t encrypt_scratch_bytes(int count) const; // T[count][L][N]
+        void generate_keys(const T* device_s_ntt, const T* device_s_from_ntt, const std::int32_t* device_errors,
+                           T* const* device_keys_host, int keys, void* scratch_device, stream_t stream) const;
+        void encrypt_symmetric(const T* device_s_ntt, const std::int32_t* device_errors, const T* device_message_ntt,
+                               T* device_out, int count, void* scratch_device, stream_t stream) const;
 
         int q_count() const;
         int rescale_limbs() const; // R

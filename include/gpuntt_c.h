@@ -34,7 +34,11 @@
  *                               multiply-accumulate over digits and key components, one kernel launch per call
  *   gpuntt_keyswitch_*          extension hybrid key switching (include/gpuntt/rns/key_switch.cuh): one plan for the
  *                               digit partition, ModUp of all digits in one launch, the inner product, the transforms
- *                               and ModDown in place inside the stacks; host-only constants and references
+ *                               and ModDown in place inside the stacks; host-only constants and references;
+ *                               key material: lift_small, generate_keys, encrypt_symmetric
+ *   gpuntt_sample_*, gpuntt_philox4x32_10
+ *                               extension counter-based samplers (include/gpuntt/rns/sampling.cuh): uniform residues and
+ *                               small polynomials, with host references; not a cryptographic generator
  *   gpuntt_operator_gpu_*       diagnostic: the public device class OPERATOR_GPU<T>
  *                               (src/include/gpuntt/common/modular_arith.cuh:174-454) applied elementwise
  *
@@ -798,6 +802,61 @@ extern "C"
                                     void* stream);
     int gpuntt_generate_4step_w_u64(uint64_t* out, uint64_t root, gpuntt_modulus64 modulus, int n_power, int ntt_type,
                                     void* stream);
+
+    /* ---- counter-based samplers (include/gpuntt/rns/sampling.cuh) -- NOT a cryptographic generator: tests, benchmarks
+     * and reproducible experiments.  Every word is a pure function of (seed, stream_id, word index).
+     *   philox4x32_10: the standard Philox4x32 with ten rounds, on the host.
+     *   sample_uniform: out T[stacks][mod_count][N] on the device, stack s at s * stack_stride_words (>= mod_count * N),
+     *     moduli_host mod_count HOST values (1 .. 256 of them, none 0); bounded rejection over 32 candidates.
+     *   sample_small: out int32[polys][N] on the device; distribution GPUNTT_SAMPLE_TERNARY (uniform on -1, 0, 1) or
+     *     GPUNTT_SAMPLE_CBD21 (centred binomial, variance 10.5).
+     *   sample_reference_*: the same words on HOST arrays (no GPU); max_candidates >= 1 (the device uses 32). */
+#define GPUNTT_SAMPLE_TERNARY 0
+#define GPUNTT_SAMPLE_CBD21 1
+    int gpuntt_philox4x32_10(const uint32_t* ctr4_host, const uint32_t* key2_host, uint32_t* out4_host);
+    int gpuntt_sample_uniform_u32(uint32_t* out, const uint32_t* moduli_host, int mod_count, int n_power, int stacks,
+                                  uint64_t stack_stride_words, uint64_t seed, uint32_t stream_id, void* stream);
+    int gpuntt_sample_uniform_u64(uint64_t* out, const uint64_t* moduli_host, int mod_count, int n_power, int stacks,
+                                  uint64_t stack_stride_words, uint64_t seed, uint32_t stream_id, void* stream);
+    int gpuntt_sample_small(int32_t* out, int polys, int n_power, int distribution, uint64_t seed, uint32_t stream_id,
+                            void* stream);
+    int gpuntt_sample_reference_uniform_u32(uint32_t* out_host, const uint32_t* moduli_host, int mod_count, int n_power,
+                                            int stacks, uint64_t stack_stride_words, uint64_t seed, uint32_t stream_id,
+                                            int max_candidates);
+    int gpuntt_sample_reference_uniform_u64(uint64_t* out_host, const uint64_t* moduli_host, int mod_count, int n_power,
+                                            int stacks, uint64_t stack_stride_words, uint64_t seed, uint32_t stream_id,
+                                            int max_candidates);
+    int gpuntt_sample_reference_small(int32_t* out_host, int polys, int n_power, int distribution, uint64_t seed,
+                                      uint32_t stream_id);
+
+    /* ---- KeySwitchPlan<T>: key material (include/gpuntt/rns/key_switch.cuh, "Key material") ----
+     *   lift_small: small int32[polys][N] -> out T[polys][M or L][N], the canonical residues; to_ntt: the plan's forward
+     *     transform over that base follows in place.
+     *   generate_keys: s T[M][N] and s_from T[keys][M][N] in NTT form over the full base, errors int32[keys][D][N],
+     *     keys_host a HOST array of `keys` (0 .. 64) device pointers, each T[D][2][M][N] with component 1 = a on entry;
+     *     component 0 = E - a s + P g_d s_from is written.  The scratch is keygen_scratch_bytes bytes, 256-byte aligned.
+     *   encrypt_symmetric: out T[2][count][L][N] with out[1] = a on entry; out[0] = E - a s + message is written; message
+     *     T[count][L][N] in NTT form or NULL; errors int32[count][N].  The scratch is encrypt_scratch_bytes bytes. */
+    int gpuntt_keyswitch_plan_lift_small_u32(const gpuntt_keyswitch_plan* plan, const int32_t* small, uint32_t* out,
+                                             int polys, int full_base, int to_ntt, void* stream);
+    int gpuntt_keyswitch_plan_lift_small_u64(const gpuntt_keyswitch_plan* plan, const int32_t* small, uint64_t* out,
+                                             int polys, int full_base, int to_ntt, void* stream);
+    int gpuntt_keyswitch_plan_keygen_scratch_bytes_u32(const gpuntt_keyswitch_plan* plan, int keys, uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_keygen_scratch_bytes_u64(const gpuntt_keyswitch_plan* plan, int keys, uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_encrypt_scratch_bytes_u32(const gpuntt_keyswitch_plan* plan, int count, uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_encrypt_scratch_bytes_u64(const gpuntt_keyswitch_plan* plan, int count, uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_generate_keys_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* s, const uint32_t* s_from,
+                                                const int32_t* errors, uint32_t* const* keys_host, int keys, void* scratch,
+                                                void* stream);
+    int gpuntt_keyswitch_plan_generate_keys_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* s, const uint64_t* s_from,
+                                                const int32_t* errors, uint64_t* const* keys_host, int keys, void* scratch,
+                                                void* stream);
+    int gpuntt_keyswitch_plan_encrypt_symmetric_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* s,
+                                                    const int32_t* errors, const uint32_t* message, uint32_t* out, int count,
+                                                    void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_encrypt_symmetric_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* s,
+                                                    const int32_t* errors, const uint64_t* message, uint64_t* out, int count,
+                                                    void* scratch, void* stream);
 
     /* frees the library-owned scratch buffers of the drop-in entry points (synchronises the device); only when no
      * hipGraph captured from drop-in calls will be replayed again and no call is in flight */
