@@ -134,7 +134,12 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "bfv_constants", "bfv_reference_extend", "bfv_reference_scale_round",
               "sample_uniform", "sample_reference_uniform", "keyswitch_plan_lift_small",
               "keyswitch_plan_keygen_scratch_bytes", "keyswitch_plan_encrypt_scratch_bytes",
-              "keyswitch_plan_generate_keys", "keyswitch_plan_encrypt_symmetric")
+              "keyswitch_plan_generate_keys", "keyswitch_plan_encrypt_symmetric",
+              "keyswitch_plan_phase_scratch_bytes", "keyswitch_plan_phase",
+              "keyswitch_plan_encrypt_public_scratch_bytes", "keyswitch_plan_encrypt_public",
+              "bfv_plan_scale_message", "bfv_plan_decode", "bfv_plan_decode_partials_bytes",
+              "bfv_plan_decode_two_launch", "bfv_plan_decrypt_scratch_bytes", "bfv_plan_decrypt",
+              "bfv_noise_budget_bits")
     for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option", "gpuntt_galois_element_u32",
                                 "gpuntt_automorphism_index_map", "gpuntt_philox4x32_10", "gpuntt_sample_small",
                                 "gpuntt_sample_reference_small"]
@@ -1584,6 +1589,58 @@ class KeySwitchPlan:
         _check(fn(self._h, _ptr(s), _ptr(errors), _ptr(message), _ptr(out), int(count), _ptr(scratch),
                   _stream(stream)))
 
+    # decryption and public-key encryption (key_switch.cuh, "Decryption and public-key encryption")
+    def phase_scratch_bytes(self, count, components=2, input_ntt=True):
+        out = ctypes.c_uint64()
+        _check(getattr(load_library(), "gpuntt_keyswitch_plan_phase_scratch_bytes_u%d" % self.bits)(
+            self._h, int(count), int(components), int(bool(input_ntt)), ctypes.byref(out)))
+        return int(out.value)
+
+    def phase(self, ct, s, out, count, components=2, input_ntt=True, output_ntt=False, scratch=None, stream=None):
+        """c0 + c1 s [+ c2 s^2]: ct T[components][count][L][N] (components 2 or 3), s T[M][N] in NTT form (the first L
+        limbs are read) -> out T[count][L][N]; out may be ct itself in NTT form.  scratch: at least
+        phase_scratch_bytes(count, components, input_ntt) bytes, 256-byte aligned (None for NTT-form input)."""
+        if ct is None or s is None or out is None:
+            raise ValueError("null pointer argument")
+        cols = self._cols(count)
+        comps = int(components) if int(components) in (2, 3) else 0
+        self._check_buffers([(ct, comps * cols * self.q_count, "ct (components x count x L x N)"),
+                             (s, self.q_count << self.n_power, "s (L x N at least)"),
+                             (out, cols * self.q_count, "out (count x L x N)")])
+        if scratch is not None and comps and int(count) >= 0:
+            self._check_aligned_scratch(scratch, self.phase_scratch_bytes(count, components, input_ntt),
+                                        "phase_scratch_bytes(count, components, input_ntt)")
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_phase_u%d" % self.bits)
+        _check(fn(self._h, _ptr(ct), _ptr(s), _ptr(out), int(count), int(components), int(bool(input_ntt)),
+                  int(bool(output_ntt)), _ptr(scratch), _stream(stream)))
+
+    def encrypt_public_scratch_bytes(self, count):
+        out = ctypes.c_uint64()
+        _check(getattr(load_library(), "gpuntt_keyswitch_plan_encrypt_public_scratch_bytes_u%d" % self.bits)(
+            self._h, int(count), ctypes.byref(out)))
+        return int(out.value)
+
+    def encrypt_public(self, pk, small, message, out, count, scratch, stream=None):
+        """`count` public-key encryptions: pk T[2][L][N] in NTT form (what encrypt_symmetric(count=1, message=None)
+        leaves in out), small int32[3][count][N] = (u, e0, e1), message T[count][L][N] in NTT form or None ->
+        out T[2][count][L][N] = (pk0 U + E0 + message, pk1 U + E1).  scratch: at least
+        encrypt_public_scratch_bytes(count) bytes, 256-byte aligned."""
+        if pk is None or small is None or out is None or scratch is None:
+            raise ValueError("null pointer argument")
+        cols = self._cols(count)
+        sized = [(pk, (2 * self.q_count) << self.n_power, "pk (2 x L x N)"),
+                 (out, 2 * cols * self.q_count, "out (2 x count x L x N)")]
+        if message is not None:
+            sized.append((message, cols * self.q_count, "message (count x L x N)"))
+        self._check_buffers(sized)
+        self._check_small(small, 3 * cols, "small (3 x count x N)")
+        if int(count) >= 0:
+            self._check_aligned_scratch(scratch, self.encrypt_public_scratch_bytes(count),
+                                        "encrypt_public_scratch_bytes(count)")
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_encrypt_public_u%d" % self.bits)
+        _check(fn(self._h, _ptr(pk), _ptr(small), _ptr(message), _ptr(out), int(count), _ptr(scratch),
+                  _stream(stream)))
+
     def close(self):
         if self._h:
             getattr(load_library(), "gpuntt_keyswitch_plan_destroy_u%d" % self.bits)(self._h)
@@ -1743,6 +1800,12 @@ def bfv_reference_scale_round(q_moduli, b_moduli, plain_modulus, full, out, n_po
     return out
 
 
+def noise_budget_bits(noise_max, q_count, bits=64):
+    """Host (no GPU): SEAL's invariant noise budget in bits from BfvMultiplyPlan.decode's noise_max over q_count limbs,
+    max(0, W - 1 - bit_length(noise_max + 3 q_count)) -- conservative by decode's band (bfv_multiply.cuh)"""
+    return max(0, int(bits) - 1 - (int(noise_max) + 3 * int(q_count)).bit_length())
+
+
 class BfvMultiplyPlan:
     """Extension BfvMultiplyPlan<T> (include/gpuntt/rns/bfv_multiply.cuh): the scale-invariant product
     round(t (x (x) y) / Q) for the q-base `q_moduli` (L), the auxiliary base `b_moduli` (K, B >= 2 t N Q or ValueError
@@ -1870,6 +1933,77 @@ class BfvMultiplyPlan:
         fn = getattr(load_library(), "gpuntt_bfv_plan_multiply_relinearize_u%d" % self.bits)
         _check(fn(self._h, _ptr(x), _ptr(y), key_switch._h, _ptr(key), _ptr(out), int(count), int(bool(input_ntt)),
                   int(bool(output_ntt)), _ptr(scratch), _ptr(key_switch_scratch), _stream(stream)))
+
+    # ---- encode, decode, decrypt (bfv_multiply.cuh, "Reading a result back") ----
+    def scale_message(self, message, out, count, to_ntt=True, stream=None):
+        """message T[count][N] (any word, read modulo t) -> out T[count][L][N] = round(Q m / t) in the q-base, what
+        encrypt_symmetric / encrypt_public take as message; with to_ntt the q-base transform follows in place"""
+        if message is None or out is None:
+            raise ValueError("null pointer argument")
+        cols = self._cols(count)
+        self._check_buffers(((message, cols, "message (count x N)"),
+                             (out, cols * self.q_count, "out (count x L x N)")))
+        fn = getattr(load_library(), "gpuntt_bfv_plan_scale_message_u%d" % self.bits)
+        _check(fn(self._h, _ptr(message), _ptr(out), int(count), int(bool(to_ntt)), _stream(stream)))
+
+    def decode_partials_bytes(self, stacks):
+        out = ctypes.c_uint64()
+        _check(getattr(load_library(), "gpuntt_bfv_plan_decode_partials_bytes_u%d" % self.bits)(
+            self._h, int(stacks), ctypes.byref(out)))
+        return int(out.value)
+
+    def decode(self, x, message_out, noise_max, stacks, stream=None, partials=None):
+        """x T[stacks][L][N] in coefficient form (any word) -> message_out T[stacks][N] = round(t x / Q) mod t and, unless
+        None, noise_max T[stacks] = the largest |noise word| of every stack (noise_budget_bits turns it into bits).
+        partials: None (a memset and one launch) or a device tensor of at least decode_partials_bytes(stacks) bytes --
+        the same words from two launches and no memset"""
+        if x is None or message_out is None:
+            raise ValueError("null pointer argument")
+        cols = self._cols(stacks)
+        self._check_buffers(((x, cols * self.q_count, "x (stacks x L x N)"), (message_out, cols, "message_out (stacks x N)"),
+                             (noise_max, max(0, int(stacks)), "noise_max (stacks)")))
+        if partials is not None:
+            _require_gpu(partials)
+            if int(stacks) > 0 and partials.numel() * partials.element_size() < self.decode_partials_bytes(stacks):
+                raise ValueError("partials holds fewer than decode_partials_bytes(stacks) bytes")
+            fn = getattr(load_library(), "gpuntt_bfv_plan_decode_two_launch_u%d" % self.bits)
+            _check(fn(self._h, _ptr(x), _ptr(message_out), _ptr(noise_max), int(stacks), _ptr(partials), _stream(stream)))
+            return
+        fn = getattr(load_library(), "gpuntt_bfv_plan_decode_u%d" % self.bits)
+        _check(fn(self._h, _ptr(x), _ptr(message_out), _ptr(noise_max), int(stacks), _stream(stream)))
+
+    def decrypt_scratch_bytes(self, count):
+        out = ctypes.c_uint64()
+        _check(getattr(load_library(), "gpuntt_bfv_plan_decrypt_scratch_bytes_u%d" % self.bits)(
+            self._h, int(count), ctypes.byref(out)))
+        return int(out.value)
+
+    def decrypt(self, ct, key_switch, s, message_out, noise_max, count, components=2, input_ntt=True, scratch=None,
+                key_switch_scratch=None, stream=None):
+        """key_switch.phase(ct, s, scratch, output_ntt=False) then decode(scratch, message_out, noise_max), word for word:
+        ct T[components][count][L][N], s T[M][N] in NTT form -> message_out T[count][N], noise_max T[count] or None.
+        scratch: at least decrypt_scratch_bytes(count) bytes; key_switch_scratch: at least
+        key_switch.phase_scratch_bytes(count, components, input_ntt) bytes (None where that is 0); 256-byte aligned."""
+        if not isinstance(key_switch, KeySwitchPlan) or key_switch.bits != self.bits:
+            raise ValueError("key_switch is a KeySwitchPlan of the same word width")
+        if ct is None or s is None or message_out is None or scratch is None:
+            raise ValueError("null pointer argument")
+        cols = self._cols(count)
+        comps = int(components) if int(components) in (2, 3) else 0
+        self._check_buffers(((ct, comps * cols * self.q_count, "ct (components x count x L x N)"),
+                             (s, self.q_count << self.n_power, "s (L x N at least)"),
+                             (message_out, cols, "message_out (count x N)"),
+                             (noise_max, max(0, int(count)), "noise_max (count)")))
+        _require_gpu(scratch, key_switch_scratch)
+        if int(count) > 0 and scratch.numel() * scratch.element_size() < self.decrypt_scratch_bytes(count):
+            raise ValueError("scratch holds fewer than decrypt_scratch_bytes(count) bytes")
+        if key_switch_scratch is not None and int(count) > 0 and comps and \
+                key_switch_scratch.numel() * key_switch_scratch.element_size() < \
+                key_switch.phase_scratch_bytes(count, components, input_ntt):
+            raise ValueError("key_switch_scratch holds fewer than key_switch.phase_scratch_bytes(...) bytes")
+        fn = getattr(load_library(), "gpuntt_bfv_plan_decrypt_u%d" % self.bits)
+        _check(fn(self._h, _ptr(ct), key_switch._h, _ptr(s), _ptr(message_out), _ptr(noise_max), int(count),
+                  int(components), int(bool(input_ntt)), _ptr(scratch), _ptr(key_switch_scratch), _stream(stream)))
 
     # ---- the summed product (bfv_multiply.cuh, "multiply_sum") ----
     @property

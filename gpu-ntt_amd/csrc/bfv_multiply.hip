@@ -38,6 +38,7 @@
 
 #include "bfv_multiply_internal.hpp"
 #include "bfv_multiply_sum_internal.hpp"
+#include "decrypt_internal.hpp"
 #include "gpuntt/ntt_merge/ntt.cuh"
 #include "gpuntt/rns/bfv_multiply.cuh"
 #include "launch.hpp"
@@ -452,6 +453,11 @@ namespace gpuntt
         kern::BcOffsets up_off{}, down_off{};
         kern::BfvOffsets ex_off{};
         std::unique_ptr<NTTPlan<T>> ntt_q_i, ntt_q_f, ntt_full_f, ntt_full_i;
+        // scale_message / decode / decrypt (decrypt.hip): the constants of t travel as kernel arguments, derived on the
+        // host at construction -- no word of the workspace, no launch
+        bool decode_ok = false, scale_ok = false; // is t usable by decode / by scale_message ("Plaintext modulus ...")
+        kern::BfvDecodeArgs<T> decode_args{};
+        kern::BfvScaleArgs<T> scale_args{};
 
         const T* consts() const { return reinterpret_cast<const T*>(ws + lay.up); }
         const T* fold() const { return reinterpret_cast<const T*>(ws + lay.fold); }
@@ -480,6 +486,132 @@ namespace gpuntt
                           static_cast<size_t>(M) * kern::BC_NT * sizeof(T), stream, full, out, consts(), up_off, down_off,
                           ex_off, L, K, bc_padded(K), bc_padded(L), n, total);
             GPUNTT_HIP_CHECK(hipGetLastError());
+        }
+
+        // message: T[count][N] -> out: T[count][L][N], round(Q m / t) in the q-base
+        void scale_message(const T* message, T* out, int count, bool to_ntt, hipStream_t stream) const
+        {
+            if (!scale_ok)
+                throw std::invalid_argument("Plaintext modulus not usable here!");
+            if (to_ntt && !ntt_q_f)
+                throw std::invalid_argument("The plan was built without transform tables!");
+            if (count < 0 || static_cast<unsigned long long>(count) * static_cast<unsigned>(L) > 0x7FFFFFFFull)
+                throw std::invalid_argument("Invalid count!");
+            if (message == nullptr || out == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            if (count == 0)
+                return;
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            if (rns_overlap(message, cols * sizeof(T), out, cols * L * sizeof(T)))
+                throw std::invalid_argument("scale_message input and output overlap!");
+            host::bfv_scale_message_launch<T>(message, out, fold(), scale_args, count, L, n, false, stream);
+            host::bfv_scale_message_launch<T>(message, out, fold(), scale_args, count, L, n, true, stream);
+            if (to_ntt)
+                ntt_q_f->execute(out, out, count * L, stream);
+        }
+
+        // every refusal of decode; returns false when stacks is 0 and nothing is to be launched
+        size_t decode_partials(int stacks) const // the partial maxima of the two-launch decode: T[stacks][tiles]
+        {
+            if (stacks < 0)
+                throw std::invalid_argument("Invalid stacks!");
+            return rns_align(host::decode_partial_words(stacks, n) * sizeof(T));
+        }
+
+        bool decode_check(const T* x, const T* message, const T* noise_max, int stacks, const void* partials = nullptr) const
+        {
+            if (!decode_ok)
+                throw std::invalid_argument("Plaintext modulus not usable here!");
+            if (stacks < 0)
+                throw std::invalid_argument("Invalid stacks!");
+            if (x == nullptr || message == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            if (stacks == 0)
+                return false;
+            const std::uint64_t cols = static_cast<std::uint64_t>(stacks) << n;
+            const std::uint64_t x_bytes = cols * L * sizeof(T), m_bytes = cols * sizeof(T);
+            const std::uint64_t n_bytes = static_cast<std::uint64_t>(stacks) * sizeof(T);
+            if (rns_overlap(x, x_bytes, message, m_bytes) ||
+                (noise_max != nullptr &&
+                 (rns_overlap(x, x_bytes, noise_max, n_bytes) || rns_overlap(message, m_bytes, noise_max, n_bytes))))
+                throw std::invalid_argument("decode input and output overlap!");
+            if (partials != nullptr && noise_max != nullptr)
+            {
+                const std::uint64_t p_bytes = host::decode_partial_words(stacks, n) * sizeof(T);
+                if (reinterpret_cast<uintptr_t>(partials) % sizeof(T) != 0 || rns_overlap(partials, p_bytes, x, x_bytes) ||
+                    rns_overlap(partials, p_bytes, message, m_bytes) || rns_overlap(partials, p_bytes, noise_max, n_bytes))
+                    throw std::invalid_argument("decode input and output overlap!");
+            }
+            // the grid limit, with the loader the launch will choose
+            try
+            {
+                host::bfv_decode_launch<T>(x, const_cast<T*>(message), nullptr, nullptr, consts(), up_off, decode_args,
+                                           stacks, L, n, false, nullptr);
+            }
+            catch (const std::invalid_argument&)
+            {
+                throw std::invalid_argument("Invalid stacks!"); // the grid's own words name a count
+            }
+            return true;
+        }
+        // partials == nullptr: the memset of noise_max and ONE launch with the atomic merge; otherwise two launches
+        void decode_run(const T* x, T* message, T* noise_max, int stacks, hipStream_t stream, void* partials = nullptr) const
+        {
+            if (noise_max != nullptr && partials == nullptr)
+                GPUNTT_HIP_CHECK(hipMemsetAsync(noise_max, 0, static_cast<size_t>(stacks) * sizeof(T), stream));
+            host::bfv_decode_launch<T>(x, message, noise_max, static_cast<T*>(partials), consts(), up_off, decode_args,
+                                       stacks, L, n, true, stream);
+        }
+        // x: T[stacks][L][N] in coefficient form -> message: T[stacks][N], noise_max: T[stacks] or nullptr
+        void decode(const T* x, T* message, T* noise_max, int stacks, hipStream_t stream, void* partials) const
+        {
+            if (decode_check(x, message, noise_max, stacks, partials))
+                decode_run(x, message, noise_max, stacks, stream, partials);
+        }
+
+        size_t decrypt_scratch(int count) const // the phase in coefficient form: T[count][L][N]
+        {
+            if (count < 0)
+                throw std::invalid_argument("Invalid count!");
+            return rns_align(((static_cast<size_t>(count) * L) << n) * sizeof(T));
+        }
+
+        void decrypt(const T* ct, const KeySwitchPlan<T>& ks, const T* s, T* message, T* noise_max, int count,
+                     int components, bool input_ntt, void* scratch, void* ks_scratch, hipStream_t stream) const
+        {
+            bool match = ntt_full_f && ks.has_transforms() && ks.q_count() == L && ks.n_power() == n &&
+                         ks.reduction_poly() == poly;
+            for (int m = 0; match && m < L; m++)
+                match = ks.modulus(m).value == moduli[m].value;
+            if (!match)
+                throw std::invalid_argument("The key-switching plan does not match!");
+            const size_t p_bytes = decrypt_scratch(count); // checks count
+            if (scratch == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
+                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            T* x = static_cast<T*>(scratch);
+            const bool work = decode_check(x, message, noise_max, count);
+            const size_t ks_bytes = ks.phase_scratch_bytes(count, components, input_ntt); // checks components
+            if (work && ct != nullptr && s != nullptr)
+            {
+                const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+                const std::uint64_t ct_bytes = cols * L * components * sizeof(T), m_bytes = cols * sizeof(T);
+                const std::uint64_t s_bytes = (static_cast<std::uint64_t>(L) << n) * sizeof(T);
+                const std::uint64_t n_bytes = static_cast<std::uint64_t>(count) * sizeof(T);
+                for (const auto& o : {std::pair<const void*, std::uint64_t>{message, m_bytes},
+                                      {noise_max, noise_max != nullptr ? n_bytes : 0}})
+                    if (o.first != nullptr &&
+                        (rns_overlap(o.first, o.second, ct, ct_bytes) || rns_overlap(o.first, o.second, s, s_bytes) ||
+                         (ks_scratch != nullptr && ks_bytes != 0 && rns_overlap(o.first, o.second, ks_scratch, ks_bytes))))
+                        throw std::invalid_argument("out or the scratch overlaps an operand!");
+            }
+            (void) p_bytes;
+            // the phase refuses the rest before its first launch: null ct or s, its own scratch, the overlaps of the
+            // coefficient region with ct, s and its scratch
+            ks.phase(ct, s, x, count, components, input_ntt, false, ks_scratch, stream);
+            if (work)
+                decode_run(x, message, noise_max, count, stream);
         }
 
         // What multiply and multiply_relinearize share up to the first launch: every refusal of multiply, with `comps`
@@ -808,6 +940,49 @@ namespace gpuntt
         std::vector<Modulus<T>> full(q_moduli_host, q_moduli_host + h.L);
         full.insert(full.end(), b_moduli_host, b_moduli_host + h.K);
         p->moduli = full;
+        {
+            // the constants of scale_message and decode, in exact integers.  decode: 2 <= t < 2^(W-2) and t < every q_i;
+            // scale_message: also gcd(t, q_i) = 1
+            constexpr int W = static_cast<int>(8 * sizeof(T));
+            const std::uint64_t t = plain_modulus;
+            bool ok = t >= 2 && t < (std::uint64_t(1) << (W - 2));
+            for (int i = 0; ok && i < L; i++)
+                ok = t < h.mod[i];
+            p->decode_ok = ok;
+            if (ok)
+            {
+                auto shoup = [&](std::uint64_t v, std::uint64_t m) {
+                    return static_cast<T>((static_cast<U128>(v) << W) / m);
+                };
+                p->decode_args.t = p->scale_args.t = static_cast<T>(t);
+                p->decode_args.one_shoup_t = p->scale_args.one_shoup_t = shoup(1, t);
+                std::uint64_t q_mod_t = 1 % t;
+                bool coprime = true;
+                for (int i = 0; i < L; i++)
+                {
+                    const std::uint64_t q = h.mod[i];
+                    p->decode_args.t_shoup[i] = shoup(t, q);
+                    q_mod_t = static_cast<std::uint64_t>(static_cast<U128>(q_mod_t) * (q % t) % t);
+                    // t^-1 mod q by the extended Euclidean algorithm (q need not be prime)
+                    __int128 r0 = static_cast<__int128>(q), r1 = static_cast<__int128>(t), c0 = 0, c1 = 1;
+                    while (r1 != 0)
+                    {
+                        const __int128 quo = r0 / r1, r2 = r0 - quo * r1, c2 = c0 - quo * c1;
+                        r0 = r1, r1 = r2, c0 = c1, c1 = c2;
+                    }
+                    if (r0 != 1)
+                    {
+                        coprime = false;
+                        continue;
+                    }
+                    const std::uint64_t inv = static_cast<std::uint64_t>(c0 < 0 ? c0 + static_cast<__int128>(q) : c0);
+                    p->scale_args.t_inv[i] = static_cast<T>(inv), p->scale_args.t_inv_shoup[i] = shoup(inv, q);
+                }
+                p->scale_args.q_mod_t = static_cast<T>(q_mod_t), p->scale_args.q_mod_t_shoup = shoup(q_mod_t, t);
+                p->scale_args.half = static_cast<T>(t / 2);
+                p->scale_ok = coprime;
+            }
+        }
 
         void* raw = workspace_device;
         if (raw == nullptr)
@@ -896,6 +1071,35 @@ namespace gpuntt
     {
         p_->multiply_relinearize_sum(device_x_host, device_y_host, terms, key_switch, device_key, device_out, count,
                                      input_ntt, output_ntt, scratch_device, key_switch_scratch_device, stream);
+    }
+    template <typename T>
+    void BfvMultiplyPlan<T>::scale_message(const T* device_message, T* device_out, int count, bool to_ntt,
+                                           stream_t stream) const
+    {
+        p_->scale_message(device_message, device_out, count, to_ntt, stream);
+    }
+    template <typename T>
+    void BfvMultiplyPlan<T>::decode(const T* device_x, T* device_message_out, T* device_noise_max, int stacks,
+                                    stream_t stream, void* partials_device) const
+    {
+        p_->decode(device_x, device_message_out, device_noise_max, stacks, stream, partials_device);
+    }
+    template <typename T> size_t BfvMultiplyPlan<T>::decode_partials_bytes(int stacks) const
+    {
+        return p_->decode_partials(stacks);
+    }
+    template <typename T> size_t BfvMultiplyPlan<T>::decrypt_scratch_bytes(int count) const
+    {
+        return p_->decrypt_scratch(count);
+    }
+    template <typename T>
+    void BfvMultiplyPlan<T>::decrypt(const T* device_ct, const KeySwitchPlan<T>& key_switch, const T* device_s_ntt,
+                                     T* device_message_out, T* device_noise_max, int count, int components,
+                                     bool input_ntt, void* scratch_device, void* key_switch_scratch_device,
+                                     stream_t stream) const
+    {
+        p_->decrypt(device_ct, key_switch, device_s_ntt, device_message_out, device_noise_max, count, components,
+                    input_ntt, scratch_device, key_switch_scratch_device, stream);
     }
     template <typename T> int BfvMultiplyPlan<T>::max_terms() const { return p_->max_terms; }
     template <typename T>

@@ -1145,6 +1145,101 @@ extern "C"
                 s, errors, message, out, count, scratch, static_cast<hipStream_t>(stream));       \
         });                                                                                       \
     }                                                                                             \
+    int gpuntt_keyswitch_plan_phase_scratch_bytes_##S(const gpuntt_keyswitch_plan* plan, int count, int components,\
+                                                      int input_ntt, uint64_t* bytes_host)        \
+    {                                                                                             \
+        GPUNTT_NEED(plan, bytes_host)                                                             \
+        return guarded([&] {                                                                      \
+            *bytes_host = reinterpret_cast<const KeySwitchPlan<T>*>(plan)->phase_scratch_bytes(   \
+                count, components, input_ntt != 0);                                               \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_phase_##S(const gpuntt_keyswitch_plan* plan, const T* ct, const T* s, T* out,\
+                                        int count, int components, int input_ntt, int output_ntt, \
+                                        void* scratch, void* stream)                              \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->phase(                               \
+                ct, s, out, count, components, input_ntt != 0, output_ntt != 0, scratch,          \
+                static_cast<hipStream_t>(stream));                                                \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_encrypt_public_scratch_bytes_##S(const gpuntt_keyswitch_plan* plan, int count,\
+                                                               uint64_t* bytes_host)              \
+    {                                                                                             \
+        GPUNTT_NEED(plan, bytes_host)                                                             \
+        return guarded([&] {                                                                      \
+            *bytes_host = reinterpret_cast<const KeySwitchPlan<T>*>(plan)->encrypt_public_scratch_bytes(count);\
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_encrypt_public_##S(const gpuntt_keyswitch_plan* plan, const T* pk,  \
+                                                 const int32_t* small, const T* message, T* out, int count,\
+                                                 void* scratch, void* stream)                     \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->encrypt_public(                      \
+                pk, small, message, out, count, scratch, static_cast<hipStream_t>(stream));       \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_plan_scale_message_##S(const gpuntt_bfv_plan* plan, const T* message, T* out, int count,\
+                                          int to_ntt, void* stream)                               \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const BfvMultiplyPlan<T>*>(plan)->scale_message(                     \
+                message, out, count, to_ntt != 0, static_cast<hipStream_t>(stream));              \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_plan_decode_##S(const gpuntt_bfv_plan* plan, const T* x, T* message_out, T* noise_max,\
+                                   int stacks, void* stream)                                      \
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const BfvMultiplyPlan<T>*>(plan)->decode(                            \
+                x, message_out, noise_max, stacks, static_cast<hipStream_t>(stream));             \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_plan_decode_partials_bytes_##S(const gpuntt_bfv_plan* plan, int stacks, uint64_t* bytes_host)\
+    {                                                                                             \
+        GPUNTT_NEED(plan, bytes_host)                                                             \
+        return guarded([&] {                                                                      \
+            *bytes_host = reinterpret_cast<const BfvMultiplyPlan<T>*>(plan)->decode_partials_bytes(stacks);\
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_plan_decode_two_launch_##S(const gpuntt_bfv_plan* plan, const T* x, T* message_out,\
+                                              T* noise_max, int stacks, void* partials, void* stream)\
+    {                                                                                             \
+        GPUNTT_NEED(plan, partials)                                                               \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const BfvMultiplyPlan<T>*>(plan)->decode(                            \
+                x, message_out, noise_max, stacks, static_cast<hipStream_t>(stream), partials);   \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_plan_decrypt_scratch_bytes_##S(const gpuntt_bfv_plan* plan, int count, uint64_t* bytes_host)\
+    {                                                                                             \
+        GPUNTT_NEED(plan, bytes_host)                                                             \
+        return guarded([&] {                                                                      \
+            *bytes_host = reinterpret_cast<const BfvMultiplyPlan<T>*>(plan)->decrypt_scratch_bytes(count);\
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_plan_decrypt_##S(const gpuntt_bfv_plan* plan, const T* ct,                     \
+                                    const gpuntt_keyswitch_plan* key_switch, const T* s, T* message_out,\
+                                    T* noise_max, int count, int components, int input_ntt, void* scratch,\
+                                    void* key_switch_scratch, void* stream)                       \
+    {                                                                                             \
+        GPUNTT_NEED(plan, key_switch)                                                             \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const BfvMultiplyPlan<T>*>(plan)->decrypt(                           \
+                ct, *reinterpret_cast<const KeySwitchPlan<T>*>(key_switch), s, message_out, noise_max, count,\
+                components, input_ntt != 0, scratch, key_switch_scratch, static_cast<hipStream_t>(stream));\
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_noise_budget_bits_##S(T noise_max, int q_count)                                \
+    {                                                                                             \
+        return noise_budget_bits<T>(noise_max, q_count);                                          \
+    }                                                                                             \
     int gpuntt_keyswitch_plan_destroy_##S(gpuntt_keyswitch_plan* plan)                            \
     {                                                                                             \
         return guarded([&] { delete reinterpret_cast<KeySwitchPlan<T>*>(plan); });                \

@@ -70,6 +70,7 @@
 #include <vector>
 
 #include "base_conversion_internal.hpp"
+#include "decrypt_internal.hpp"
 #include "gpuntt/ntt_merge/ntt.cuh"
 #include "gpuntt/rns/key_switch.cuh"
 #include "hoisted_rotation_internal.hpp"
@@ -1229,7 +1230,126 @@ namespace gpuntt
             ntt_q_f->execute(e, e, count * L, stream);
             host::keygen_combine_launch<T>(e, s, message, args, shape, 1, consts, M, n, true, stream);
         }
+
+        // Decryption and public-key encryption (decrypt.hip)
+
+        static void phase_components(int components)
+        {
+            if (components != 2 && components != 3)
+                throw std::invalid_argument("Invalid components!");
+        }
+        size_t phase_scratch(int count, int components, bool input_ntt) const // the NTT of ct: T[components][count][L][N]
+        {
+            phase_components(components);
+            if (count < 0)
+                throw std::invalid_argument("Invalid count!");
+            if (input_ntt)
+                return 0;
+            return rns_align(((static_cast<size_t>(components) * count * L) << n) * sizeof(T));
+        }
+        size_t encrypt_public_scratch(int count) const // (U, E0, E1): T[3][count][L][N]
+        {
+            if (count < 0)
+                throw std::invalid_argument("Invalid count!");
+            return rns_align(((static_cast<size_t>(3) * count * L) << n) * sizeof(T));
+        }
+
+        // ct: T[components][count][L][N], s: T[M][N] (the first L limbs are read), out: T[count][L][N]; the scratch:
+        // phase_scratch(count, components, input_ntt)
+        void phase(const T* ct, const T* s, T* out, int count, int components, bool input_ntt, bool output_ntt,
+                   void* scratch, hipStream_t stream) const
+        {
+            if (!input_ntt || !output_ntt)
+                need_transforms();
+            const size_t s_bytes = phase_scratch(count, components, input_ntt); // checks components and count
+            if (ct == nullptr || s == nullptr || out == nullptr || (!input_ntt && scratch == nullptr))
+                throw std::invalid_argument("null pointer argument");
+            if (!input_ntt && reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
+                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            if (static_cast<unsigned long long>(components) * static_cast<unsigned>(count) * static_cast<unsigned>(L) >
+                0x7FFFFFFFull) // the transforms' batch
+                throw std::invalid_argument("Invalid count!");
+            if (count == 0)
+                return;
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const std::uint64_t out_bytes = cols * L * sizeof(T), ct_bytes = out_bytes * components;
+            const std::uint64_t sec_bytes = (static_cast<std::uint64_t>(L) << n) * sizeof(T);
+            // out may be exactly ct in NTT form: every word of component 0 is written by the lane that read it
+            if ((rns_overlap(out, out_bytes, ct, ct_bytes) && !(input_ntt && out == ct)) ||
+                rns_overlap(out, out_bytes, s, sec_bytes))
+                throw std::invalid_argument("out overlaps an operand!");
+            if (!input_ntt && (rns_overlap(scratch, s_bytes, ct, ct_bytes) || rns_overlap(scratch, s_bytes, s, sec_bytes)))
+                throw std::invalid_argument("out or the scratch overlaps an operand!");
+            if (!input_ntt && rns_overlap(scratch, s_bytes, out, out_bytes))
+                throw std::invalid_argument("The scratch overlaps out!");
+            const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
+            const T* c = input_ntt ? ct : static_cast<const T*>(scratch);
+            host::decrypt_phase_launch<T>(c, s, out, consts, count, components, L, M, n, false, stream);
+            if (!input_ntt)
+                ntt_q_f->execute(ct, static_cast<T*>(scratch), components * count * L, stream);
+            host::decrypt_phase_launch<T>(c, s, out, consts, count, components, L, M, n, true, stream);
+            if (!output_ntt)
+                ntt_q_i->execute(out, out, count * L, stream);
+        }
+
+        // pk: T[2][L][N], small: int32[3][count][N] = (u, e0, e1), message: T[count][L][N] or nullptr,
+        // out: T[2][count][L][N]; the scratch: encrypt_public_scratch(count)
+        void encrypt_public(const T* pk, const std::int32_t* small, const T* message, T* out, int count, void* scratch,
+                            hipStream_t stream) const
+        {
+            need_transforms();
+            const size_t e_bytes = encrypt_public_scratch(count); // checks count
+            if (pk == nullptr || small == nullptr || out == nullptr || scratch == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
+                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            if (3ull * static_cast<unsigned>(count) * static_cast<unsigned>(L) > 0x7FFFFFFFull)
+                throw std::invalid_argument("Invalid count!");
+            if (count == 0)
+                return;
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T), msg_bytes = cols * L * sizeof(T);
+            const std::pair<const void*, std::uint64_t> inputs[] = {
+                {pk, (static_cast<std::uint64_t>(2 * L) << n) * sizeof(T)}, {small, 3 * cols * sizeof(std::int32_t)},
+                {message, message != nullptr ? msg_bytes : 0}};
+            for (const auto& op : inputs)
+                if (op.first != nullptr &&
+                    (rns_overlap(scratch, e_bytes, op.first, op.second) || rns_overlap(out, ct_bytes, op.first, op.second)))
+                    throw std::invalid_argument("out or the scratch overlaps an operand!");
+            if (rns_overlap(out, ct_bytes, scratch, e_bytes))
+                throw std::invalid_argument("The scratch overlaps out!");
+            T* e = static_cast<T*>(scratch);
+            const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
+            host::keygen_lift_launch<T>(small, e, consts, 3 * count, L, M, n, false, stream);
+            host::encrypt_public_combine_launch<T>(pk, e, message, out, consts, count, L, M, n, false, stream);
+            host::keygen_lift_launch<T>(small, e, consts, 3 * count, L, M, n, true, stream);
+            ntt_q_f->execute(e, e, 3 * count * L, stream);
+            host::encrypt_public_combine_launch<T>(pk, e, message, out, consts, count, L, M, n, true, stream);
+        }
     };
+
+    template <typename T>
+    size_t KeySwitchPlan<T>::phase_scratch_bytes(int count, int components, bool input_ntt) const
+    {
+        return p_->phase_scratch(count, components, input_ntt);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::phase(const T* device_ct, const T* device_s_ntt, T* device_out, int count, int components,
+                                 bool input_ntt, bool output_ntt, void* scratch_device, stream_t stream) const
+    {
+        p_->phase(device_ct, device_s_ntt, device_out, count, components, input_ntt, output_ntt, scratch_device, stream);
+    }
+    template <typename T> size_t KeySwitchPlan<T>::encrypt_public_scratch_bytes(int count) const
+    {
+        return p_->encrypt_public_scratch(count);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::encrypt_public(const T* device_pk, const std::int32_t* device_small,
+                                          const T* device_message_ntt, T* device_out, int count, void* scratch_device,
+                                          stream_t stream) const
+    {
+        p_->encrypt_public(device_pk, device_small, device_message_ntt, device_out, count, scratch_device, stream);
+    }
 
     template <typename T>
     void KeySwitchPlan<T>::lift_small(const std::int32_t* device_small, T* device_out, int polys, bool full_base,

@@ -132,6 +132,59 @@
 //     other: std::invalid_argument before anything is launched.  The same for a null pointer, a scratch that is not
 //     256-byte aligned, count < 0, a count beyond the grid and int limits of the transforms and kernels, and a multiply on
 //     a plan without transforms
+//
+// Reading a result back (the kernels are in decrypt.hip).  The three calls below need a plaintext modulus
+// with 2 <= t < 2^(W-2) and t < every q_i -- and, for scale_message, gcd(t, q_i) = 1 --:
+// std::invalid_argument("Plaintext modulus not usable here!") otherwise, from these calls only (multiply* take any t >= 2).
+// Their constants (Q mod t, t^-1 mod q_i, floor(t 2^W / q_i), with Shoup companions) are derived on the host at
+// construction in exact integers and travel as kernel arguments: workspace_bytes and every launch above are unchanged.
+//   scale_message(message, out, count, to_ntt):  round(Q m / t) in the q-base, what KeySwitchPlan::encrypt_symmetric /
+//     encrypt_public take as message_ntt.  message = T[count][N], any word, read modulo t; out = T[count][L][N].
+//     DEFINITION, with m = word mod t, h = floor(t / 2) and r = ((Q mod t) m + h) mod t:
+//       out[c][i][j] = floor((Q m + h) / t) mod q_i = ((h - r) [t^-1 mod q_i]) mod q_i, canonical
+//     (Q m vanishes modulo q_i: no wide arithmetic).  ONE launch of bfv_scale_message, then with to_ntt the q-base
+//     GPU_NTT in place.  Refusals: a null pointer, message overlapping out, count < 0 or count * L beyond an int,
+//     to_ntt on a plan without transforms; count = 0 launches nothing
+//   decode(x, message_out, noise_max, stacks):  m = round(t x / Q) mod t with the noise, from coefficient-form residues.
+//     x = T[stacks][L][N], any word; message_out = T[stacks][N]; noise_max = T[stacks] or nullptr.  DEFINITION, all
+//     integers, per coefficient, on base_conversion.cuh's constants qhat_i^-1 and R_i = floor(2^(W-1+b_i) / q_i), b_i the
+//     bit length of q_i:
+//       y_i = (x_i [qhat_i^-1 mod q_i]) mod q_i, canonical
+//       (a_i, r_i) = divmod(t y_i, q_i)                      -- a_i < t
+//       z_i = (r_i R_i) >> (b_i - 1)
+//       S = 2^W sum_i a_i + sum_i z_i
+//       message_out = ((S + 2^(W-1)) >> W) mod t
+//       noise word n = ((S + 2^(W-1)) mod 2^W) - 2^(W-1), a signed W-bit value;  noise_max[s] = max_j |n|
+//     Why this is the rounding.  t x / Q = sum_i t y_i / q_i (mod t), and 0 <= r_i 2^W / q_i - z_i < 3, so 2^W (t x / Q)
+//     lies in [S, S + 3 L) modulo t 2^W.  THE BAND: outside (S mod 2^W) in [2^(W-1) - 3 L, 2^(W-1)) message_out is
+//     round-half-up(t x^ / Q) mod t for any representative x^; inside it is that value or that value - 1 (mod t).  The
+//     invariant noise v = t x / Q - round(.) obeys |n| <= 2^W |v| + 3 L and 2^W |v| <= |n| + 3 L.
+//     noise_budget_bits(noise_max, L) = max(0, W - 1 - bit_length(noise_max + 3 L)) below is SEAL's invariant noise budget,
+//     conservative by the band, and CAPPED at W - 1 - bit_length(3 L): a larger true budget (wide bases, fresh
+//     ciphertexts) reads as the cap -- see the limitation stated at the function.
+//     What runs: [noise_max given: a hipMemsetAsync of its T[stacks],] ONE launch of bfv_decode: a lane owns a 16-byte
+//     group of columns and walks the limbs; the per-stack maximum is reduced across the wave (lane exchanges) and the
+//     workgroup (one word per wave in LDS, one barrier) and merged with one atomicMax per workgroup, only when
+//     noise_max is given (nullptr: nothing is written there).
+//     partials_device (optional, last argument): decode_partials_bytes(stacks) bytes of device memory.  Given, the same
+//     words come from TWO launches and no memset: bfv_decode stores every workgroup's maximum there and
+//     bfv_decode_merge (one wave per stack) stores noise_max.  Which is faster is a matter of the call's size
+//     (DESIGN.md 3.23 has both, measured); decrypt uses the one-launch form.  partials must not overlap x or an output  Refusals: a null x or
+//     message_out, x overlapping an output (or the outputs each other), stacks < 0 or beyond the grid limit; stacks = 0
+//     launches nothing
+//   decrypt(ct, key_switch, s_ntt, message_out, noise_max, count, components, input_ntt, scratch, key_switch_scratch):
+//     DEFINITION, word for word:
+//       key_switch.phase(ct, s_ntt, scratch, count, components, input_ntt, output_ntt = false, key_switch_scratch)
+//       decode(scratch, message_out, noise_max, count)
+//     The two plans are checked against each other first, as multiply_relinearize checks them ("The key-switching plan
+//     does not match!").  scratch: decrypt_scratch_bytes(count) bytes = T[count][L][N], 256-byte aligned;
+//     key_switch_scratch: key_switch.phase_scratch_bytes(count, components, input_ntt) bytes (nullptr is accepted where
+//     that is 0).  Every refusal of both calls arrives before the first launch.  Allocates nothing, never synchronises,
+//     one stream, capturable as it is (the memset is a node)
+//   Not here: CKKS encode / decode, BFV batching (an NTT modulo t), a centred multi-precision output of the phase, BGV,
+//     noise flooding, the INTT's last pass fused into bfv_decode
+//
+//
 //   * transforms: as KeySwitchPlan -- ONE caller table pair in full-base order (slot i at i << n_power, the q-base is its
 //     first L slots), the M host n^-1 values, the reduction polynomial and a batch_hint; the plan builds four NTTPlan<T>
 //     inside its workspace (inverse and forward over the q-base, forward and inverse over the full base).  The tables
@@ -159,6 +212,23 @@ namespace gpuntt
 {
     // terms of one multiply_sum call at most: the cross term is one exact sum of 2 * terms products
     constexpr int BFV_MAX_TERMS = 32;
+
+    // SEAL's invariant noise budget in bits from decode's noise_max over L limbs: max(0, W - 1 - bit_length(noise_max +
+    // 3 L)), conservative by the band of decode ("Reading a result back" in this header).
+    // LIMITATION: the noise word has W bits, so the result never exceeds W - 1 - bit_length(3 L) (59 bits for u64 at
+    // L = 3, 27 for u32).  A ciphertext whose true budget is larger -- any fresh one over a base of two or more 60-bit
+    // primes, where the budget is log2(Q / (2 t |e|)) > 64 -- reads as that cap, before and after an operation alike:
+    // the value says "at least this much" there and nothing more.  It resolves the budget only once the noise has
+    // grown to within W bits of Q / t
+    template <typename T> inline int noise_budget_bits(T noise_max, int q_count)
+    {
+        constexpr int W = static_cast<int>(8 * sizeof(T));
+        unsigned __int128 v = static_cast<unsigned __int128>(noise_max) + 3u * static_cast<unsigned>(q_count);
+        int bits = 0;
+        for (; v != 0; v >>= 1)
+            bits++;
+        return W - 1 - bits > 0 ? W - 1 - bits : 0;
+    }
 
     // The plan's constants as the host derived them (BfvMultiplyPlan::constants, gpuntt_bfv_constants_*): every pointer
     // is a caller array of the stated length.
@@ -204,6 +274,16 @@ namespace gpuntt
                                       const KeySwitchPlan<T>& key_switch, const T* device_key, T* device_out, int count,
                                       bool input_ntt, bool output_ntt, void* scratch_device,
                                       void* key_switch_scratch_device, stream_t stream) const;
+        // encode, decode and decrypt ("Reading a result back" above)
+        void scale_message(const T* device_message, T* device_out, int count, bool to_ntt, stream_t stream) const;
+        void decode(const T* device_x, T* device_message_out, T* device_noise_max, int stacks, stream_t stream,
+                    void* partials_device = nullptr) const;
+        size_t decode_partials_bytes(int stacks) const; // the partial maxima of the two-launch decode
+        size_t decrypt_scratch_bytes(int count) const; // T[count][L][N]
+        void decrypt(const T* device_ct, const KeySwitchPlan<T>& key_switch, const T* device_s_ntt,
+                     T* device_message_out, T* device_noise_max, int count, int components, bool input_ntt,
+                     void* scratch_device, void* key_switch_scratch_device, stream_t stream) const;
+
         int max_terms() const; // min(BFV_MAX_TERMS, floor(B / (2 t N Q))), fixed at construction; >= 1
         static size_t sum_scratch_bytes(int q_count, int b_count, int n_power, int count, int operands);
         size_t sum_scratch_bytes(int count, int operands) const;

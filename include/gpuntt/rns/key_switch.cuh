@@ -360,8 +360,39 @@
 //       out[0][r][m][j] = (E[r][m][j] - a[r][m][j] s[m][j] + message[r][m][j]) mod q_m, canonical.
 //     The same kernel over the first L limbs, one row per ciphertext, the message in the gadget term's place with
 //     multiplier 1.  The scratch is encrypt_scratch_bytes(count) bytes (T[count][L][N]), 256-byte aligned; refusals as
-//     for generate_keys (count < 0 in the place of keys).  Not here: public-key encryption, coefficient-form output,
-//     fixed-Hamming-weight secrets, BGV error scaling, a sampler fused into the combine kernel
+//     for generate_keys (count < 0 in the place of keys).  Public-key encryption: encrypt_public below.  Not here:
+//     coefficient-form output, fixed-Hamming-weight secrets, BGV error scaling, a sampler fused into the combine kernel
+//     
+//
+// Decryption and public-key encryption (the kernels are in decrypt.hip).
+//   phase(ct, s_ntt, out, count, components, input_ntt, output_ntt, scratch):  c0 + c1 s [+ c2 s^2], what CKKS and BFV both
+//     decrypt from.  components in {2, 3}; ct = T[components][count][L][N]; s_ntt = T[M][N] as encrypt_symmetric takes it
+//     (any word, read modulo its limb; only the first L limbs are read); out = T[count][L][N].  DEFINITION, word for word:
+//       1. [input_ntt false: the q-base GPU_NTT of ct into the scratch, components * count * L polynomials; canonical
+//          words are required, as for any transform]
+//       2. out[r][m][j] = (c0[r][m][j] + c1[r][m][j] s[m][j] + c2[r][m][j] s[m][j]^2) mod q_m, canonical, from ANY input
+//          words (c2 = 0 with two components)
+//       3. [output_ntt false: the q-base GPU_INTT of out in place, count * L polynomials]
+//     What runs: [the NTT,] ONE launch of decrypt_phase -- the exact accumulator of the inner product seeded with c0, one
+//     mac per product, one fold per output word; with three components s^2 is formed in registers at three more Shoup
+//     products per word (one makes s canonical, two are the partial fold of s * s) -- [the INTT].  phase_scratch_bytes(count,
+//     components, input_ntt) is 0 for NTT-form input (the scratch may then be nullptr) and T[components][count][L][N]
+//     otherwise, 256-byte aligned.  out may be exactly ct (component 0's place) in NTT form.  Allocates nothing, never
+//     synchronises, capturable as it is; count = 0 launches nothing.  std::invalid_argument, before anything is
+//     launched: components outside {2, 3} ("Invalid components!"), count < 0 or components * count * L beyond an int, a
+//     null pointer, out overlapping ct (other than being exactly ct in NTT form) or s, the scratch overlapping ct, s or
+//     out, a misaligned scratch, a transform on a plan without transforms
+//   encrypt_public(pk, small, message_ntt, out, count, scratch):  pk = T[2][L][N] in NTT form, any word -- what
+//     encrypt_symmetric(count = 1, message = nullptr) leaves in out: pk0 + pk1 s = e_pk; small = int32[3][count][N] holding
+//     (u, e0, e1), any value; message_ntt = T[count][L][N] in NTT form (any word) or nullptr; out = T[2][count][L][N].
+//     DEFINITION, with U, E0, E1 = the q-base GPU_NTT of lift_small(small):
+//       out[0][r][m][j] = (pk[0][m][j] U[r][m][j] + E0[r][m][j] + message[r][m][j]) mod q_m
+//       out[1][r][m][j] = (pk[1][m][j] U[r][m][j] + E1[r][m][j]) mod q_m,
+//     both canonical: out0 + out1 s = m + e_pk u + e0 + e1 s.  What runs: ONE lift_small over 3 * count polynomials into
+//     the scratch T[3][count][L][N] (encrypt_public_scratch_bytes(count) bytes, 256-byte aligned), ONE q-base NTT over
+//     3 * count * L polynomials, ONE launch of encrypt_public_combine, which writes both components from one read of U
+//     (keygen_combine's accumulator and fold).  Refusals as for encrypt_symmetric.  Not here: a sampler fused into the
+//     kernel, coefficient-form output, BGV error scaling
 //
 //   * ranges: 1 <= L, 1 <= K, M = L + K <= 64, alpha >= 1, 1 <= components <= 4, count >= 0 and stacks >= 0 (0: nothing
 //     happens), n_power in [1, 28], M <= key_mod_count <= 256.  A plan is built for ONE level (one L) and one ring; a
@@ -512,6 +543,14 @@ namespace gpuntt
                            T* const* device_keys_host, int keys, void* scratch_device, stream_t stream) const;
         void encrypt_symmetric(const T* device_s_ntt, const std::int32_t* device_errors, const T* device_message_ntt,
                                T* device_out, int count, void* scratch_device, stream_t stream) const;
+
+        // decryption and public-key encryption ("Decryption and public-key encryption" above)
+        size_t phase_scratch_bytes(int count, int components, bool input_ntt) const; // 0 for NTT-form input
+        void phase(const T* device_ct, const T* device_s_ntt, T* device_out, int count, int components, bool input_ntt,
+                   bool output_ntt, void* scratch_device, stream_t stream) const;
+        size_t encrypt_public_scratch_bytes(int count) const; // T[3][count][L][N]
+        void encrypt_public(const T* device_pk, const std::int32_t* device_small, const T* device_message_ntt,
+                            T* device_out, int count, void* scratch_device, stream_t stream) const;
 
         int q_count() const;
         int rescale_limbs() const; // R

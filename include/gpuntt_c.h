@@ -36,6 +36,8 @@
  *                               digit partition, ModUp of all digits in one launch, the inner product, the transforms
  *                               and ModDown in place inside the stacks; host-only constants and references;
  *                               key material: lift_small, generate_keys, encrypt_symmetric
+ *                               decryption and public-key encryption: phase, encrypt_public; gpuntt_bfv_plan_*:
+ *                               scale_message, decode, decrypt
  *   gpuntt_sample_*, gpuntt_philox4x32_10
  *                               extension counter-based samplers (include/gpuntt/rns/sampling.cuh): uniform residues and
  *                               small polynomials, with host references; not a cryptographic generator
@@ -857,6 +859,65 @@ extern "C"
     int gpuntt_keyswitch_plan_encrypt_symmetric_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* s,
                                                     const int32_t* errors, const uint64_t* message, uint64_t* out, int count,
                                                     void* scratch, void* stream);
+
+    /* ---- decryption and public-key encryption (key_switch.cuh, "Decryption and public-key encryption";
+     *      bfv_multiply.cuh, "Reading a result back") ----
+     *   phase: ct T[components][count][L][N] (components 2 or 3), s T[M][N] in NTT form, out T[count][L][N] =
+     *     c0 + c1 s [+ c2 s^2]; the scratch is phase_scratch_bytes bytes (0 and NULL accepted for NTT-form input).
+     *   encrypt_public: pk T[2][L][N] in NTT form, small int32[3][count][N] = (u, e0, e1), message T[count][L][N] in NTT
+     *     form or NULL, out T[2][count][L][N]; the scratch is encrypt_public_scratch_bytes bytes.
+     *   bfv scale_message: message T[count][N] (read modulo t) -> out T[count][L][N] = round(Q m / t) in the q-base.
+     *   bfv decode: x T[stacks][L][N] in coefficient form -> message_out T[stacks][N], noise_max T[stacks] or NULL.
+     *   bfv decrypt: phase into the scratch (decrypt_scratch_bytes bytes), then decode; key_switch_scratch is the
+     *     key-switching plan's phase_scratch_bytes bytes.
+     *   noise_budget_bits (host only): max(0, W - 1 - bit_length(noise_max + 3 q_count)). */
+    int gpuntt_keyswitch_plan_phase_scratch_bytes_u32(const gpuntt_keyswitch_plan* plan, int count, int components,
+                                                      int input_ntt, uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_phase_scratch_bytes_u64(const gpuntt_keyswitch_plan* plan, int count, int components,
+                                                      int input_ntt, uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_phase_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* ct, const uint32_t* s,
+                                        uint32_t* out, int count, int components, int input_ntt, int output_ntt,
+                                        void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_phase_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* ct, const uint64_t* s,
+                                        uint64_t* out, int count, int components, int input_ntt, int output_ntt,
+                                        void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_encrypt_public_scratch_bytes_u32(const gpuntt_keyswitch_plan* plan, int count,
+                                                               uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_encrypt_public_scratch_bytes_u64(const gpuntt_keyswitch_plan* plan, int count,
+                                                               uint64_t* bytes_host);
+    int gpuntt_keyswitch_plan_encrypt_public_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* pk,
+                                                 const int32_t* small, const uint32_t* message, uint32_t* out, int count,
+                                                 void* scratch, void* stream);
+    int gpuntt_keyswitch_plan_encrypt_public_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* pk,
+                                                 const int32_t* small, const uint64_t* message, uint64_t* out, int count,
+                                                 void* scratch, void* stream);
+    int gpuntt_bfv_plan_scale_message_u32(const gpuntt_bfv_plan* plan, const uint32_t* message, uint32_t* out, int count,
+                                          int to_ntt, void* stream);
+    int gpuntt_bfv_plan_scale_message_u64(const gpuntt_bfv_plan* plan, const uint64_t* message, uint64_t* out, int count,
+                                          int to_ntt, void* stream);
+    int gpuntt_bfv_plan_decode_u32(const gpuntt_bfv_plan* plan, const uint32_t* x, uint32_t* message_out,
+                                   uint32_t* noise_max, int stacks, void* stream);
+    int gpuntt_bfv_plan_decode_u64(const gpuntt_bfv_plan* plan, const uint64_t* x, uint64_t* message_out,
+                                   uint64_t* noise_max, int stacks, void* stream);
+    /* decode with noise_max from two launches and no memset: partials is decode_partials_bytes bytes of device memory */
+    int gpuntt_bfv_plan_decode_partials_bytes_u32(const gpuntt_bfv_plan* plan, int stacks, uint64_t* bytes_host);
+    int gpuntt_bfv_plan_decode_partials_bytes_u64(const gpuntt_bfv_plan* plan, int stacks, uint64_t* bytes_host);
+    int gpuntt_bfv_plan_decode_two_launch_u32(const gpuntt_bfv_plan* plan, const uint32_t* x, uint32_t* message_out,
+                                              uint32_t* noise_max, int stacks, void* partials, void* stream);
+    int gpuntt_bfv_plan_decode_two_launch_u64(const gpuntt_bfv_plan* plan, const uint64_t* x, uint64_t* message_out,
+                                              uint64_t* noise_max, int stacks, void* partials, void* stream);
+    int gpuntt_bfv_plan_decrypt_scratch_bytes_u32(const gpuntt_bfv_plan* plan, int count, uint64_t* bytes_host);
+    int gpuntt_bfv_plan_decrypt_scratch_bytes_u64(const gpuntt_bfv_plan* plan, int count, uint64_t* bytes_host);
+    int gpuntt_bfv_plan_decrypt_u32(const gpuntt_bfv_plan* plan, const uint32_t* ct,
+                                    const gpuntt_keyswitch_plan* key_switch, const uint32_t* s, uint32_t* message_out,
+                                    uint32_t* noise_max, int count, int components, int input_ntt, void* scratch,
+                                    void* key_switch_scratch, void* stream);
+    int gpuntt_bfv_plan_decrypt_u64(const gpuntt_bfv_plan* plan, const uint64_t* ct,
+                                    const gpuntt_keyswitch_plan* key_switch, const uint64_t* s, uint64_t* message_out,
+                                    uint64_t* noise_max, int count, int components, int input_ntt, void* scratch,
+                                    void* key_switch_scratch, void* stream);
+    int gpuntt_bfv_noise_budget_bits_u32(uint32_t noise_max, int q_count);
+    int gpuntt_bfv_noise_budget_bits_u64(uint64_t noise_max, int q_count);
 
     /* frees the library-owned scratch buffers of the drop-in entry points (synchronises the device); only when no
      * hipGraph captured from drop-in calls will be replayed again and no call is in flight */
