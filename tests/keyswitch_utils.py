@@ -5,6 +5,9 @@ import math
 
 import numpy as np
 
+from innerprod_utils import from_words
+
+GUARD = 4096  # bytes of 0xA5 on either side of a guarded buffer
 # (L, K, alpha): a single digit, D = L, an uneven last digit, alpha above the 16-term chunk, M = 64, L = 63 with one
 # special prime
 SHAPES = [(1, 1, 1), (3, 1, 1), (5, 2, 2), (8, 3, 3), (4, 4, 4), (40, 24, 20), (63, 1, 1)]
@@ -134,3 +137,37 @@ def public_sequence(g, plan, inner, st, c_in, key, count, C, input_ntt, output_n
         g.GPU_NTT_Inplace(out, st["fwd"], st["mods"], cfg_f, C * count * L, L)
     torch.cuda.synchronize()
     return out, a
+
+
+def unmodified(tensors, keep):
+    import torch
+    assert all(torch.equal(t, k) for t, k in zip(tensors, keep)), "an input was modified"
+
+
+def column_sample(total, seed):
+    """at least 2048 of the `total` = count N columns: the first and the last 64, both sides of every multiple of 2^13,
+    2048 seeded random ones"""
+    cols = set(range(64)) | set(range(total - 64, total))
+    for m in range(1 << 13, total, 1 << 13):
+        cols |= {m - 1, m}
+    cols |= set(int(c) for c in np.random.default_rng(seed).choice(total, size=2048, replace=False))
+    assert len(cols) >= 2048
+    return np.array(sorted(cols))
+
+
+def columns_of(flat, lead, count, rows, n, cols):
+    """flat words of a [lead][count][rows][N] -> Python integers [lead][rows][len(cols)]; columns count over count N"""
+    x = np.asarray(flat).reshape(lead, count, rows, n).transpose(0, 2, 1, 3).reshape(lead, rows, count * n)
+    return from_words(np.ascontiguousarray(x[:, :, cols]), (lead, rows, len(cols)))
+
+
+def guarded(nbytes):
+    """exactly nbytes from the middle of a buffer of 0xA5; returns (the buffer, the view)"""
+    import torch
+    big = torch.full((nbytes + 2 * GUARD,), 0xA5, dtype=torch.uint8, device="cuda:0")
+    assert big.data_ptr() % 256 == 0
+    return big, big[GUARD:GUARD + nbytes]
+
+
+def guards_intact(big):
+    return bool((big[:GUARD] == 0xA5).all()) and bool((big[-GUARD:] == 0xA5).all())

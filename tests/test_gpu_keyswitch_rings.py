@@ -32,7 +32,8 @@ from hoisted_sum_utils import composition_sum, make_weights, sum_scratch, with_n
 from hoisted_utils import (WIDE_WIDTHS, any_words, canonical_key, composition, device_words, elements_for, filled,
                            make_plan, ring, tdtype)
 from innerprod_utils import from_words, moduli, words
-from keyswitch_utils import planted_input, public_sequence, ref_mod_down, ref_mod_up
+from keyswitch_utils import (column_sample, columns_of, guarded, guards_intact, planted_input, public_sequence,
+                             ref_mod_down, ref_mod_up, unmodified)
 from relin_exact import exact_multiply_relinearize
 from relin_sum_exact import exact_multiply_relinearize_sum
 from relin_sum_utils import composition_relin_sum, relin_sum_operands
@@ -43,7 +44,6 @@ pytestmark = pytest.mark.gpu
 N_POWERS = (13, 14, 15, 16)
 SHAPE, SHAPE_D3 = (3, 2, 2), (6, 2, 2)  # D = 2, M = 5 and D = 3, M = 8
 G, T = 3, 3
-GUARD = 4096
 
 # (bits, n_power, prime set, (L, K, alpha)): every ring on the default and the widest primes (62/61 and 30/29 bits: the
 # 4 q / 8 q kernels, 4096-coefficient tiles), 45-bit primes at u64 2^16 (the 31 q forward family), D = 3 once per word
@@ -124,29 +124,7 @@ def run_checked(s, eligible, call, out, want, what, prefill=True):
             g.set_test_hook("contig_p4", "1")
 
 
-def unmodified(tensors, keep):
-    import torch
-    assert all(torch.equal(t, k) for t, k in zip(tensors, keep)), "an input was modified"
-
-
 # ------------------------------------------------------------------------------- 1. mod_up and mod_down at real sizes
-def column_sample(total, seed):
-    """at least 2048 of the `total` = count N columns: the first and the last 64, both sides of every multiple of 2^13,
-    2048 seeded random ones"""
-    cols = set(range(64)) | set(range(total - 64, total))
-    for m in range(1 << 13, total, 1 << 13):
-        cols |= {m - 1, m}
-    cols |= set(int(c) for c in np.random.default_rng(seed).choice(total, size=2048, replace=False))
-    assert len(cols) >= 2048
-    return np.array(sorted(cols))
-
-
-def columns_of(flat, lead, count, rows, n, cols):
-    """flat words of a [lead][count][rows][N] -> Python integers [lead][rows][len(cols)]; columns count over count N"""
-    x = np.asarray(flat).reshape(lead, count, rows, n).transpose(0, 2, 1, 3).reshape(lead, rows, count * n)
-    return from_words(np.ascontiguousarray(x[:, :, cols]), (lead, rows, len(cols)))
-
-
 MOD_CASES = [(bits, n_power, shape) for bits in (64, 32) for n_power in N_POWERS for shape in ((3, 2, 2), (8, 3, 3))]
 MOD_CASES.append((64, 13, (40, 24, 20)))  # the 64-lane form
 
@@ -477,18 +455,6 @@ def test_against_exact_integers_at_2_16_on_the_widest_primes(g, entry, bits):
 
 
 # ------------------------------------------------------------- 4. workspace, scratch, chunks, alignment, graph at 2^16
-def guarded(nbytes):
-    """exactly nbytes from the middle of a buffer of 0xA5; returns (the buffer, the view)"""
-    import torch
-    big = torch.full((nbytes + 2 * GUARD,), 0xA5, dtype=torch.uint8, device="cuda:0")
-    assert big.data_ptr() % 256 == 0
-    return big, big[GUARD:GUARD + nbytes]
-
-
-def guards_intact(big):
-    return bool((big[:GUARD] == 0xA5).all()) and bool((big[-GUARD:] == 0xA5).all())
-
-
 def five_entry_points(plan, data, outs, scratches):
     """every pipeline call of the family on one plan; outs / scratches: dicts by entry point"""
     count, C = data["count"], data["C"]
