@@ -139,10 +139,13 @@ EXPORTED_SYMBOLS = ["gpuntt_last_error", "gpuntt_version"] + [
               "keyswitch_plan_encrypt_public_scratch_bytes", "keyswitch_plan_encrypt_public",
               "bfv_plan_scale_message", "bfv_plan_decode", "bfv_plan_decode_partials_bytes",
               "bfv_plan_decode_two_launch", "bfv_plan_decrypt_scratch_bytes", "bfv_plan_decrypt",
-              "bfv_noise_budget_bits")
+              "bfv_noise_budget_bits",
+              "bfv_encoder_workspace_bytes", "bfv_encoder_scratch_bytes", "bfv_encoder_create", "bfv_encoder_encode",
+              "bfv_encoder_decode", "bfv_encoder_owns_workspace", "bfv_encoder_destroy",
+              "keyswitch_plan_lift_centred", "keyswitch_plan_multiply_plain")
     for s in ("u32", "u64")] + ["gpuntt_release_workspaces", "gpuntt_set_option", "gpuntt_galois_element_u32",
                                 "gpuntt_automorphism_index_map", "gpuntt_philox4x32_10", "gpuntt_sample_small",
-                                "gpuntt_sample_reference_small"]
+                                "gpuntt_sample_reference_small", "gpuntt_bfv_slot_maps"]
 
 # GPUNTT_* environment variables of the A/B scripts and tests -> library options.  The C++ library reads no
 # environment variable; this harness forwards them once, when it loads the library.
@@ -1641,6 +1644,37 @@ class KeySwitchPlan:
         _check(fn(self._h, _ptr(pk), _ptr(small), _ptr(message), _ptr(out), int(count), _ptr(scratch),
                   _stream(stream)))
 
+    # plaintext operands (key_switch.cuh, "Plaintext operands")
+    def lift_centred(self, words, plain_modulus, out, polys, full_base=True, to_ntt=True, stream=None):
+        """words T[polys][N] (any words, read modulo plain_modulus and centred: m - t from (t + 1) >> 1 on) -> out
+        T[polys][M or L][N], the canonical residues; with to_ntt the plan's forward transform over that base follows in
+        place.  One launch plus the transform's own.  How a plaintext (BfvBatchEncoder.encode) becomes an operand of
+        multiply_plain (q-base) or a diagonal of rotate_hoisted_sum / linear_transform_bsgs (full base)."""
+        if words is None or out is None:
+            raise ValueError("null pointer argument")
+        if not 0 <= int(plain_modulus) < 1 << self.bits:
+            raise ValueError("Invalid plaintext modulus!")
+        cols = self._cols(polys)
+        self._check_buffers(((words, cols, "words (polys x N)"),
+                             (out, cols * (self.mod_count if full_base else self.q_count), "out (polys x B x N)")))
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_lift_centred_u%d" % self.bits)
+        _check(fn(self._h, _ptr(words), _ct(self.bits)(int(plain_modulus)), _ptr(out), int(polys),
+                  int(bool(full_base)), int(bool(to_ntt)), _stream(stream)))
+
+    def multiply_plain(self, ct, pt, out, count, plain_count=1, stream=None):
+        """ct T[2][count][L][N] times pt T[plain_count][L][N] word by word modulo q_i, both in NTT form and any words;
+        plain_count 1 (one plaintext for every ciphertext) or count -> out T[2][count][L][N], canonical; out may be ct
+        itself.  One launch."""
+        if ct is None or pt is None or out is None:
+            raise ValueError("null pointer argument")
+        cols = self._cols(count)
+        pc = int(plain_count) if int(plain_count) in (1, int(count)) else 0
+        self._check_buffers(((ct, 2 * cols * self.q_count, "ct (2 x count x L x N)"),
+                             (pt, (pc * self.q_count) << self.n_power, "pt (plain_count x L x N)"),
+                             (out, 2 * cols * self.q_count, "out (2 x count x L x N)")))
+        fn = getattr(load_library(), "gpuntt_keyswitch_plan_multiply_plain_u%d" % self.bits)
+        _check(fn(self._h, _ptr(ct), _ptr(pt), _ptr(out), int(count), int(plain_count), _stream(stream)))
+
     def close(self):
         if self._h:
             getattr(load_library(), "gpuntt_keyswitch_plan_destroy_u%d" % self.bits)(self._h)
@@ -2081,6 +2115,109 @@ class BfvMultiplyPlan:
     def close(self):
         if self._h:
             getattr(load_library(), "gpuntt_bfv_plan_destroy_u%d" % self.bits)(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bfv_slot_maps(n_power):
+    """Host (no GPU): (to_position, to_slot), two uint32 arrays of N entries -- where GPU_NTT's output holds slot
+    r N/2 + c of the 2 x N/2 BFV slot matrix, and the inverse (include/gpuntt/rns/bfv_encode.cuh has the convention)."""
+    if not 1 <= int(n_power) <= 28:
+        raise ValueError("Invalid n_power range!")
+    to_position = np.empty(1 << int(n_power), dtype=np.uint32)
+    to_slot = np.empty_like(to_position)
+    _check(load_library().gpuntt_bfv_slot_maps(int(n_power), to_position.ctypes.data_as(ctypes.c_void_p),
+                                               to_slot.ctypes.data_as(ctypes.c_void_p)))
+    return to_position, to_slot
+
+
+class BfvBatchEncoder:
+    """Extension BfvBatchEncoder<T> (include/gpuntt/rns/bfv_encode.cuh): BFV batching for the plaintext modulus
+    `plain_modulus` (a Modulus with t = 1 mod 2N) on a ring of 2^n_power.  forward_table / inverse_table: device tensors
+    modulo t as for GPU_NTT / GPU_INTT with X_N_plus, n_inverse = N^-1 mod t.  `workspace`: an optional uint8 device
+    tensor of workspace_bytes() bytes owned by the caller.  encode takes slot values to coefficients modulo t, decode
+    back; decode needs a caller-owned scratch of scratch_bytes(count) bytes, 256-byte aligned."""
+
+    def __init__(self, plain_modulus, n_power, forward_table, inverse_table, n_inverse, batch_hint=1024, stream=None,
+                 workspace=None):
+        lib = load_library()
+        _require_gpu(workspace, forward_table, inverse_table)
+        self.bits, self.n_power, self.plain_modulus = plain_modulus.bits, int(n_power), int(plain_modulus.value)
+        for t in (forward_table, inverse_table):
+            if t is not None and 1 <= self.n_power <= 28 and (t.element_size() * 8 != self.bits or
+                                                              t.numel() < 1 << self.n_power):
+                raise ValueError("a table holds N %d-bit words" % self.bits)
+        if workspace is not None:
+            need = self.workspace_bytes(n_power, self.bits)  # raises for an n_power out of range
+            if workspace.numel() * workspace.element_size() < need:
+                raise ValueError("workspace holds fewer than workspace_bytes() bytes")
+        self._keep = (workspace, forward_table, inverse_table)
+        self._h = ctypes.c_void_p()
+        fn = getattr(lib, "gpuntt_bfv_encoder_create_u%d" % self.bits)
+        _check(fn(ctypes.byref(self._h), plain_modulus.c(), int(n_power), _ptr(forward_table), _ptr(inverse_table),
+                  _ct(self.bits)(int(n_inverse)), int(batch_hint), _ptr(workspace), _stream(stream)))
+
+    @staticmethod
+    def workspace_bytes(n_power, bits=64):
+        out = ctypes.c_uint64()
+        _check(getattr(load_library(), "gpuntt_bfv_encoder_workspace_bytes_u%d" % bits)(int(n_power), ctypes.byref(out)))
+        return int(out.value)
+
+    def scratch_bytes(self, count):
+        """the caller-owned scratch of decode: T[count][N], rounded up to 256 bytes"""
+        out = ctypes.c_uint64()
+        _check(getattr(load_library(), "gpuntt_bfv_encoder_scratch_bytes_u%d" % self.bits)(
+            self.n_power, int(count), ctypes.byref(out)))
+        return int(out.value)
+
+    @property
+    def owns_workspace(self):
+        """False: the plan lives in the caller's workspace and has allocated no device memory"""
+        return bool(getattr(load_library(), "gpuntt_bfv_encoder_owns_workspace_u%d" % self.bits)(self._h))
+
+    def _check_buffers(self, sized):
+        """the library cannot see tensor sizes or types: sized = (tensor, words needed, name) ..."""
+        _require_gpu(*[t for t, _, _ in sized])
+        for t, words, name in sized:
+            if t.element_size() * 8 != self.bits or t.dtype.is_floating_point:
+                raise ValueError("a %d-bit BfvBatchEncoder takes %d-bit integer tensors" % (self.bits, self.bits))
+            if words > 0 and t.numel() < words:
+                raise ValueError("%s needs %d words; got %d" % (name, words, t.numel()))
+
+    def _cols(self, count):
+        return (int(count) << self.n_power) if int(count) > 0 else 0
+
+    def encode(self, values, plain, count, stream=None):
+        """values T[count][N] (any words, read modulo t, indexed by slot) -> plain T[count][N], the coefficients modulo
+        t: one bfv_slot_permute, then the inverse transform modulo t in place"""
+        if values is None or plain is None:
+            raise ValueError("null pointer argument")
+        cols = self._cols(count)
+        self._check_buffers(((values, cols, "values (count x N)"), (plain, cols, "plain (count x N)")))
+        fn = getattr(load_library(), "gpuntt_bfv_encoder_encode_u%d" % self.bits)
+        _check(fn(self._h, _ptr(values), _ptr(plain), int(count), _stream(stream)))
+
+    def decode(self, plain, values, count, scratch, stream=None):
+        """plain T[count][N] (canonical coefficients modulo t, left untouched) -> values T[count][N] by slot: the
+        forward transform modulo t into the scratch, then one bfv_slot_permute"""
+        if plain is None or values is None or scratch is None:
+            raise ValueError("null pointer argument")
+        cols = self._cols(count)
+        self._check_buffers(((plain, cols, "plain (count x N)"), (values, cols, "values (count x N)")))
+        _require_gpu(scratch)
+        if int(count) >= 0 and scratch.numel() * scratch.element_size() < self.scratch_bytes(count):
+            raise ValueError("scratch holds fewer than scratch_bytes(count) bytes")
+        fn = getattr(load_library(), "gpuntt_bfv_encoder_decode_u%d" % self.bits)
+        _check(fn(self._h, _ptr(plain), _ptr(values), int(count), _ptr(scratch), _stream(stream)))
+
+    def close(self):
+        if self._h:
+            getattr(load_library(), "gpuntt_bfv_encoder_destroy_u%d" % self.bits)(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

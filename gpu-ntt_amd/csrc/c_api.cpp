@@ -11,6 +11,7 @@
 #include "gpuntt/ntt_merge/galois.cuh"
 #include "gpuntt/ntt_merge/ntt.cuh"
 #include "gpuntt/rns/base_conversion.cuh"
+#include "gpuntt/rns/bfv_encode.cuh"
 #include "gpuntt/rns/bfv_multiply.cuh"
 #include "gpuntt/rns/inner_product.cuh"
 #include "gpuntt/rns/key_switch.cuh"
@@ -606,6 +607,11 @@ extern "C"
         });
     }
 
+    int gpuntt_bfv_slot_maps(int n_power, uint32_t* to_position_host, uint32_t* to_slot_host)
+    {
+        return guarded([&] { bfv_slot_maps(n_power, to_position_host, to_slot_host); });
+    }
+
     int gpuntt_modulus_u32(uint32_t q, gpuntt_modulus32* out)
     {
         return guarded([&] {
@@ -1182,6 +1188,72 @@ extern "C"
             reinterpret_cast<const KeySwitchPlan<T>*>(plan)->encrypt_public(                      \
                 pk, small, message, out, count, scratch, static_cast<hipStream_t>(stream));       \
         });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_lift_centred_##S(const gpuntt_keyswitch_plan* plan, const T* words, T plain_modulus,\
+                                               T* out, int polys, int full_base, int to_ntt, void* stream)\
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->lift_centred(                        \
+                words, plain_modulus, out, polys, full_base != 0, to_ntt != 0, static_cast<hipStream_t>(stream));\
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_keyswitch_plan_multiply_plain_##S(const gpuntt_keyswitch_plan* plan, const T* ct, const T* pt,\
+                                                 T* out, int count, int plain_count, void* stream)\
+    {                                                                                             \
+        GPUNTT_NEED(plan)                                                                         \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const KeySwitchPlan<T>*>(plan)->multiply_plain(                      \
+                ct, pt, out, count, plain_count, static_cast<hipStream_t>(stream));               \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_encoder_workspace_bytes_##S(int n_power, uint64_t* bytes_host)                 \
+    {                                                                                             \
+        GPUNTT_NEED(bytes_host)                                                                   \
+        return guarded([&] { *bytes_host = BfvBatchEncoder<T>::workspace_bytes(n_power); });       \
+    }                                                                                             \
+    int gpuntt_bfv_encoder_scratch_bytes_##S(int n_power, int count, uint64_t* bytes_host)        \
+    {                                                                                             \
+        GPUNTT_NEED(bytes_host)                                                                   \
+        return guarded([&] { *bytes_host = BfvBatchEncoder<T>::scratch_bytes(n_power, count); });  \
+    }                                                                                             \
+    int gpuntt_bfv_encoder_create_##S(gpuntt_bfv_encoder** encoder_host, CM plain_modulus, int n_power,\
+                                      const T* forward_table, const T* inverse_table, T n_inverse,\
+                                      int batch_hint, void* workspace_device, void* stream)       \
+    {                                                                                             \
+        GPUNTT_NEED(encoder_host)                                                                 \
+        return guarded([&] {                                                                      \
+            *encoder_host = reinterpret_cast<gpuntt_bfv_encoder*>(new BfvBatchEncoder<T>(         \
+                to_mod<T>(plain_modulus), n_power, forward_table, inverse_table, n_inverse, batch_hint,\
+                static_cast<hipStream_t>(stream), workspace_device));                             \
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_encoder_encode_##S(const gpuntt_bfv_encoder* encoder, const T* values, T* plain, int count,\
+                                      void* stream)                                               \
+    {                                                                                             \
+        GPUNTT_NEED(encoder)                                                                      \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const BfvBatchEncoder<T>*>(encoder)->encode(values, plain, count,    \
+                                                                         static_cast<hipStream_t>(stream));\
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_encoder_decode_##S(const gpuntt_bfv_encoder* encoder, const T* plain, T* values, int count,\
+                                      void* scratch, void* stream)                                \
+    {                                                                                             \
+        GPUNTT_NEED(encoder)                                                                      \
+        return guarded([&] {                                                                      \
+            reinterpret_cast<const BfvBatchEncoder<T>*>(encoder)->decode(plain, values, count, scratch,\
+                                                                         static_cast<hipStream_t>(stream));\
+        });                                                                                       \
+    }                                                                                             \
+    int gpuntt_bfv_encoder_owns_workspace_##S(const gpuntt_bfv_encoder* encoder)                  \
+    {                                                                                             \
+        GPUNTT_NEED(encoder)                                                                      \
+        return reinterpret_cast<const BfvBatchEncoder<T>*>(encoder)->owns_workspace() ? 1 : 0;    \
+    }                                                                                             \
+    int gpuntt_bfv_encoder_destroy_##S(gpuntt_bfv_encoder* encoder)                               \
+    {                                                                                             \
+        return guarded([&] { delete reinterpret_cast<BfvBatchEncoder<T>*>(encoder); });           \
     }                                                                                             \
     int gpuntt_bfv_plan_scale_message_##S(const gpuntt_bfv_plan* plan, const T* message, T* out, int count,\
                                           int to_ntt, void* stream)                               \

@@ -1119,6 +1119,63 @@ namespace gpuntt
                 (full_base ? ntt_full_f : ntt_q_f)->execute(out, out, polys * B, stream);
         }
 
+        // Plaintext operands (keygen.hip)
+
+        // words: T[polys][N], read modulo t and centred -> out: T[polys][B][N], B = M (full_base) or L
+        void lift_centred(const T* words, T t, T* out, int polys, bool full_base, bool to_ntt, hipStream_t stream) const
+        {
+            if (to_ntt)
+                need_transforms();
+            if (t < 2 || (t >> (8 * sizeof(T) - 1)) != 0) // (Modulus<T> leaves mu = 0 from 2^(W-1) on and does not throw)
+                throw std::invalid_argument("Invalid plaintext modulus!");
+            try
+            {
+                (void) Modulus<T>(t); // what Modulus<T> accepts: below 2^(W-1), all the Shoup product by 1 needs
+            }
+            catch (const std::invalid_argument&)
+            {
+                throw std::invalid_argument("Invalid plaintext modulus!");
+            }
+            if (polys < 0)
+                throw std::invalid_argument("Invalid polys!");
+            if (words == nullptr || out == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            const int B = full_base ? M : L;
+            if (static_cast<unsigned long long>(polys) * static_cast<unsigned>(B) > 0x7FFFFFFFull) // the transforms' batch
+                throw std::invalid_argument("Invalid polys!");
+            if (polys == 0)
+                return;
+            const std::uint64_t cols = static_cast<std::uint64_t>(polys) << n;
+            if (rns_overlap(words, cols * sizeof(T), out, cols * B * sizeof(T)))
+                throw std::invalid_argument("The lift's input and output overlap!");
+            const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
+            host::lift_centred_launch<T>(words, out, consts, t, polys, B, M, n, false, stream);
+            host::lift_centred_launch<T>(words, out, consts, t, polys, B, M, n, true, stream);
+            if (to_ntt)
+                (full_base ? ntt_full_f : ntt_q_f)->execute(out, out, polys * B, stream);
+        }
+
+        // ct, out: T[2][count][L][N], pt: T[plain_count][L][N], all in NTT form
+        void multiply_plain(const T* ct, const T* pt, T* out, int count, int plain_count, hipStream_t stream) const
+        {
+            if (count < 0)
+                throw std::invalid_argument("Invalid count!");
+            if (plain_count != 1 && plain_count != count)
+                throw std::invalid_argument("Invalid plain_count!");
+            if (ct == nullptr || pt == nullptr || out == nullptr)
+                throw std::invalid_argument("null pointer argument");
+            if (count == 0)
+                return;
+            const std::uint64_t stack = (static_cast<std::uint64_t>(L) << n) * sizeof(T);
+            const std::uint64_t ct_bytes = 2 * stack * count, pt_bytes = stack * plain_count;
+            // out may be exactly ct: every word is written by the lane that read it, after its loads
+            if ((rns_overlap(out, ct_bytes, ct, ct_bytes) && out != ct) || rns_overlap(out, ct_bytes, pt, pt_bytes))
+                throw std::invalid_argument("out overlaps an operand!");
+            const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
+            host::multiply_plain_launch<T>(ct, pt, out, consts, count, plain_count, L, M, n, false, stream);
+            host::multiply_plain_launch<T>(ct, pt, out, consts, count, plain_count, L, M, n, true, stream);
+        }
+
         size_t keygen_scratch(int keys) const // E: T[keys][D][M][N]
         {
             if (keys < 0 || keys > KEYGEN_MAX_KEYS)
@@ -1356,6 +1413,18 @@ namespace gpuntt
                                       bool to_ntt, stream_t stream) const
     {
         p_->lift_small(device_small, device_out, polys, full_base, to_ntt, stream);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::lift_centred(const T* device_words, T plain_modulus, T* device_out, int polys, bool full_base,
+                                        bool to_ntt, stream_t stream) const
+    {
+        p_->lift_centred(device_words, plain_modulus, device_out, polys, full_base, to_ntt, stream);
+    }
+    template <typename T>
+    void KeySwitchPlan<T>::multiply_plain(const T* device_ct, const T* device_pt_ntt, T* device_out, int count,
+                                          int plain_count, stream_t stream) const
+    {
+        p_->multiply_plain(device_ct, device_pt_ntt, device_out, count, plain_count, stream);
     }
     template <typename T> size_t KeySwitchPlan<T>::keygen_scratch_bytes(int keys) const
     {

@@ -46,6 +46,18 @@ namespace gpuntt
         void keygen_lift_launch(const std::int32_t* small, T* out, const T* consts, int polys, int B, int M, int n_power,
                                 bool enqueue, hipStream_t stream);
 
+        // words: T[polys][N], any word, read modulo t and centred -> out: T[polys][B][N], the canonical residues under the
+        // first B moduli of the fold image.  t in [2, 2^(W-1)).  One launch.  enqueue false: only the checks
+        template <typename T>
+        void lift_centred_launch(const T* words, T* out, const T* consts, T t, int polys, int B, int M, int n_power,
+                                 bool enqueue, hipStream_t stream);
+
+        // ct, out: T[2][count][L][N] (out may be exactly ct), pt: T[plain_count][L][N], plain_count 1 (shared) or count.
+        // One launch.  enqueue false: only the checks.  Throws std::invalid_argument beyond the grid limits
+        template <typename T>
+        void multiply_plain_launch(const T* ct, const T* pt, T* out, const T* consts, int count, int plain_count, int L,
+                                   int M, int n_power, bool enqueue, hipStream_t stream);
+
         // keygen_combine: for every group g, row d, limb m < B and column j
         //   group[g][d * row + m N + j] = (E[g][d][m][j] - a * s[m][j] + [gadget on] mult[m] * gadget[...]) mod q_m
         // with a = group[g][d * row + a_at + m N + j]; gadget may be nullptr (no gadget term at all).  One launch.

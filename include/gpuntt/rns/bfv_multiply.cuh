@@ -181,8 +181,8 @@
 //     key_switch_scratch: key_switch.phase_scratch_bytes(count, components, input_ntt) bytes (nullptr is accepted where
 //     that is 0).  Every refusal of both calls arrives before the first launch.  Allocates nothing, never synchronises,
 //     one stream, capturable as it is (the memset is a node)
-//   Not here: CKKS encode / decode, BFV batching (an NTT modulo t), a centred multi-precision output of the phase, BGV,
-//     noise flooding, the INTT's last pass fused into bfv_decode
+//   Not here: CKKS encode / decode, a centred multi-precision output of the phase, BGV, noise flooding, the INTT's last
+//     pass fused into bfv_decode.  (BFV batching -- slots to and from the coefficients modulo t -- is rns/bfv_encode.cuh.)
 //
 //
 //   * transforms: as KeySwitchPlan -- ONE caller table pair in full-base order (slot i at i << n_power, the q-base is its

@@ -394,6 +394,25 @@
 //     (keygen_combine's accumulator and fold).  Refusals as for encrypt_symmetric.  Not here: a sampler fused into the
 //     kernel, coefficient-form output, BGV error scaling
 //
+// Plaintext operands (the kernels are in keygen.hip).  How a plaintext modulo a word-sized t -- what
+// BfvBatchEncoder::encode (rns/bfv_encode.cuh) writes -- becomes an operand of a ciphertext, on the device.
+//   lift_centred(words, t, out, polys, full_base, to_ntt):  a sibling of lift_small.  words = T[polys][N], any word;
+//     out = T[polys][B][N] with B = M (full_base) or L.  DEFINITION, in integers: m = word mod t, v = m - t if
+//     m >= (t + 1) >> 1, else m; out[p][i][j] = v mod modulus_i, canonical; with to_ntt the plan's forward transform
+//     over that base follows in place.  The centred lift multiplies the noise by |pt| <= t / 2 and not by t.  ONE launch
+//     (lift_centred) plus the transform's own; no scratch.  t is any value Modulus<T> accepts, from 2 on; it may exceed
+//     a limb's modulus.  This is how a plaintext operand of multiply_plain (q-base, NTT form) or a diagonal for
+//     rotate_hoisted_sum / linear_transform_bsgs (full base, NTT form) is made.  Refusals are lift_small's, and
+//     "Invalid plaintext modulus!" for a t outside that range
+//   multiply_plain(ct, pt_ntt, out, count, plain_count):  ct = T[2][count][L][N] and pt_ntt = T[plain_count][L][N], both in
+//     NTT form and both holding any word; plain_count in {1, count}: 1 means the plaintext is shared (otherwise
+//     "Invalid plain_count!").  out[c][r][i][j] = (ct[c][r][i][j] * pt[r or 0][i][j]) mod q_i, canonical.  ONE launch of
+//     multiply_plain, which writes both components from one read of the plaintext word: the inner product's mac and
+//     fold with one term, no new arithmetic.  out may be exactly ct; any other overlap of out with an operand is
+//     refused ("out overlaps an operand!").  Works on a plan without transforms.  Allocates nothing, never synchronises,
+//     capturable as it is; count = 0 launches nothing.  Not here: add_plain (one modular addition of scale_message's
+//     output to component 0), three-component inputs, a coefficient-form path
+//
 //   * ranges: 1 <= L, 1 <= K, M = L + K <= 64, alpha >= 1, 1 <= components <= 4, count >= 0 and stacks >= 0 (0: nothing
 //     happens), n_power in [1, 28], M <= key_mod_count <= 256.  A plan is built for ONE level (one L) and one ring; a
 //     caller at a lower level builds another plan and points it at the full-level key through key_mod_count /
@@ -543,6 +562,12 @@ namespace gpuntt
                            T* const* device_keys_host, int keys, void* scratch_device, stream_t stream) const;
         void encrypt_symmetric(const T* device_s_ntt, const std::int32_t* device_errors, const T* device_message_ntt,
                                T* device_out, int count, void* scratch_device, stream_t stream) const;
+
+        // plaintext operands ("Plaintext operands" above)
+        void lift_centred(const T* device_words, T plain_modulus, T* device_out, int polys, bool full_base, bool to_ntt,
+                          stream_t stream) const;
+        void multiply_plain(const T* device_ct, const T* device_pt_ntt, T* device_out, int count, int plain_count,
+                            stream_t stream) const;
 
         // decryption and public-key encryption ("Decryption and public-key encryption" above)
         size_t phase_scratch_bytes(int count, int components, bool input_ntt) const; // 0 for NTT-form input

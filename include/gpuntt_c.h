@@ -38,6 +38,10 @@
  *                               key material: lift_small, generate_keys, encrypt_symmetric
  *                               decryption and public-key encryption: phase, encrypt_public; gpuntt_bfv_plan_*:
  *                               scale_message, decode, decrypt
+ *                               plaintext operands: lift_centred, multiply_plain
+ *   gpuntt_bfv_encoder_*, gpuntt_bfv_slot_maps
+ *                               extension BFV batching (include/gpuntt/rns/bfv_encode.cuh): slots to and from the
+ *                               coefficients modulo t, one permutation launch and one transform per call
  *   gpuntt_sample_*, gpuntt_philox4x32_10
  *                               extension counter-based samplers (include/gpuntt/rns/sampling.cuh): uniform residues and
  *                               small polynomials, with host references; not a cryptographic generator
@@ -918,6 +922,58 @@ extern "C"
                                     void* key_switch_scratch, void* stream);
     int gpuntt_bfv_noise_budget_bits_u32(uint32_t noise_max, int q_count);
     int gpuntt_bfv_noise_budget_bits_u64(uint64_t noise_max, int q_count);
+
+    /* ---- BFV batching (include/gpuntt/rns/bfv_encode.cuh; key_switch.cuh, "Plaintext operands") ----
+     *   slot_maps (host only): to_position[N] indexed by slot, to_slot[N] its inverse, for the slot convention of
+     *     bfv_encode.cuh.  "Invalid n_power range!" outside [1, 28].
+     *   encoder create: t the modulus struct of the plaintext modulus, the tables modulo t on the device as for the
+     *     negacyclic transforms, n_inverse = N^-1 mod t.  "Plaintext modulus does not support batching!" unless
+     *     (t - 1) mod 2N = 0; "Invalid modulus!"; "Invalid n_power range!"; "null pointer argument".
+     *   encode: values T[count][N] (any word, by slot) -> plain T[count][N], coefficients modulo t.
+     *   decode: plain T[count][N] (canonical) -> values T[count][N]; the scratch is scratch_bytes bytes, 256-byte
+     *     aligned.  "Invalid count!", "null pointer argument", "encode input and output overlap!", "decode input and
+     *     output overlap!", "The scratch overlaps an operand!", "The scratch is not 256-byte aligned!".
+     *   lift_centred: words T[polys][N] read modulo t and centred -> out T[polys][M or L][N]; to_ntt: the plan's forward
+     *     transform follows in place.  "Invalid plaintext modulus!", "Invalid polys!", "null pointer argument", "The
+     *     lift's input and output overlap!".
+     *   multiply_plain: ct T[2][count][L][N] times pt T[plain_count][L][N] (plain_count 1 or count), word by word; out
+     *     may be ct.  "Invalid count!", "Invalid plain_count!", "null pointer argument", "out overlaps an operand!". */
+    typedef struct gpuntt_bfv_encoder gpuntt_bfv_encoder;
+    int gpuntt_bfv_slot_maps(int n_power, uint32_t* to_position_host, uint32_t* to_slot_host);
+    int gpuntt_bfv_encoder_workspace_bytes_u32(int n_power, uint64_t* bytes_host);
+    int gpuntt_bfv_encoder_workspace_bytes_u64(int n_power, uint64_t* bytes_host);
+    int gpuntt_bfv_encoder_scratch_bytes_u32(int n_power, int count, uint64_t* bytes_host);
+    int gpuntt_bfv_encoder_scratch_bytes_u64(int n_power, int count, uint64_t* bytes_host);
+    int gpuntt_bfv_encoder_create_u32(gpuntt_bfv_encoder** encoder_host, gpuntt_modulus32 plain_modulus, int n_power,
+                                      const uint32_t* forward_table, const uint32_t* inverse_table, uint32_t n_inverse,
+                                      int batch_hint, void* workspace_device, void* stream);
+    int gpuntt_bfv_encoder_create_u64(gpuntt_bfv_encoder** encoder_host, gpuntt_modulus64 plain_modulus, int n_power,
+                                      const uint64_t* forward_table, const uint64_t* inverse_table, uint64_t n_inverse,
+                                      int batch_hint, void* workspace_device, void* stream);
+    int gpuntt_bfv_encoder_encode_u32(const gpuntt_bfv_encoder* encoder, const uint32_t* values, uint32_t* plain,
+                                      int count, void* stream);
+    int gpuntt_bfv_encoder_encode_u64(const gpuntt_bfv_encoder* encoder, const uint64_t* values, uint64_t* plain,
+                                      int count, void* stream);
+    int gpuntt_bfv_encoder_decode_u32(const gpuntt_bfv_encoder* encoder, const uint32_t* plain, uint32_t* values,
+                                      int count, void* scratch, void* stream);
+    int gpuntt_bfv_encoder_decode_u64(const gpuntt_bfv_encoder* encoder, const uint64_t* plain, uint64_t* values,
+                                      int count, void* scratch, void* stream);
+    int gpuntt_bfv_encoder_owns_workspace_u32(const gpuntt_bfv_encoder* encoder);
+    int gpuntt_bfv_encoder_owns_workspace_u64(const gpuntt_bfv_encoder* encoder);
+    int gpuntt_bfv_encoder_destroy_u32(gpuntt_bfv_encoder* encoder);
+    int gpuntt_bfv_encoder_destroy_u64(gpuntt_bfv_encoder* encoder);
+    int gpuntt_keyswitch_plan_lift_centred_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* words,
+                                               uint32_t plain_modulus, uint32_t* out, int polys, int full_base,
+                                               int to_ntt, void* stream);
+    int gpuntt_keyswitch_plan_lift_centred_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* words,
+                                               uint64_t plain_modulus, uint64_t* out, int polys, int full_base,
+                                               int to_ntt, void* stream);
+    int gpuntt_keyswitch_plan_multiply_plain_u32(const gpuntt_keyswitch_plan* plan, const uint32_t* ct,
+                                                 const uint32_t* pt, uint32_t* out, int count, int plain_count,
+                                                 void* stream);
+    int gpuntt_keyswitch_plan_multiply_plain_u64(const gpuntt_keyswitch_plan* plan, const uint64_t* ct,
+                                                 const uint64_t* pt, uint64_t* out, int count, int plain_count,
+                                                 void* stream);
 
     /* frees the library-owned scratch buffers of the drop-in entry points (synchronises the device); only when no
      * hipGraph captured from drop-in calls will be replayed again and no call is in flight */
