@@ -21,7 +21,7 @@
 #include "inner_product_internal.hpp"
 #include "launch.hpp"
 #include "relinearize_internal.hpp"
-#include "rns_host.hpp"
+#include "rns_call.hpp"
 
 namespace gpuntt
 {
@@ -56,8 +56,7 @@ namespace gpuntt
     void bfv_slot_maps(int n_power, std::uint32_t* to_position_host, std::uint32_t* to_slot_host)
     {
         host::rns_check_n_power(n_power);
-        if (to_position_host == nullptr || to_slot_host == nullptr)
-            throw std::invalid_argument("null pointer argument");
+        host::need_pointers(to_position_host, to_slot_host);
         const std::uint32_t n = 1u << n_power, half = n >> 1, mask = 2u * n - 1u;
         std::uint32_t e = 1u; // 5^c mod 2N
         for (std::uint32_t c = 0; c < half; c++)
@@ -127,12 +126,10 @@ namespace gpuntt
         void encode(const T* values, T* plain, int count, hipStream_t stream) const
         {
             check_count(count);
-            if (values == nullptr || plain == nullptr)
-                throw std::invalid_argument("null pointer argument");
+            host::need_pointers(values, plain);
             if (count == 0)
                 return;
-            if (host::rns_overlap(values, bytes(count), plain, bytes(count)))
-                throw std::invalid_argument("encode input and output overlap!");
+            host::refuse_overlap({{plain, bytes(count)}}, {{values, bytes(count)}}, "encode input and output overlap!");
             permute<T>(values, plain, to_slot(), count, n, true, mod.value, one_shoup, stream);
             inv->execute(plain, plain, count, stream);
         }
@@ -140,18 +137,13 @@ namespace gpuntt
         void decode(const T* plain, T* values, int count, void* scratch, hipStream_t stream) const
         {
             check_count(count);
-            if (plain == nullptr || values == nullptr || scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
-            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            host::need_pointers(plain, values, scratch);
+            host::need_aligned_scratch(scratch);
             if (count == 0)
                 return;
-            if (host::rns_overlap(plain, bytes(count), values, bytes(count)))
-                throw std::invalid_argument("decode input and output overlap!");
-            const std::uint64_t s_bytes = host::rns_align(bytes(count));
-            if (host::rns_overlap(scratch, s_bytes, plain, bytes(count)) ||
-                host::rns_overlap(scratch, s_bytes, values, bytes(count)))
-                throw std::invalid_argument("The scratch overlaps an operand!");
+            host::refuse_overlap({{values, bytes(count)}}, {{plain, bytes(count)}}, "decode input and output overlap!");
+            host::refuse_overlap({{scratch, host::rns_align(bytes(count))}}, {{plain, bytes(count)}, {values, bytes(count)}},
+                                 "The scratch overlaps an operand!");
             T* w = static_cast<T*>(scratch);
             fwd->execute(plain, w, count, stream);
             permute<T>(w, values, to_position(), count, n, false, mod.value, one_shoup, stream);

@@ -43,6 +43,7 @@
 #include "gpuntt/rns/bfv_multiply.cuh"
 #include "launch.hpp"
 #include "relinearize_internal.hpp"
+#include "rns_call.hpp"
 
 namespace gpuntt
 {
@@ -227,9 +228,13 @@ namespace gpuntt
         // rns_host.hpp and, for bc_padded, base_conversion_internal.hpp
         using host::bc_padded;
         using host::column_tiles;
+        using host::need_aligned_scratch;
+        using host::need_int_batch;
+        using host::need_pointers;
+        using host::refuse_overlap;
         using host::rns_align;
         using host::rns_check_n_power;
-        using host::rns_overlap;
+        using host::words_at;
 
         void bfv_check_counts(int L, int K)
         {
@@ -410,11 +415,10 @@ namespace gpuntt
             rns_check_n_power(n_power);
             if (stacks < 0)
                 throw std::invalid_argument("Invalid stacks!");
-            if (a == nullptr || b == nullptr)
-                throw std::invalid_argument("null pointer argument");
+            need_pointers(a, b);
             const std::uint64_t cols = static_cast<std::uint64_t>(stacks) << n_power;
-            if (stacks > 0 && rns_overlap(a, cols * narrow * sizeof(T), b, cols * wide * sizeof(T)))
-                throw std::invalid_argument(what);
+            if (stacks > 0)
+                refuse_overlap({{a, cols * narrow * sizeof(T)}}, {{b, cols * wide * sizeof(T)}}, what);
         }
 
         template <typename T, int V>
@@ -497,13 +501,12 @@ namespace gpuntt
                 throw std::invalid_argument("The plan was built without transform tables!");
             if (count < 0 || static_cast<unsigned long long>(count) * static_cast<unsigned>(L) > 0x7FFFFFFFull)
                 throw std::invalid_argument("Invalid count!");
-            if (message == nullptr || out == nullptr)
-                throw std::invalid_argument("null pointer argument");
+            need_pointers(message, out);
             if (count == 0)
                 return;
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
-            if (rns_overlap(message, cols * sizeof(T), out, cols * L * sizeof(T)))
-                throw std::invalid_argument("scale_message input and output overlap!");
+            refuse_overlap({{out, cols * L * sizeof(T)}}, {{message, cols * sizeof(T)}},
+                           "scale_message input and output overlap!");
             host::bfv_scale_message_launch<T>(message, out, fold(), scale_args, count, L, n, false, stream);
             host::bfv_scale_message_launch<T>(message, out, fold(), scale_args, count, L, n, true, stream);
             if (to_ntt)
@@ -524,23 +527,21 @@ namespace gpuntt
                 throw std::invalid_argument("Plaintext modulus not usable here!");
             if (stacks < 0)
                 throw std::invalid_argument("Invalid stacks!");
-            if (x == nullptr || message == nullptr)
-                throw std::invalid_argument("null pointer argument");
+            need_pointers(x, message);
             if (stacks == 0)
                 return false;
             const std::uint64_t cols = static_cast<std::uint64_t>(stacks) << n;
             const std::uint64_t x_bytes = cols * L * sizeof(T), m_bytes = cols * sizeof(T);
             const std::uint64_t n_bytes = static_cast<std::uint64_t>(stacks) * sizeof(T);
-            if (rns_overlap(x, x_bytes, message, m_bytes) ||
-                (noise_max != nullptr &&
-                 (rns_overlap(x, x_bytes, noise_max, n_bytes) || rns_overlap(message, m_bytes, noise_max, n_bytes))))
-                throw std::invalid_argument("decode input and output overlap!");
+            const char* overlap = "decode input and output overlap!";
+            refuse_overlap({{message, m_bytes}, {noise_max, n_bytes}}, {{x, x_bytes}}, overlap);
+            refuse_overlap({{message, m_bytes}}, {{noise_max, n_bytes}}, overlap);
             if (partials != nullptr && noise_max != nullptr)
             {
-                const std::uint64_t p_bytes = host::decode_partial_words(stacks, n) * sizeof(T);
-                if (reinterpret_cast<uintptr_t>(partials) % sizeof(T) != 0 || rns_overlap(partials, p_bytes, x, x_bytes) ||
-                    rns_overlap(partials, p_bytes, message, m_bytes) || rns_overlap(partials, p_bytes, noise_max, n_bytes))
-                    throw std::invalid_argument("decode input and output overlap!");
+                if (reinterpret_cast<uintptr_t>(partials) % sizeof(T) != 0)
+                    throw std::invalid_argument(overlap);
+                refuse_overlap({{partials, host::decode_partial_words(stacks, n) * sizeof(T)}},
+                               {{x, x_bytes}, {message, m_bytes}, {noise_max, n_bytes}}, overlap);
             }
             // the grid limit, with the loader the launch will choose
             try
@@ -576,8 +577,9 @@ namespace gpuntt
             return rns_align(((static_cast<size_t>(count) * L) << n) * sizeof(T));
         }
 
-        void decrypt(const T* ct, const KeySwitchPlan<T>& ks, const T* s, T* message, T* noise_max, int count,
-                     int components, bool input_ntt, void* scratch, void* ks_scratch, hipStream_t stream) const
+        // the calls that hand their q-base to a key-switching plan: both plans have their transforms and agree in the
+        // q-base, the ring and the reduction polynomial
+        void need_matching(const KeySwitchPlan<T>& ks) const
         {
             bool match = ntt_full_f && ks.has_transforms() && ks.q_count() == L && ks.n_power() == n &&
                          ks.reduction_poly() == poly;
@@ -585,11 +587,15 @@ namespace gpuntt
                 match = ks.modulus(m).value == moduli[m].value;
             if (!match)
                 throw std::invalid_argument("The key-switching plan does not match!");
-            const size_t p_bytes = decrypt_scratch(count); // checks count
-            if (scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
-            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+        }
+
+        void decrypt(const T* ct, const KeySwitchPlan<T>& ks, const T* s, T* message, T* noise_max, int count,
+                     int components, bool input_ntt, void* scratch, void* ks_scratch, hipStream_t stream) const
+        {
+            need_matching(ks);
+            (void) decrypt_scratch(count); // checks count
+            need_pointers(scratch);
+            need_aligned_scratch(scratch);
             T* x = static_cast<T*>(scratch);
             const bool work = decode_check(x, message, noise_max, count);
             const size_t ks_bytes = ks.phase_scratch_bytes(count, components, input_ntt); // checks components
@@ -599,19 +605,41 @@ namespace gpuntt
                 const std::uint64_t ct_bytes = cols * L * components * sizeof(T), m_bytes = cols * sizeof(T);
                 const std::uint64_t s_bytes = (static_cast<std::uint64_t>(L) << n) * sizeof(T);
                 const std::uint64_t n_bytes = static_cast<std::uint64_t>(count) * sizeof(T);
-                for (const auto& o : {std::pair<const void*, std::uint64_t>{message, m_bytes},
-                                      {noise_max, noise_max != nullptr ? n_bytes : 0}})
-                    if (o.first != nullptr &&
-                        (rns_overlap(o.first, o.second, ct, ct_bytes) || rns_overlap(o.first, o.second, s, s_bytes) ||
-                         (ks_scratch != nullptr && ks_bytes != 0 && rns_overlap(o.first, o.second, ks_scratch, ks_bytes))))
-                        throw std::invalid_argument("out or the scratch overlaps an operand!");
+                refuse_overlap({{message, m_bytes}, {noise_max, n_bytes}},
+                               {{ct, ct_bytes}, {s, s_bytes}, {ks_bytes != 0 ? ks_scratch : nullptr, ks_bytes}},
+                               "out or the scratch overlaps an operand!");
             }
-            (void) p_bytes;
             // the phase refuses the rest before its first launch: null ct or s, its own scratch, the overlaps of the
             // coefficient region with ct, s and its scratch
             ks.phase(ct, s, x, count, components, input_ntt, false, ks_scratch, stream);
             if (work)
                 decode_run(x, message, noise_max, count, stream);
+        }
+
+        // The tail product_check and sum_check share: the scratch (of `total` bytes) and out (`comps` components) against
+        // the U operands at ops, and the limits of the calls -- `widest` count M is the widest batch of a transform.
+        // Returns false when count is 0 and nothing is to be launched
+        bool operands_check(const T* const* ops, int U, const T* out, int comps, int count, const void* scratch,
+                            size_t total, unsigned long long widest) const
+        {
+            need_aligned_scratch(scratch);
+            if (count == 0)
+                return false;
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T), out_bytes = cols * L * comps * sizeof(T);
+            for (int u = 0; u < U; u++)
+            {
+                const char* operand = "out or the scratch overlaps an operand!";
+                refuse_overlap({{scratch, total}}, {{ops[u], ct_bytes}}, operand);
+                // out may be exactly one operand: the last read of every operand (bfv_extend, or the INTT before it)
+                // precedes bfv_scale_round's first write on the stream.  Any other overlap is refused
+                refuse_overlap({{out, out_bytes}}, {{ops[u], ct_bytes, true}}, operand);
+            }
+            refuse_overlap({{out, out_bytes}}, {{scratch, total}}, "The scratch overlaps out!");
+            // every limit before the first launch: the batches of the transforms are ints, the grids as the launches check
+            need_int_batch(widest * static_cast<unsigned>(count) * static_cast<unsigned>(M), "Invalid count!");
+            (void) column_tiles((3ull * static_cast<unsigned>(count)) << n, kern::BC_NT, "Invalid stacks!");
+            return true;
         }
 
         // What multiply and multiply_relinearize share up to the first launch: every refusal of multiply, with `comps`
@@ -621,31 +649,13 @@ namespace gpuntt
             if (!ntt_full_f)
                 throw std::invalid_argument("The plan was built without transform tables!");
             const BfvScratch s = bfv_scratch<T>(L, M, n, count); // checks count
-            if (x == nullptr || y == nullptr || out == nullptr || scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
-            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
-            if (count == 0)
+            need_pointers(x, y, out, scratch);
+            const T* const ops[] = {x, y};
+            if (!operands_check(ops, 2, out, comps, count, scratch, s.total, 4))
                 return false;
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
-            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T), out_bytes = cols * L * comps * sizeof(T);
-            for (const T* op : {x, y})
-            {
-                if (rns_overlap(scratch, s.total, op, ct_bytes))
-                    throw std::invalid_argument("out or the scratch overlaps an operand!");
-                // out may be exactly x or exactly y: the last read of both (bfv_extend, or the INTT before it) precedes
-                // bfv_scale_round's first write on the stream.  Any other overlap is refused
-                if (rns_overlap(out, out_bytes, op, ct_bytes) && op != out)
-                    throw std::invalid_argument("out or the scratch overlaps an operand!");
-            }
-            if (rns_overlap(out, out_bytes, scratch, s.total))
-                throw std::invalid_argument("The scratch overlaps out!");
-            // every limit before the first launch: the batches of the transforms are ints, the grids as the launches check
-            if (4ull * static_cast<unsigned>(count) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
-                throw std::invalid_argument("Invalid count!");
-            (void) column_tiles((3ull * static_cast<unsigned>(count)) << n, kern::BC_NT, "Invalid stacks!");
             const bool square = x == y;
-            T* e = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.e);
+            T* e = words_at<T>(scratch, s.e);
             bfv_tensor_launch<T>(e, square ? e : e + cols * M * 2, e, fold(), count, M, n, false, nullptr);
             return true;
         }
@@ -657,8 +667,8 @@ namespace gpuntt
             const BfvScratch s = bfv_scratch<T>(L, M, n, count);
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
             const bool square = x == y;
-            T* e = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.e);
-            T* coeff = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.coeff);
+            T* e = words_at<T>(scratch, s.e);
+            T* coeff = words_at<T>(scratch, s.coeff);
             T* xe = e;
             T* ye = square ? e : e + cols * M * 2;
             auto bring = [&](const T* op, T* full) { // steps 1 and 2 for one operand
@@ -686,49 +696,64 @@ namespace gpuntt
                 ntt_q_f->execute(out, out, 3 * count * L, stream);
         }
 
-        void multiply_relinearize(const T* x, const T* y, const KeySwitchPlan<T>& ks, const T* key, T* out, int count,
-                                  bool input_ntt, bool output_ntt, void* scratch, void* ks_scratch,
-                                  hipStream_t stream) const
+        // What multiply_relinearize and multiply_relinearize_sum refuse before the product's own checks; returns the
+        // bytes of the key-switching plan's scratch
+        size_t relin_head(const KeySwitchPlan<T>& ks, const T* key, int count, const void* ks_scratch) const
         {
-            bool match = ntt_full_f && ks.has_transforms() && ks.q_count() == L && ks.n_power() == n &&
-                         ks.reduction_poly() == poly;
-            for (int m = 0; match && m < L; m++)
-                match = ks.modulus(m).value == moduli[m].value;
-            if (!match)
-                throw std::invalid_argument("The key-switching plan does not match!");
-            if (key == nullptr || ks_scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
+            need_matching(ks);
+            need_pointers(key, ks_scratch);
             const size_t ks_bytes = ks.scratch_bytes(count, 2); // checks count
-            if (reinterpret_cast<uintptr_t>(ks_scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
-            if (!product_check(x, y, out, 2, count, scratch))
-                return;
-            const BfvScratch s = bfv_scratch<T>(L, M, n, count);
+            need_aligned_scratch(ks_scratch);
+            return ks_bytes;
+        }
+
+        // ... and after them: the key and the key-switching plan's scratch against the U operands at ops, out and the
+        // scratch, and the limits of relinearize's coefficient path, before the first launch: the batch of its widest
+        // transform is an int, and its grids (mod_up, the inner product, mod_down_add) launch at most
+        // 2 * count * max(N, 256) work-items
+        void relin_check(const T* const* ops, int U, const KeySwitchPlan<T>& ks, const T* key, const T* out, int count,
+                         const void* scratch, size_t total, const void* ks_scratch, size_t ks_bytes) const
+        {
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
             const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T);
             const std::uint64_t key_bytes =
                 ((static_cast<std::uint64_t>(ks.digits()) * 2 * ks.key_mod_count()) << n) * sizeof(T);
-            if (rns_overlap(ks_scratch, ks_bytes, x, ct_bytes) || rns_overlap(ks_scratch, ks_bytes, y, ct_bytes) ||
-                rns_overlap(ks_scratch, ks_bytes, key, key_bytes) || rns_overlap(scratch, s.total, key, key_bytes) ||
-                rns_overlap(out, ct_bytes, key, key_bytes) || rns_overlap(x, ct_bytes, key, key_bytes) ||
-                rns_overlap(y, ct_bytes, key, key_bytes))
-                throw std::invalid_argument("out or the scratch overlaps an operand!");
-            if (rns_overlap(ks_scratch, ks_bytes, out, ct_bytes) || rns_overlap(ks_scratch, ks_bytes, scratch, s.total))
-                throw std::invalid_argument("The scratch overlaps out!");
-            // the limits of relinearize's coefficient path, before the first launch: the batch of its widest transform is
-            // an int, and its grids (mod_up, the inner product, mod_down_add) launch at most 2 * count * max(N, 256)
-            // work-items
+            const char* operand = "out or the scratch overlaps an operand!";
+            refuse_overlap({{ks_scratch, ks_bytes}, {scratch, total}, {out, ct_bytes}}, {{key, key_bytes}}, operand);
+            for (int u = 0; u < U; u++)
+                refuse_overlap({{ks_scratch, ks_bytes}, {key, key_bytes}}, {{ops[u], ct_bytes}}, operand);
+            refuse_overlap({{ks_scratch, ks_bytes}}, {{out, ct_bytes}, {scratch, total}}, "The scratch overlaps out!");
             const unsigned long long ks_m = static_cast<unsigned>(L + ks.p_count());
-            if (static_cast<unsigned long long>(ks.digits()) * static_cast<unsigned>(count) * ks_m > 0x7FFFFFFFull ||
-                2ull * static_cast<unsigned>(count) * ((1ull << n) > 256ull ? (1ull << n) : 256ull) > 0xFFFFFFFFull)
+            need_int_batch(static_cast<unsigned long long>(ks.digits()) * static_cast<unsigned>(count) * ks_m,
+                           "Invalid count!");
+            if (2ull * static_cast<unsigned>(count) * ((1ull << n) > 256ull ? (1ull << n) : 256ull) > 0xFFFFFFFFull)
                 throw std::invalid_argument("Invalid count!");
-            const T* e = product(x, y, count, input_ntt, scratch, stream);
-            // the low components straight into out, the top one into the coeff region: dead since bfv_extend, and
-            // T[count][L][N] fits its T[2][count][L][N]
-            T* top = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.coeff);
+        }
+
+        // the three tensor components at e, divided and rounded: the low ones straight into out, the top one into the
+        // coeff region of the scratch (dead since bfv_extend, and T[count][L][N] fits its T[2][count][L][N]); then the
+        // key switch of the top one
+        void relin_tail(const T* e, const KeySwitchPlan<T>& ks, const T* key, T* out, int count, bool output_ntt, T* top,
+                        void* ks_scratch, hipStream_t stream) const
+        {
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
             scale_round(e, out, 2 * count, stream);
             scale_round(e + 2 * cols * M, top, count, stream);
             ks.relinearize(out, top, key, out, count, false, output_ntt, ks_scratch, stream);
+        }
+
+        void multiply_relinearize(const T* x, const T* y, const KeySwitchPlan<T>& ks, const T* key, T* out, int count,
+                                  bool input_ntt, bool output_ntt, void* scratch, void* ks_scratch,
+                                  hipStream_t stream) const
+        {
+            const size_t ks_bytes = relin_head(ks, key, count, ks_scratch);
+            if (!product_check(x, y, out, 2, count, scratch))
+                return;
+            const BfvScratch s = bfv_scratch<T>(L, M, n, count);
+            const T* const ops[] = {x, y};
+            relin_check(ops, 2, ks, key, out, count, scratch, s.total, ks_scratch, ks_bytes);
+            const T* e = product(x, y, count, input_ntt, scratch, stream);
+            relin_tail(e, ks, key, out, count, output_ntt, words_at<T>(scratch, s.coeff), ks_scratch, stream);
         }
 
         // one multiply_sum call as the host sees it: the U distinct operand pointers in order of first appearance (x_0
@@ -751,14 +776,12 @@ namespace gpuntt
                 throw std::invalid_argument("Invalid terms!");
             if (terms > max_terms)
                 throw std::invalid_argument("Auxiliary base too small for these terms!");
-            if (xs == nullptr || ys == nullptr || out == nullptr || scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
+            need_pointers(xs, ys, out, scratch);
             call.U = 0;
             call.args = kern::BfvSumArgs{};
             call.args.terms = terms;
             auto slot_of = [&](const T* p) {
-                if (p == nullptr)
-                    throw std::invalid_argument("null pointer argument");
+                need_pointers(p);
                 for (int s = 0; s < call.U; s++)
                     if (call.op[s] == p)
                         return static_cast<unsigned char>(s);
@@ -771,31 +794,10 @@ namespace gpuntt
                 call.args.y_slot[i] = slot_of(ys[i]);
             }
             const BfvScratch s = bfv_sum_scratch<T>(L, M, n, count, call.U); // checks count
-            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
-            if (count == 0)
+            // the widest transform batch is 2 U count M (3 count M for U = 1)
+            if (!operands_check(call.op, call.U, out, comps, count, scratch, s.total, std::max(2 * call.U, 3)))
                 return false;
-            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
-            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T), out_bytes = cols * L * comps * sizeof(T);
-            for (int u = 0; u < call.U; u++)
-            {
-                const T* op = call.op[u];
-                if (rns_overlap(scratch, s.total, op, ct_bytes))
-                    throw std::invalid_argument("out or the scratch overlaps an operand!");
-                // out may be exactly one operand: the last read of every operand (bfv_extend, or the INTT before it)
-                // precedes bfv_scale_round's first write on the stream.  Any other overlap is refused
-                if (rns_overlap(out, out_bytes, op, ct_bytes) && op != out)
-                    throw std::invalid_argument("out or the scratch overlaps an operand!");
-            }
-            if (rns_overlap(out, out_bytes, scratch, s.total))
-                throw std::invalid_argument("The scratch overlaps out!");
-            // every limit before the first launch: the widest transform batch, 2 U count M (3 count M for U = 1), is an
-            // int; the grids as the launches check
-            const unsigned long long widest = static_cast<unsigned>(std::max(2 * call.U, 3));
-            if (widest * static_cast<unsigned>(count) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
-                throw std::invalid_argument("Invalid count!");
-            (void) column_tiles((3ull * static_cast<unsigned>(count)) << n, kern::BC_NT, "Invalid stacks!");
-            T* e = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.e);
+            T* e = words_at<T>(scratch, s.e);
             host::bfv_tensor_sum_launch<T>(e, fold(), call.args, count, M, n, false, nullptr);
             return true;
         }
@@ -806,8 +808,8 @@ namespace gpuntt
         {
             const BfvScratch s = bfv_sum_scratch<T>(L, M, n, count, call.U);
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
-            T* e = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.e);
-            T* coeff = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.coeff);
+            T* e = words_at<T>(scratch, s.e);
+            T* coeff = words_at<T>(scratch, s.coeff);
             for (int u = 0; u < call.U; u++) // the coefficient region is reused in stream order
             {
                 if (input_ntt)
@@ -836,45 +838,14 @@ namespace gpuntt
                                       const T* key, T* out, int count, bool input_ntt, bool output_ntt, void* scratch,
                                       void* ks_scratch, hipStream_t stream) const
         {
-            bool match = ntt_full_f && ks.has_transforms() && ks.q_count() == L && ks.n_power() == n &&
-                         ks.reduction_poly() == poly;
-            for (int m = 0; match && m < L; m++)
-                match = ks.modulus(m).value == moduli[m].value;
-            if (!match)
-                throw std::invalid_argument("The key-switching plan does not match!");
-            if (key == nullptr || ks_scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
-            const size_t ks_bytes = ks.scratch_bytes(count, 2); // checks count
-            if (reinterpret_cast<uintptr_t>(ks_scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            const size_t ks_bytes = relin_head(ks, key, count, ks_scratch);
             SumCall call;
             if (!sum_check(xs, ys, terms, out, 2, count, scratch, call))
                 return;
             const BfvScratch s = bfv_sum_scratch<T>(L, M, n, count, call.U);
-            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
-            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T);
-            const std::uint64_t key_bytes =
-                ((static_cast<std::uint64_t>(ks.digits()) * 2 * ks.key_mod_count()) << n) * sizeof(T);
-            bool bad = rns_overlap(ks_scratch, ks_bytes, key, key_bytes) || rns_overlap(scratch, s.total, key, key_bytes) ||
-                       rns_overlap(out, ct_bytes, key, key_bytes);
-            for (int u = 0; u < call.U; u++)
-                bad = bad || rns_overlap(ks_scratch, ks_bytes, call.op[u], ct_bytes) ||
-                      rns_overlap(call.op[u], ct_bytes, key, key_bytes);
-            if (bad)
-                throw std::invalid_argument("out or the scratch overlaps an operand!");
-            if (rns_overlap(ks_scratch, ks_bytes, out, ct_bytes) || rns_overlap(ks_scratch, ks_bytes, scratch, s.total))
-                throw std::invalid_argument("The scratch overlaps out!");
-            // the limits of relinearize's coefficient path, as multiply_relinearize checks them
-            const unsigned long long ks_m = static_cast<unsigned>(L + ks.p_count());
-            if (static_cast<unsigned long long>(ks.digits()) * static_cast<unsigned>(count) * ks_m > 0x7FFFFFFFull ||
-                2ull * static_cast<unsigned>(count) * ((1ull << n) > 256ull ? (1ull << n) : 256ull) > 0xFFFFFFFFull)
-                throw std::invalid_argument("Invalid count!");
+            relin_check(call.op, call.U, ks, key, out, count, scratch, s.total, ks_scratch, ks_bytes);
             const T* e = sum_product(call, count, input_ntt, scratch, stream);
-            // as multiply_relinearize: the low components straight into out, the top one into the coeff region
-            T* top = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.coeff);
-            scale_round(e, out, 2 * count, stream);
-            scale_round(e + 2 * cols * M, top, count, stream);
-            ks.relinearize(out, top, key, out, count, false, output_ntt, ks_scratch, stream);
+            relin_tail(e, ks, key, out, count, output_ntt, words_at<T>(scratch, s.coeff), ks_scratch, stream);
         }
     };
 

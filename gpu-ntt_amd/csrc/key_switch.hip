@@ -79,6 +79,7 @@
 #include "relinearize_internal.hpp"
 #include "relinearize_sum_internal.hpp"
 #include "rescale_internal.hpp"
+#include "rns_call.hpp"
 
 namespace gpuntt
 {
@@ -211,12 +212,17 @@ namespace gpuntt
     {
         using U128 = unsigned __int128;
 
-        // rns_host.hpp and, for bc_padded, base_conversion_internal.hpp
+        // rns_host.hpp, rns_call.hpp and, for bc_padded, base_conversion_internal.hpp
         using host::bc_padded;
         using host::column_tiles;
+        using host::need_aligned_scratch;
+        using host::need_int_batch;
+        using host::need_pointers;
+        using host::refuse_overlap;
         using host::rns_align;
         using host::rns_check_n_power;
         using host::rns_overlap;
+        using host::words_at;
 
         // everything the host derives for one (q-base, special base, alpha), in exact integers
         struct KsHost
@@ -544,15 +550,13 @@ namespace gpuntt
         void mod_down_add(const T* x, const T* addend, T* out, int stacks, hipStream_t stream) const
         {
             ks_check_mod_down<T>(L, M, x, out, n, stacks);
-            if (addend == nullptr)
-                throw std::invalid_argument("null pointer argument");
+            need_pointers(addend);
             if (stacks == 0)
                 return;
             const std::uint64_t cols = static_cast<std::uint64_t>(stacks) << n;
             const std::uint64_t low_bytes = cols * L * sizeof(T);
-            if (rns_overlap(addend, low_bytes, x, cols * M * sizeof(T)) ||
-                (addend != out && rns_overlap(addend, low_bytes, out, low_bytes)))
-                throw std::invalid_argument("The addend overlaps an operand!");
+            refuse_overlap({{addend, low_bytes}}, {{x, cols * M * sizeof(T)}, {out, low_bytes, true}},
+                           "The addend overlaps an operand!");
             divide_in_stack(x, out, stacks, M, K, L, lay.down, down_off, stream, addend);
         }
 
@@ -594,20 +598,15 @@ namespace gpuntt
                 return;
             }
             const size_t scratch_bytes = rescale_scratch(stacks);
-            if (scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
-            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            need_pointers(scratch);
+            need_aligned_scratch(scratch);
             if (stacks == 0)
                 return;
             const std::uint64_t cols = static_cast<std::uint64_t>(stacks) << n;
-            if (rns_overlap(scratch, scratch_bytes, x, cols * L * sizeof(T)))
-                throw std::invalid_argument("The scratch overlaps an operand!");
-            if (rns_overlap(scratch, scratch_bytes, out, cols * Lk * sizeof(T)))
-                throw std::invalid_argument("The scratch overlaps out!");
+            refuse_overlap({{scratch, scratch_bytes}}, {{x, cols * L * sizeof(T)}}, "The scratch overlaps an operand!");
+            refuse_overlap({{scratch, scratch_bytes}}, {{out, cols * Lk * sizeof(T)}}, "The scratch overlaps out!");
             // every limit before the first launch: the batches of the transforms are ints, the grids as their launches check
-            if (static_cast<unsigned long long>(stacks) * static_cast<unsigned>(L) > 0x7FFFFFFFull)
-                throw std::invalid_argument("Invalid stacks!");
+            need_int_batch(static_cast<unsigned long long>(stacks) * static_cast<unsigned>(L), "Invalid stacks!");
             const unsigned long long tiles = column_tiles(cols, kern::BC_NT, "Invalid stacks!");
             T* dropped = static_cast<T*>(scratch);
             const T* image = reinterpret_cast<const T*>(ws + lay.rs);
@@ -638,21 +637,21 @@ namespace gpuntt
         {
             need_transforms();
             const KsScratch s = ks_scratch<T>(L, M, D, n, count, 1);
-            if (c_in == nullptr || a == nullptr || (input_ntt && scratch == nullptr))
-                throw std::invalid_argument("null pointer argument");
+            need_pointers(c_in, a);
+            if (input_ntt)
+                need_pointers(scratch);
             if (count == 0)
                 return;
             const T* coeff = c_in;
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
             const std::uint64_t c_bytes = cols * L * sizeof(T), a_bytes = cols * M * D * sizeof(T);
-            if (rns_overlap(c_in, c_bytes, a, a_bytes)) // every refusal comes before the first launch
-                throw std::invalid_argument("ModUp input and output overlap!");
+            // every refusal comes before the first launch
+            refuse_overlap({{a, a_bytes}}, {{c_in, c_bytes}}, "ModUp input and output overlap!");
             if (input_ntt)
             {
-                T* tmp = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.c_coeff);
-                if (rns_overlap(tmp, s.inner_out - s.c_coeff, a, a_bytes) ||
-                    rns_overlap(tmp, s.inner_out - s.c_coeff, c_in, c_bytes))
-                    throw std::invalid_argument("The scratch overlaps an operand!");
+                T* tmp = words_at<T>(scratch, s.c_coeff);
+                refuse_overlap({{tmp, s.inner_out - s.c_coeff}}, {{a, a_bytes}, {c_in, c_bytes}},
+                               "The scratch overlaps an operand!");
                 ntt_q_i->execute(c_in, tmp, count * L, stream);
                 coeff = tmp;
             }
@@ -665,14 +664,12 @@ namespace gpuntt
         {
             need_transforms();
             const KsScratch s = ks_scratch<T>(L, M, D, n, count, C);
-            if (a == nullptr || key == nullptr || out == nullptr || scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
+            need_pointers(a, key, out, scratch);
             if (count == 0)
                 return;
-            T* acc = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.inner_out);
-            const std::uint64_t acc_bytes = (static_cast<std::uint64_t>(count) << n) * M * C * sizeof(T);
-            if (rns_overlap(acc, acc_bytes, out, (static_cast<std::uint64_t>(count) << n) * L * C * sizeof(T)))
-                throw std::invalid_argument("The scratch overlaps out!");
+            T* acc = words_at<T>(scratch, s.inner_out);
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            refuse_overlap({{acc, cols * M * C * sizeof(T)}}, {{out, cols * L * C * sizeof(T)}}, "The scratch overlaps out!");
             // a or key overlapping the accumulators in the scratch: refused by the inner product's own check of its
             // output against its inputs, before its launch -- the first of this call
             inner->multiply_accumulate(a, key, acc, n, D, C, count, false, KM, limbs.data(), stream);
@@ -692,6 +689,27 @@ namespace gpuntt
                 (rescale ? ntt_keep_f : ntt_q_f)->execute(out, out, stacks * (rescale ? Lk : L), stream);
         }
 
+        // a Galois element reduced as GPU_Automorphism_NTT reduces it (odd, or refused) and its inverse
+        std::uint32_t galois_checked(std::uint32_t element, std::uint32_t& inverse) const
+        {
+            const std::uint32_t mask = negacyclic ? (2u << n) - 1u : (1u << n) - 1u;
+            const std::uint32_t k = element & mask;
+            if ((k & 1u) == 0u)
+                throw std::invalid_argument("Invalid Galois element (must be odd)!");
+            inverse = galois_inverse(k) & mask;
+            return k;
+        }
+
+        // what the kernel arguments of the pipeline calls carry of the base: the key limb of every modulus, P mod q_j
+        // and its Shoup companion
+        void fill_base(unsigned char* limb, T* p_mod_q_out, T* p_mod_q_shoup_out) const
+        {
+            for (int m = 0; m < M; m++)
+                limb[m] = static_cast<unsigned char>(limbs[m]);
+            std::copy(p_mod_q.begin(), p_mod_q.end(), p_mod_q_out);
+            std::copy(p_mod_q_shoup.begin(), p_mod_q_shoup.end(), p_mod_q_shoup_out);
+        }
+
         // What rotate_hoisted (groups = G, no weights) and rotate_hoisted_sum (groups = 1) share up to the launch: every
         // refusal of the call, in one order, and the kernel arguments.  out: T[groups][2][count][L][N], the scratch:
         // T[groups][2][count][M][N]; weights: G device pointers (each may be null) or null.  Returns the stacks the tail
@@ -706,48 +724,31 @@ namespace gpuntt
             const size_t acc_bytes = ks_hoisted_scratch<T>(M, n, count, groups); // checks count (and G = groups)
             if (G < 1 || G > GALOIS_MAX_COUNT)
                 throw std::invalid_argument("Invalid galois_count!");
-            if (a == nullptr || keys == nullptr || elts == nullptr || out == nullptr || scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
-            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            need_pointers(a, keys, elts, out, scratch);
+            need_aligned_scratch(scratch);
             args.count = G;
-            const std::uint32_t mask = negacyclic ? (2u << n) - 1u : (1u << n) - 1u; // as GPU_Automorphism_NTT reduces
             for (int g = 0; g < G; g++)
             {
-                const std::uint32_t k = elts[g] & mask;
-                if ((k & 1u) == 0u)
-                    throw std::invalid_argument("Invalid Galois element (must be odd)!");
-                if (keys[g] == nullptr)
-                    throw std::invalid_argument("null pointer argument");
-                args.elt[g] = k, args.inv[g] = galois_inverse(k) & mask, args.key[g] = keys[g];
+                args.elt[g] = galois_checked(elts[g], args.inv[g]);
+                need_pointers(keys[g]);
+                args.key[g] = keys[g];
             }
-            for (int m = 0; m < M; m++)
-                args.limb[m] = static_cast<unsigned char>(limbs[m]);
-            for (int j = 0; j < L; j++)
-                args.p_mod_q[j] = p_mod_q[j], args.p_mod_q_shoup[j] = p_mod_q_shoup[j];
+            fill_base(args.limb, args.p_mod_q, args.p_mod_q_shoup);
             if (count == 0)
                 return 0;
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
-            const std::uint64_t a_bytes = cols * M * D * sizeof(T), c0_bytes = cols * L * sizeof(T);
             const std::uint64_t out_bytes = cols * (rescale ? Lk : L) * 2 * groups * sizeof(T);
             const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
             const std::uint64_t weight_bytes = (static_cast<std::uint64_t>(M) << n) * sizeof(T);
-            for (const auto& w : {std::pair<const void*, std::uint64_t>{out, out_bytes}, {scratch, acc_bytes}})
-            {
-                bool hit = rns_overlap(w.first, w.second, a, a_bytes) ||
-                           (c0 != nullptr && rns_overlap(w.first, w.second, c0, c0_bytes));
-                for (int g = 0; g < G; g++)
-                    hit = hit || rns_overlap(w.first, w.second, keys[g], key_bytes) ||
-                          (weights != nullptr && weights[g] != nullptr &&
-                           rns_overlap(w.first, w.second, weights[g], weight_bytes));
-                if (hit)
-                    throw std::invalid_argument("out or the scratch overlaps an operand!");
-            }
-            if (rns_overlap(out, out_bytes, scratch, acc_bytes))
-                throw std::invalid_argument("The scratch overlaps out!");
+            const char* operand = "out or the scratch overlaps an operand!";
+            const std::initializer_list<host::RnsRange> written = {{out, out_bytes}, {scratch, acc_bytes}};
+            refuse_overlap(written, {{a, cols * M * D * sizeof(T)}, {c0, cols * L * sizeof(T)}}, operand);
+            for (int g = 0; g < G; g++)
+                refuse_overlap(written, {{keys[g], key_bytes}, {weights != nullptr ? weights[g] : nullptr, weight_bytes}},
+                               operand);
+            refuse_overlap({{out, out_bytes}}, {{scratch, acc_bytes}}, "The scratch overlaps out!");
             const unsigned long long stacks = 2ull * static_cast<unsigned>(groups) * static_cast<unsigned>(count);
-            if (stacks * static_cast<unsigned>(M) > 0x7FFFFFFFull) // the batch of the transforms is an int
-                throw std::invalid_argument("Invalid count!");
+            need_int_batch(stacks * static_cast<unsigned>(M), "Invalid count!"); // the batch of the transforms
             // mod_down's own grid limit, checked before the first launch
             (void) column_tiles(stacks << n, kern::BC_NT, "Invalid count!");
             return static_cast<int>(stacks);
@@ -789,18 +790,16 @@ namespace gpuntt
         int bsgs_axis(const T* const* keys, const std::uint32_t* elts, int steps, kern::HoistArgs<T>& args,
                       int* order) const
         {
-            const std::uint32_t mask = negacyclic ? (2u << n) - 1u : (1u << n) - 1u; // as GPU_Automorphism_NTT reduces
             int keyed = 0;
             for (int i = 0; i < steps; i++)
             {
-                const std::uint32_t k = elts[i] & mask;
-                if ((k & 1u) == 0u)
-                    throw std::invalid_argument("Invalid Galois element (must be odd)!");
+                std::uint32_t inverse;
+                const std::uint32_t k = galois_checked(elts[i], inverse);
                 if (keys[i] == nullptr && k != 1u)
                     throw std::invalid_argument("A null key is accepted only where the element is 1!");
                 if (keys[i] != nullptr)
                 {
-                    args.elt[keyed] = k, args.inv[keyed] = galois_inverse(k) & mask, args.key[keyed] = keys[i];
+                    args.elt[keyed] = k, args.inv[keyed] = inverse, args.key[keyed] = keys[i];
                     order[keyed++] = i;
                 }
             }
@@ -808,10 +807,7 @@ namespace gpuntt
             for (int i = 0, at = keyed; i < steps; i++)
                 if (keys[i] == nullptr)
                     order[at++] = i;
-            for (int m = 0; m < M; m++)
-                args.limb[m] = static_cast<unsigned char>(limbs[m]);
-            for (int j = 0; j < L; j++)
-                args.p_mod_q[j] = p_mod_q[j], args.p_mod_q_shoup[j] = p_mod_q_shoup[j];
+            fill_base(args.limb, args.p_mod_q, args.p_mod_q_shoup);
             return keyed;
         }
 
@@ -824,17 +820,14 @@ namespace gpuntt
             if (rescale)
                 need_rescale();
             const KsBsgsScratch s = ks_bsgs_scratch<T>(L, M, D, n, count, n1, n2); // checks count, n1 and n2
-            if (a == nullptr || bkeys == nullptr || belts == nullptr || gkeys == nullptr || gelts == nullptr ||
-                weights == nullptr || out == nullptr || scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
-            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            need_pointers(a, bkeys, belts, gkeys, gelts, weights, out, scratch);
+            need_aligned_scratch(scratch);
             kern::HoistArgs<T> bargs{}, gargs{};
             int border[KEYSWITCH_MAX_STEPS], gorder[KEYSWITCH_MAX_STEPS];
             const int n1k = bsgs_axis(bkeys, belts, n1, bargs, border);
             const int n2k = bsgs_axis(gkeys, gelts, n2, gargs, gorder);
-            if (n1k < n1 && c1 == nullptr)
-                throw std::invalid_argument("null pointer argument"); // a baby step without a key reads c1
+            if (n1k < n1)
+                need_pointers(c1); // a baby step without a key reads c1
             kern::BsgsWeights<T> wa{};
             wa.n1 = n1, wa.n2 = n2;
             for (int g = 0; g < n2; g++)
@@ -851,40 +844,32 @@ namespace gpuntt
             if (count == 0)
                 return;
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
-            const std::uint64_t a_bytes = cols * M * D * sizeof(T), c_bytes = cols * L * sizeof(T);
+            const std::uint64_t c_bytes = cols * L * sizeof(T);
             const std::uint64_t out_bytes = cols * (rescale ? Lk : L) * 2 * sizeof(T);
             const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
             const std::uint64_t weight_bytes = (static_cast<std::uint64_t>(M) << n) * sizeof(T);
-            for (const auto& w : {std::pair<const void*, std::uint64_t>{out, out_bytes}, {scratch, s.total}})
-            {
-                bool hit = rns_overlap(w.first, w.second, a, a_bytes) ||
-                           (c0 != nullptr && rns_overlap(w.first, w.second, c0, c_bytes)) ||
-                           (c1 != nullptr && rns_overlap(w.first, w.second, c1, c_bytes));
-                for (int i = 0; i < n1k; i++)
-                    hit = hit || rns_overlap(w.first, w.second, bargs.key[i], key_bytes);
-                for (int i = 0; i < n2k; i++)
-                    hit = hit || rns_overlap(w.first, w.second, gargs.key[i], key_bytes);
-                for (int i = 0; i < n1 * n2; i++)
-                    hit = hit || (wa.w[i] != nullptr && rns_overlap(w.first, w.second, wa.w[i], weight_bytes));
-                if (hit)
-                    throw std::invalid_argument("out or the scratch overlaps an operand!");
-            }
-            if (rns_overlap(out, out_bytes, scratch, s.total))
-                throw std::invalid_argument("The scratch overlaps out!");
+            const char* operand = "out or the scratch overlaps an operand!";
+            const std::initializer_list<host::RnsRange> written = {{out, out_bytes}, {scratch, s.total}};
+            refuse_overlap(written, {{a, cols * M * D * sizeof(T)}, {c0, c_bytes}, {c1, c_bytes}}, operand);
+            for (int i = 0; i < n1k; i++)
+                refuse_overlap(written, {{bargs.key[i], key_bytes}}, operand);
+            for (int i = 0; i < n2k; i++)
+                refuse_overlap(written, {{gargs.key[i], key_bytes}}, operand);
+            for (int i = 0; i < n1 * n2; i++)
+                refuse_overlap(written, {{wa.w[i], weight_bytes}}, operand);
+            refuse_overlap({{out, out_bytes}}, {{scratch, s.total}}, "The scratch overlaps out!");
             // every limit before the first launch, at n2 keyed giant steps whatever their number is: the batches of the
             // transforms are ints; the grids of mod_up, mod_down and the five kernels of hoisted_rotation.hip launch at
             // most stacks * max(N, 256) work-items
             const unsigned long long stacks = static_cast<unsigned long long>(n2 > 2 ? n2 : 2) * static_cast<unsigned>(count);
-            if (stacks * static_cast<unsigned>(D) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
-                throw std::invalid_argument("Invalid count!");
+            need_int_batch(stacks * static_cast<unsigned>(D) * static_cast<unsigned>(M), "Invalid count!");
             if (stacks * ((1ull << n) > 256ull ? (1ull << n) : 256ull) > 0xFFFFFFFFull)
                 throw std::invalid_argument("Invalid count!");
 
-            char* base = static_cast<char*>(scratch);
-            T* u = reinterpret_cast<T*>(base + s.u);
-            T* v = reinterpret_cast<T*>(base + s.v);
-            T* t = reinterpret_cast<T*>(base + s.t);
-            T* a2 = reinterpret_cast<T*>(base + s.a2);
+            T* u = words_at<T>(scratch, s.u);
+            T* v = words_at<T>(scratch, s.v);
+            T* t = words_at<T>(scratch, s.t);
+            T* a2 = words_at<T>(scratch, s.a2);
             T* acc = u; // u is dead once v is formed
             const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
             // 1. the baby steps: u[b] for the keyed b < n1k, then the others
@@ -910,67 +895,26 @@ namespace gpuntt
             finish(acc, out, 2 * count, output_ntt, rescale, stream);
         }
 
-        // x, y: T[2][count][L][N]; out: T[2][count][L][N], rescale: T[2][count][Lk][N]; key: T[D_key][2][KM][N]; the
-        // scratch: ks_scratch(count, 2)
-        void multiply_relinearize(const T* x, const T* y, const T* key, T* out, int count, bool output_ntt, bool rescale,
-                                  void* scratch, hipStream_t stream) const
+        // the limits of the relinearizing calls, before their first launch: the batches of the transforms are ints; the
+        // grids of mod_up and mod_down: as their own launches check
+        void relin_limits(std::uint64_t cols, int count) const
         {
-            need_transforms();
-            if (rescale)
-                need_rescale();
-            const KsScratch s = ks_scratch<T>(L, M, D, n, count, 2); // checks count
-            if (x == nullptr || y == nullptr || key == nullptr || out == nullptr || scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
-            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
-            if (count == 0)
-                return;
-            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
-            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T);
-            const std::uint64_t out_bytes = cols * (rescale ? Lk : L) * 2 * sizeof(T);
-            const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
-            for (const auto& op : {std::pair<const void*, std::uint64_t>{x, ct_bytes}, {y, ct_bytes}, {key, key_bytes}})
-            {
-                if (rns_overlap(scratch, s.total, op.first, op.second))
-                    throw std::invalid_argument("out or the scratch overlaps an operand!");
-                // out may be exactly x or exactly y: the last read of both (inner_product_tensor) precedes mod_down's
-                // first write on the stream.  Any other overlap is refused
-                if (rns_overlap(out, out_bytes, op.first, op.second) && (op.first == key || op.first != out))
-                    throw std::invalid_argument("out or the scratch overlaps an operand!");
-            }
-            if (rns_overlap(out, out_bytes, scratch, s.total))
-                throw std::invalid_argument("The scratch overlaps out!");
-            // the batches of the transforms are ints; the grids of mod_up and mod_down: as their own launches check
-            if (static_cast<unsigned long long>(D) * static_cast<unsigned>(count) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
-                throw std::invalid_argument("Invalid count!");
+            need_int_batch(static_cast<unsigned long long>(D) * static_cast<unsigned>(count) * static_cast<unsigned>(M),
+                           "Invalid count!");
             (void) column_tiles(cols, kern::KS_NT, "Invalid count!");
             (void) column_tiles(2 * cols, kern::BC_NT, "Invalid count!");
-            kern::RelinArgs<T> args{};
-            for (int m = 0; m < M; m++)
-                args.limbs.v[m] = static_cast<unsigned char>(limbs[m]);
-            for (int j = 0; j < L; j++)
-                args.p_mod_q[j] = p_mod_q[j], args.p_mod_q_shoup[j] = p_mod_q_shoup[j];
-            T* a = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.a);
-            T* d2 = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.c_coeff);
-            T* acc = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.inner_out);
-            const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
-            const T* x1 = x + cols * L;
-            const T* y1 = y + cols * L;
-            // the grid limits of both kernels, before the first launch
-            host::relin_top_launch<T>(x1, y1, d2, consts, count, L, M, n, false, stream);
-            host::relin_inner_launch<T>(a, key, acc, consts, x, y, args, D, count, L, M, KM, n, false, stream);
-
-            host::relin_top_launch<T>(x1, y1, d2, consts, count, L, M, n, true, stream);
-            ntt_q_i->execute(d2, d2, count * L, stream);
-            mod_up(d2, a, count, BaseConvMode::centred, stream);
-            ntt_full_f->execute(a, a, D * count * M, stream);
-            host::relin_inner_launch<T>(a, key, acc, consts, x, y, args, D, count, L, M, KM, n, true, stream);
-            finish(acc, out, 2 * count, output_ntt, rescale, stream);
         }
 
-        // xs, ys: host arrays of `terms` pointers to T[2][count][L][N]; everything else as multiply_relinearize
-        void multiply_relinearize_sum(const T* const* xs, const T* const* ys, int terms, const T* key, T* out, int count,
-                                      bool output_ntt, bool rescale, void* scratch, hipStream_t stream) const
+        struct RelinScratch // the regions of ks_scratch(count, 2): the digits, the top term, the accumulators
+        {
+            T *a, *d2, *acc;
+        };
+
+        // What multiply_relinearize (one term: xs = &x, ys = &y) and multiply_relinearize_sum share up to the first
+        // launch: every refusal of the call, in one order, the kernel arguments of the base and the regions of the
+        // scratch.  Returns false when count is 0 and nothing is to be launched
+        bool relin_prepare(const T* const* xs, const T* const* ys, int terms, const T* key, const T* out, int count,
+                           bool rescale, void* scratch, kern::RelinArgs<T>& args, RelinScratch& r) const
         {
             need_transforms();
             if (rescale)
@@ -978,59 +922,79 @@ namespace gpuntt
             const KsScratch s = ks_scratch<T>(L, M, D, n, count, 2); // checks count
             if (terms < 1 || terms > KEYSWITCH_MAX_TERMS)
                 throw std::invalid_argument("Invalid terms!");
-            if (xs == nullptr || ys == nullptr || key == nullptr || out == nullptr || scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
-            kern::RelinSumArgs<T> args{};
-            args.terms = terms;
+            need_pointers(xs, ys, key, out, scratch);
             for (int t = 0; t < terms; t++)
-            {
-                if (xs[t] == nullptr || ys[t] == nullptr)
-                    throw std::invalid_argument("null pointer argument");
-                args.x[t] = xs[t], args.y[t] = ys[t];
-            }
-            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+                need_pointers(xs[t], ys[t]);
+            need_aligned_scratch(scratch);
             if (count == 0)
-                return;
+                return false;
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
             const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T);
             const std::uint64_t out_bytes = cols * (rescale ? Lk : L) * 2 * sizeof(T);
             const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
-            // out may be exactly any x[t] or y[t]: the last read of them (inner_product_tensor_sum) precedes mod_down's
+            const char* operand = "out or the scratch overlaps an operand!";
+            // out may be exactly any x[t] or y[t]: the last read of them (inner_product_tensor[_sum]) precedes mod_down's
             // first write on the stream.  Any other overlap is refused
-            if (rns_overlap(scratch, s.total, key, key_bytes) || rns_overlap(out, out_bytes, key, key_bytes))
-                throw std::invalid_argument("out or the scratch overlaps an operand!");
-            for (int t = 0; t < 2 * terms; t++)
+            refuse_overlap({{scratch, s.total}, {out, out_bytes}}, {{key, key_bytes}}, operand);
+            for (int t = 0; t < terms; t++)
             {
-                const T* op = t < terms ? xs[t] : ys[t - terms];
-                if (rns_overlap(scratch, s.total, op, ct_bytes) || (rns_overlap(out, out_bytes, op, ct_bytes) && op != out))
-                    throw std::invalid_argument("out or the scratch overlaps an operand!");
+                refuse_overlap({{scratch, s.total}}, {{xs[t], ct_bytes}, {ys[t], ct_bytes}}, operand);
+                refuse_overlap({{out, out_bytes}}, {{xs[t], ct_bytes, true}, {ys[t], ct_bytes, true}}, operand);
             }
-            if (rns_overlap(out, out_bytes, scratch, s.total))
-                throw std::invalid_argument("The scratch overlaps out!");
-            // the batches of the transforms are ints; the grids of mod_up and mod_down: as their own launches check
-            if (static_cast<unsigned long long>(D) * static_cast<unsigned>(count) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
-                throw std::invalid_argument("Invalid count!");
-            (void) column_tiles(cols, kern::KS_NT, "Invalid count!");
-            (void) column_tiles(2 * cols, kern::BC_NT, "Invalid count!");
-            for (int m = 0; m < M; m++)
-                args.r.limbs.v[m] = static_cast<unsigned char>(limbs[m]);
-            for (int j = 0; j < L; j++)
-                args.r.p_mod_q[j] = p_mod_q[j], args.r.p_mod_q_shoup[j] = p_mod_q_shoup[j];
-            T* a = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.a);
-            T* d2 = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.c_coeff);
-            T* acc = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.inner_out);
+            refuse_overlap({{out, out_bytes}}, {{scratch, s.total}}, "The scratch overlaps out!");
+            relin_limits(cols, count);
+            fill_base(args.limbs.v, args.p_mod_q, args.p_mod_q_shoup);
+            r = RelinScratch{words_at<T>(scratch, s.a), words_at<T>(scratch, s.c_coeff), words_at<T>(scratch, s.inner_out)};
+            return true;
+        }
+
+        // x, y: T[2][count][L][N]; out: T[2][count][L][N], rescale: T[2][count][Lk][N]; key: T[D_key][2][KM][N]; the
+        // scratch: ks_scratch(count, 2)
+        void multiply_relinearize(const T* x, const T* y, const T* key, T* out, int count, bool output_ntt, bool rescale,
+                                  void* scratch, hipStream_t stream) const
+        {
+            kern::RelinArgs<T> args{};
+            RelinScratch r{};
+            if (!relin_prepare(&x, &y, 1, key, out, count, rescale, scratch, args, r))
+                return;
+            const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const T* x1 = x + cols * L;
+            const T* y1 = y + cols * L;
+            // the grid limits of both kernels, before the first launch
+            host::relin_top_launch<T>(x1, y1, r.d2, consts, count, L, M, n, false, stream);
+            host::relin_inner_launch<T>(r.a, key, r.acc, consts, x, y, args, D, count, L, M, KM, n, false, stream);
+
+            host::relin_top_launch<T>(x1, y1, r.d2, consts, count, L, M, n, true, stream);
+            ntt_q_i->execute(r.d2, r.d2, count * L, stream);
+            mod_up(r.d2, r.a, count, BaseConvMode::centred, stream);
+            ntt_full_f->execute(r.a, r.a, D * count * M, stream);
+            host::relin_inner_launch<T>(r.a, key, r.acc, consts, x, y, args, D, count, L, M, KM, n, true, stream);
+            finish(r.acc, out, 2 * count, output_ntt, rescale, stream);
+        }
+
+        // xs, ys: host arrays of `terms` pointers to T[2][count][L][N]; everything else as multiply_relinearize
+        void multiply_relinearize_sum(const T* const* xs, const T* const* ys, int terms, const T* key, T* out, int count,
+                                      bool output_ntt, bool rescale, void* scratch, hipStream_t stream) const
+        {
+            kern::RelinSumArgs<T> args{};
+            RelinScratch r{};
+            if (!relin_prepare(xs, ys, terms, key, out, count, rescale, scratch, args.r, r))
+                return;
+            args.terms = terms;
+            for (int t = 0; t < terms; t++)
+                args.x[t] = xs[t], args.y[t] = ys[t];
             const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
             // the grid limits of both kernels, before the first launch
-            host::relin_sum_top_launch<T>(d2, consts, args, count, L, M, n, false, stream);
-            host::relin_sum_inner_launch<T>(a, key, acc, consts, args, D, count, L, M, KM, n, false, stream);
+            host::relin_sum_top_launch<T>(r.d2, consts, args, count, L, M, n, false, stream);
+            host::relin_sum_inner_launch<T>(r.a, key, r.acc, consts, args, D, count, L, M, KM, n, false, stream);
 
-            host::relin_sum_top_launch<T>(d2, consts, args, count, L, M, n, true, stream);
-            ntt_q_i->execute(d2, d2, count * L, stream);
-            mod_up(d2, a, count, BaseConvMode::centred, stream);
-            ntt_full_f->execute(a, a, D * count * M, stream);
-            host::relin_sum_inner_launch<T>(a, key, acc, consts, args, D, count, L, M, KM, n, true, stream);
-            finish(acc, out, 2 * count, output_ntt, rescale, stream);
+            host::relin_sum_top_launch<T>(r.d2, consts, args, count, L, M, n, true, stream);
+            ntt_q_i->execute(r.d2, r.d2, count * L, stream);
+            mod_up(r.d2, r.a, count, BaseConvMode::centred, stream);
+            ntt_full_f->execute(r.a, r.a, D * count * M, stream);
+            host::relin_sum_inner_launch<T>(r.a, key, r.acc, consts, args, D, count, L, M, KM, n, true, stream);
+            finish(r.acc, out, 2 * count, output_ntt, rescale, stream);
         }
 
         // c01: T[2][count][L][N], c2: T[count][L][N], out: T[2][count][L][N]; key: T[D_key][2][KM][N]; the scratch:
@@ -1040,34 +1004,24 @@ namespace gpuntt
         {
             need_transforms();
             const KsScratch s = ks_scratch<T>(L, M, D, n, count, 2); // checks count
-            if (c01 == nullptr || c2 == nullptr || key == nullptr || out == nullptr || scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
-            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+            need_pointers(c01, c2, key, out, scratch);
+            need_aligned_scratch(scratch);
             if (count == 0)
                 return;
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
             const std::uint64_t low_bytes = cols * L * 2 * sizeof(T), top_bytes = cols * L * sizeof(T);
             const std::uint64_t key_bytes = ((static_cast<std::uint64_t>(D) * 2 * KM) << n) * sizeof(T);
-            for (const auto& op :
-                 {std::pair<const void*, std::uint64_t>{c01, low_bytes}, {c2, top_bytes}, {key, key_bytes}})
-                if (rns_overlap(scratch, s.total, op.first, op.second))
-                    throw std::invalid_argument("out or the scratch overlaps an operand!");
+            const char* operand = "out or the scratch overlaps an operand!";
+            refuse_overlap({{scratch, s.total}}, {{c01, low_bytes}, {c2, top_bytes}, {key, key_bytes}}, operand);
             // out may be exactly c01: every word of c01 is read by the lane that later writes it (mod_down_add), or all of
             // it is read before mod_down's first write on the stream (inner_product_seeded).  Any other overlap is refused
-            if (rns_overlap(out, low_bytes, c2, top_bytes) || rns_overlap(out, low_bytes, key, key_bytes) ||
-                (rns_overlap(out, low_bytes, c01, low_bytes) && out != c01) || rns_overlap(c01, low_bytes, c2, top_bytes) ||
-                rns_overlap(c01, low_bytes, key, key_bytes) || rns_overlap(c2, top_bytes, key, key_bytes))
-                throw std::invalid_argument("out or the scratch overlaps an operand!");
-            if (rns_overlap(out, low_bytes, scratch, s.total))
-                throw std::invalid_argument("The scratch overlaps out!");
-            // the batches of the transforms are ints; the grids of mod_up and mod_down: as their own launches check
-            if (static_cast<unsigned long long>(D) * static_cast<unsigned>(count) * static_cast<unsigned>(M) > 0x7FFFFFFFull)
-                throw std::invalid_argument("Invalid count!");
-            (void) column_tiles(cols, kern::KS_NT, "Invalid count!");
-            (void) column_tiles(2 * cols, kern::BC_NT, "Invalid count!");
-            T* a = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.a);
-            T* acc = reinterpret_cast<T*>(static_cast<char*>(scratch) + s.inner_out);
+            refuse_overlap({{out, low_bytes}}, {{c2, top_bytes}, {key, key_bytes}, {c01, low_bytes, true}}, operand);
+            refuse_overlap({{c01, low_bytes}}, {{c2, top_bytes}, {key, key_bytes}}, operand);
+            refuse_overlap({{c2, top_bytes}}, {{key, key_bytes}}, operand);
+            refuse_overlap({{out, low_bytes}}, {{scratch, s.total}}, "The scratch overlaps out!");
+            relin_limits(cols, count);
+            T* a = words_at<T>(scratch, s.a);
+            T* acc = words_at<T>(scratch, s.inner_out);
             if (!input_ntt)
             {
                 // c01 is in coefficient form: it joins after the division, in mod_down's own epilogue
@@ -1081,10 +1035,7 @@ namespace gpuntt
                 return;
             }
             kern::RelinArgs<T> args{};
-            for (int m = 0; m < M; m++)
-                args.limbs.v[m] = static_cast<unsigned char>(limbs[m]);
-            for (int j = 0; j < L; j++)
-                args.p_mod_q[j] = p_mod_q[j], args.p_mod_q_shoup[j] = p_mod_q_shoup[j];
+            fill_base(args.limbs.v, args.p_mod_q, args.p_mod_q_shoup);
             const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
             // the grid limit of the kernel, before the first launch
             host::relin_seeded_launch<T>(a, key, acc, consts, c01, args, D, count, L, M, KM, n, false, stream);
@@ -1095,23 +1046,29 @@ namespace gpuntt
 
         // Key material (keygen.hip)
 
+        // What lift_small and lift_centred share between their own refusals and their launches; in: [polys][N] words of
+        // in_word bytes, out: T[polys][B][N].  Returns false when polys is 0 and nothing is to be launched
+        bool lift_prepare(const void* in, std::uint64_t in_word, const T* out, int polys, int B) const
+        {
+            if (polys < 0)
+                throw std::invalid_argument("Invalid polys!");
+            need_pointers(in, out);
+            need_int_batch(static_cast<unsigned long long>(polys) * static_cast<unsigned>(B), "Invalid polys!");
+            if (polys == 0)
+                return false;
+            const std::uint64_t cols = static_cast<std::uint64_t>(polys) << n;
+            refuse_overlap({{out, cols * B * sizeof(T)}}, {{in, cols * in_word}}, "The lift's input and output overlap!");
+            return true;
+        }
+
         // small: int32[polys][N] -> out: T[polys][B][N], B = M (full_base) or L
         void lift_small(const std::int32_t* small, T* out, int polys, bool full_base, bool to_ntt, hipStream_t stream) const
         {
             if (to_ntt)
                 need_transforms();
-            if (polys < 0)
-                throw std::invalid_argument("Invalid polys!");
-            if (small == nullptr || out == nullptr)
-                throw std::invalid_argument("null pointer argument");
             const int B = full_base ? M : L;
-            if (static_cast<unsigned long long>(polys) * static_cast<unsigned>(B) > 0x7FFFFFFFull) // the transforms' batch
-                throw std::invalid_argument("Invalid polys!");
-            if (polys == 0)
+            if (!lift_prepare(small, sizeof(std::int32_t), out, polys, B))
                 return;
-            const std::uint64_t cols = static_cast<std::uint64_t>(polys) << n;
-            if (rns_overlap(small, cols * sizeof(std::int32_t), out, cols * B * sizeof(T)))
-                throw std::invalid_argument("The lift's input and output overlap!");
             const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
             host::keygen_lift_launch<T>(small, out, consts, polys, B, M, n, false, stream);
             host::keygen_lift_launch<T>(small, out, consts, polys, B, M, n, true, stream);
@@ -1136,18 +1093,9 @@ namespace gpuntt
             {
                 throw std::invalid_argument("Invalid plaintext modulus!");
             }
-            if (polys < 0)
-                throw std::invalid_argument("Invalid polys!");
-            if (words == nullptr || out == nullptr)
-                throw std::invalid_argument("null pointer argument");
             const int B = full_base ? M : L;
-            if (static_cast<unsigned long long>(polys) * static_cast<unsigned>(B) > 0x7FFFFFFFull) // the transforms' batch
-                throw std::invalid_argument("Invalid polys!");
-            if (polys == 0)
+            if (!lift_prepare(words, sizeof(T), out, polys, B))
                 return;
-            const std::uint64_t cols = static_cast<std::uint64_t>(polys) << n;
-            if (rns_overlap(words, cols * sizeof(T), out, cols * B * sizeof(T)))
-                throw std::invalid_argument("The lift's input and output overlap!");
             const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
             host::lift_centred_launch<T>(words, out, consts, t, polys, B, M, n, false, stream);
             host::lift_centred_launch<T>(words, out, consts, t, polys, B, M, n, true, stream);
@@ -1162,15 +1110,13 @@ namespace gpuntt
                 throw std::invalid_argument("Invalid count!");
             if (plain_count != 1 && plain_count != count)
                 throw std::invalid_argument("Invalid plain_count!");
-            if (ct == nullptr || pt == nullptr || out == nullptr)
-                throw std::invalid_argument("null pointer argument");
+            need_pointers(ct, pt, out);
             if (count == 0)
                 return;
             const std::uint64_t stack = (static_cast<std::uint64_t>(L) << n) * sizeof(T);
             const std::uint64_t ct_bytes = 2 * stack * count, pt_bytes = stack * plain_count;
             // out may be exactly ct: every word is written by the lane that read it, after its loads
-            if ((rns_overlap(out, ct_bytes, ct, ct_bytes) && out != ct) || rns_overlap(out, ct_bytes, pt, pt_bytes))
-                throw std::invalid_argument("out overlaps an operand!");
+            refuse_overlap({{out, ct_bytes}}, {{ct, ct_bytes, true}, {pt, pt_bytes}}, "out overlaps an operand!");
             const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
             host::multiply_plain_launch<T>(ct, pt, out, consts, count, plain_count, L, M, n, false, stream);
             host::multiply_plain_launch<T>(ct, pt, out, consts, count, plain_count, L, M, n, true, stream);
@@ -1182,11 +1128,38 @@ namespace gpuntt
                 throw std::invalid_argument("Invalid keys!");
             return rns_align(((static_cast<size_t>(keys) * D * M) << n) * sizeof(T));
         }
-        size_t encrypt_scratch(int count) const // E: T[count][L][N]
+        size_t lifted_scratch(int count, int polys) const // what lift_small makes of int32[polys][count][N] over the q-base
         {
             if (count < 0)
                 throw std::invalid_argument("Invalid count!");
-            return rns_align(((static_cast<size_t>(count) * L) << n) * sizeof(T));
+            return rns_align(((static_cast<size_t>(polys) * count * L) << n) * sizeof(T));
+        }
+        size_t encrypt_scratch(int count) const { return lifted_scratch(count, 1); }        // E: T[count][L][N]
+        size_t encrypt_public_scratch(int count) const { return lifted_scratch(count, 3); } // (U, E0, E1): T[3][count][L][N]
+
+        // What encrypt_symmetric (polys = 1, key = s, L limbs read) and encrypt_public (polys = 3, key = pk, 2 L limbs)
+        // share up to the first launch: every refusal of the call, in one order.  small: int32[polys][count][N].  Returns
+        // false when count is 0 and nothing is to be launched
+        bool encrypt_prepare(const T* key, int key_limbs, const std::int32_t* small, int polys, const T* message,
+                             const T* out, int count, const void* scratch) const
+        {
+            need_transforms();
+            const size_t e_bytes = lifted_scratch(count, polys); // checks count
+            need_pointers(key, small, out, scratch);
+            need_aligned_scratch(scratch);
+            need_int_batch(static_cast<unsigned long long>(polys) * static_cast<unsigned>(count) * static_cast<unsigned>(L),
+                           "Invalid count!");
+            if (count == 0)
+                return false;
+            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
+            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T);
+            refuse_overlap({{scratch, e_bytes}, {out, ct_bytes}},
+                           {{key, (static_cast<std::uint64_t>(key_limbs) << n) * sizeof(T)},
+                            {small, polys * cols * sizeof(std::int32_t)},
+                            {message, cols * L * sizeof(T)}},
+                           "out or the scratch overlaps an operand!");
+            refuse_overlap({{out, ct_bytes}}, {{scratch, e_bytes}}, "The scratch overlaps out!");
+            return true;
         }
 
         // s: T[M][N], s_from: T[keys][M][N], errors: int32[keys][D][N], key_ptrs: a host array of `keys` device
@@ -1201,34 +1174,26 @@ namespace gpuntt
             for (int m = 0; m < M; m++)
                 if (limbs[m] != m)
                     throw std::invalid_argument("Keys are generated by the plan of the level they are laid out for!");
-            if (s == nullptr || s_from == nullptr || errors == nullptr || key_ptrs == nullptr || scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
+            need_pointers(s, s_from, errors, key_ptrs, scratch);
             for (int g = 0; g < keys; g++)
-                if (key_ptrs[g] == nullptr)
-                    throw std::invalid_argument("null pointer argument");
-            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
+                need_pointers(key_ptrs[g]);
+            need_aligned_scratch(scratch);
             if (keys == 0)
                 return;
             const std::uint64_t stack = (static_cast<std::uint64_t>(M) << n) * sizeof(T);
             const std::uint64_t key_bytes = stack * 2 * D, from_bytes = stack * keys;
             const std::uint64_t err_bytes = ((static_cast<std::uint64_t>(keys) * D) << n) * sizeof(std::int32_t);
-            const std::pair<const void*, std::uint64_t> inputs[] = {{s, stack}, {s_from, from_bytes}, {errors, err_bytes}};
-            for (const auto& op : inputs)
+            for (const host::RnsRange& op : {host::RnsRange{s, stack}, {s_from, from_bytes}, {errors, err_bytes}})
             {
-                if (rns_overlap(scratch, e_bytes, op.first, op.second))
-                    throw std::invalid_argument("The scratch overlaps an operand!");
+                refuse_overlap({{scratch, e_bytes}}, {op}, "The scratch overlaps an operand!");
                 for (int g = 0; g < keys; g++)
-                    if (rns_overlap(key_ptrs[g], key_bytes, op.first, op.second))
-                        throw std::invalid_argument("A key overlaps an operand!");
+                    refuse_overlap({{key_ptrs[g], key_bytes}}, {op}, "A key overlaps an operand!");
             }
             for (int g = 0; g < keys; g++)
             {
-                if (rns_overlap(key_ptrs[g], key_bytes, scratch, e_bytes))
-                    throw std::invalid_argument("The scratch overlaps a key!");
+                refuse_overlap({{key_ptrs[g], key_bytes}}, {{scratch, e_bytes}}, "The scratch overlaps a key!");
                 for (int o = g + 1; o < keys; o++)
-                    if (rns_overlap(key_ptrs[g], key_bytes, key_ptrs[o], key_bytes))
-                        throw std::invalid_argument("Two keys overlap!");
+                    refuse_overlap({{key_ptrs[g], key_bytes}}, {{key_ptrs[o], key_bytes}}, "Two keys overlap!");
             }
             kern::KeygenArgs<T> args{};
             for (int g = 0; g < keys; g++)
@@ -1252,27 +1217,9 @@ namespace gpuntt
         void encrypt_symmetric(const T* s, const std::int32_t* errors, const T* message, T* out, int count, void* scratch,
                                hipStream_t stream) const
         {
-            need_transforms();
-            const size_t e_bytes = encrypt_scratch(count); // checks count
-            if (s == nullptr || errors == nullptr || out == nullptr || scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
-            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
-            if (static_cast<unsigned long long>(count) * static_cast<unsigned>(L) > 0x7FFFFFFFull)
-                throw std::invalid_argument("Invalid count!");
-            if (count == 0)
+            if (!encrypt_prepare(s, L, errors, 1, message, out, count, scratch))
                 return;
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
-            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T), msg_bytes = cols * L * sizeof(T);
-            const std::pair<const void*, std::uint64_t> inputs[] = {
-                {s, (static_cast<std::uint64_t>(L) << n) * sizeof(T)}, {errors, cols * sizeof(std::int32_t)},
-                {message, message != nullptr ? msg_bytes : 0}};
-            for (const auto& op : inputs)
-                if (op.first != nullptr &&
-                    (rns_overlap(scratch, e_bytes, op.first, op.second) || rns_overlap(out, ct_bytes, op.first, op.second)))
-                    throw std::invalid_argument("out or the scratch overlaps an operand!");
-            if (rns_overlap(out, ct_bytes, scratch, e_bytes))
-                throw std::invalid_argument("The scratch overlaps out!");
             kern::KeygenArgs<T> args{};
             args.group[0] = out;
             for (int j = 0; j < L; j++)
@@ -1304,12 +1251,6 @@ namespace gpuntt
                 return 0;
             return rns_align(((static_cast<size_t>(components) * count * L) << n) * sizeof(T));
         }
-        size_t encrypt_public_scratch(int count) const // (U, E0, E1): T[3][count][L][N]
-        {
-            if (count < 0)
-                throw std::invalid_argument("Invalid count!");
-            return rns_align(((static_cast<size_t>(3) * count * L) << n) * sizeof(T));
-        }
 
         // ct: T[components][count][L][N], s: T[M][N] (the first L limbs are read), out: T[count][L][N]; the scratch:
         // phase_scratch(count, components, input_ntt)
@@ -1319,26 +1260,26 @@ namespace gpuntt
             if (!input_ntt || !output_ntt)
                 need_transforms();
             const size_t s_bytes = phase_scratch(count, components, input_ntt); // checks components and count
-            if (ct == nullptr || s == nullptr || out == nullptr || (!input_ntt && scratch == nullptr))
-                throw std::invalid_argument("null pointer argument");
-            if (!input_ntt && reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
-            if (static_cast<unsigned long long>(components) * static_cast<unsigned>(count) * static_cast<unsigned>(L) >
-                0x7FFFFFFFull) // the transforms' batch
-                throw std::invalid_argument("Invalid count!");
+            need_pointers(ct, s, out);
+            if (!input_ntt)
+            {
+                need_pointers(scratch);
+                need_aligned_scratch(scratch);
+            }
+            need_int_batch(static_cast<unsigned long long>(components) * static_cast<unsigned>(count) * static_cast<unsigned>(L),
+                           "Invalid count!"); // the transforms' batch
             if (count == 0)
                 return;
             const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
             const std::uint64_t out_bytes = cols * L * sizeof(T), ct_bytes = out_bytes * components;
             const std::uint64_t sec_bytes = (static_cast<std::uint64_t>(L) << n) * sizeof(T);
             // out may be exactly ct in NTT form: every word of component 0 is written by the lane that read it
-            if ((rns_overlap(out, out_bytes, ct, ct_bytes) && !(input_ntt && out == ct)) ||
-                rns_overlap(out, out_bytes, s, sec_bytes))
-                throw std::invalid_argument("out overlaps an operand!");
-            if (!input_ntt && (rns_overlap(scratch, s_bytes, ct, ct_bytes) || rns_overlap(scratch, s_bytes, s, sec_bytes)))
-                throw std::invalid_argument("out or the scratch overlaps an operand!");
-            if (!input_ntt && rns_overlap(scratch, s_bytes, out, out_bytes))
-                throw std::invalid_argument("The scratch overlaps out!");
+            refuse_overlap({{out, out_bytes}}, {{ct, ct_bytes, input_ntt}, {s, sec_bytes}}, "out overlaps an operand!");
+            if (!input_ntt)
+            {
+                refuse_overlap({{scratch, s_bytes}}, {{ct, ct_bytes}, {s, sec_bytes}}, "out or the scratch overlaps an operand!");
+                refuse_overlap({{scratch, s_bytes}}, {{out, out_bytes}}, "The scratch overlaps out!");
+            }
             const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
             const T* c = input_ntt ? ct : static_cast<const T*>(scratch);
             host::decrypt_phase_launch<T>(c, s, out, consts, count, components, L, M, n, false, stream);
@@ -1354,27 +1295,8 @@ namespace gpuntt
         void encrypt_public(const T* pk, const std::int32_t* small, const T* message, T* out, int count, void* scratch,
                             hipStream_t stream) const
         {
-            need_transforms();
-            const size_t e_bytes = encrypt_public_scratch(count); // checks count
-            if (pk == nullptr || small == nullptr || out == nullptr || scratch == nullptr)
-                throw std::invalid_argument("null pointer argument");
-            if (reinterpret_cast<uintptr_t>(scratch) % 256 != 0)
-                throw std::invalid_argument("The scratch is not 256-byte aligned!");
-            if (3ull * static_cast<unsigned>(count) * static_cast<unsigned>(L) > 0x7FFFFFFFull)
-                throw std::invalid_argument("Invalid count!");
-            if (count == 0)
+            if (!encrypt_prepare(pk, 2 * L, small, 3, message, out, count, scratch))
                 return;
-            const std::uint64_t cols = static_cast<std::uint64_t>(count) << n;
-            const std::uint64_t ct_bytes = cols * L * 2 * sizeof(T), msg_bytes = cols * L * sizeof(T);
-            const std::pair<const void*, std::uint64_t> inputs[] = {
-                {pk, (static_cast<std::uint64_t>(2 * L) << n) * sizeof(T)}, {small, 3 * cols * sizeof(std::int32_t)},
-                {message, message != nullptr ? msg_bytes : 0}};
-            for (const auto& op : inputs)
-                if (op.first != nullptr &&
-                    (rns_overlap(scratch, e_bytes, op.first, op.second) || rns_overlap(out, ct_bytes, op.first, op.second)))
-                    throw std::invalid_argument("out or the scratch overlaps an operand!");
-            if (rns_overlap(out, ct_bytes, scratch, e_bytes))
-                throw std::invalid_argument("The scratch overlaps out!");
             T* e = static_cast<T*>(scratch);
             const T* consts = reinterpret_cast<const T*>(ws + lay.inner);
             host::keygen_lift_launch<T>(small, e, consts, 3 * count, L, M, n, false, stream);
@@ -1753,14 +1675,14 @@ namespace gpuntt
     {
         p_->need_transforms();
         const KsScratch s = ks_scratch<T>(p_->L, p_->M, p_->D, p_->n, count, components);
-        if (scratch_device == nullptr)
-            throw std::invalid_argument("null pointer argument");
-        T* a = reinterpret_cast<T*>(static_cast<char*>(scratch_device) + s.a);
-        if (device_c_in != nullptr && device_out != nullptr && count > 0 &&
-            (rns_overlap(scratch_device, s.total, device_c_in, (static_cast<size_t>(count) << p_->n) * p_->L * sizeof(T)) ||
-             rns_overlap(scratch_device, s.total, device_out,
-                        (static_cast<size_t>(count) << p_->n) * p_->L * components * sizeof(T))))
-            throw std::invalid_argument("The scratch overlaps an operand!");
+        need_pointers(scratch_device);
+        T* a = words_at<T>(scratch_device, s.a);
+        if (device_c_in != nullptr && device_out != nullptr && count > 0) // (decompose and switch_digits refuse the rest)
+        {
+            const std::uint64_t c_bytes = (static_cast<std::uint64_t>(count) << p_->n) * p_->L * sizeof(T);
+            refuse_overlap({{scratch_device, s.total}}, {{device_c_in, c_bytes}, {device_out, c_bytes * components}},
+                           "The scratch overlaps an operand!");
+        }
         p_->decompose(device_c_in, a, count, input_ntt, scratch_device, stream);
         p_->switch_digits(a, device_key, device_out, count, components, output_ntt, scratch_device, stream);
     }
